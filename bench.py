@@ -1,16 +1,24 @@
 #!/usr/bin/env python
 """bench.py -- proposal images/sec of the RPN hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path (predictor.py:50-56 + NMS(300)) over one batch of synthetic
 500x500x3 images per GPU: conv backbone -> RPN head -> fused delta-decode + NMS -> (N > 1) one RCCL
-all-gather of the proposal records.  Inputs are resident in HBM before the timed region.
+all-gather of the proposal records.  Inputs are resident in HBM before the timed region; weights and images are
+seeded, so the same arguments give the same inputs in every run.
 At N = 1 the workload is BASELINE.json configs[1] (batch 8, VGG16 backbone + RPN head).
 Images shard over ranks (weak scaling: the per-GPU batch is fixed), no other data-path collective.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (f16x3 / bf16x3: the persistent LDS-DMA
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, 2 untimed steps, W warm-up steps,
+exactly K timed steps, then the line (`metric`, `value` = images/s over the K steps, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, the workload `config` and the `device`).  `--dump-outputs DIR` writes what the last timed
+step returned to its caller as DIR/<name>.npy (N = 1: boxes, scores, valid, indices; N > 1: the all-gathered boxes,
+scores, valid of every rank), float32, integers as float64.
+
+Everything below is measured with `--full` only (`--layers` implies it); its headline carries HIP events around the
+dominant kernel's launches in the timed steps.  `roofline` is for the dominant kernel (f16x3 / bf16x3: the persistent LDS-DMA
 16x16x32-MFMA conv; f32: the 128x128 f32-MFMA implicit-GEMM conv), found by an untimed pre-pass and then timed
 live with HIP events recorded on the launch stream around its launches in the K timed steps (one launch per step,
 round robin, when K samples every launch at least twice; else all of them);
@@ -158,7 +166,15 @@ def parse_args():
     ap.add_argument("--sustained-seconds", type=float, default=1.0,
                     help="also loop the headline step for at least this long (wall clock) and report it as `sustained`; 0: off")
     ap.add_argument("--cpu-seconds", type=float, default=18.0, help="time budget of the whole CPU-baseline leg")
-    ap.add_argument("--layers", action="store_true", help="also print the per-layer table to stderr")
+    ap.add_argument("--layers", action="store_true", help="also print the per-layer table to stderr (implies --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline of the dominant kernel, per-op / conv-stack / decode+NMS "
+                         "timings, the sustained leg, self-checks, the configs[2] and exact-f32 legs, the other configs, the "
+                         "multi-GPU legs and the CPU baseline (the --no-* / --sustained-seconds / --cpu-seconds options apply "
+                         "to it).  Default: set up, warm up, time the K steps, print the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0) to DIR/<name>.npy "
+                         "(float32 / float64)")
     return ap.parse_args()
 
 
@@ -887,8 +903,47 @@ def _device_info():
         return {"error": str(exc)}
 
 
+def _headline(args, hp, prop, world, use_dist, overlap, value, ms_per_step):
+    """The fields of the result line that a plain run and a --full run share (the headline and what it describes)."""
+    B = args.batch
+    return {
+        "metric": "proposal images/sec at 500x500x3 VOC batch; NMS boxes/sec",
+        "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+        "dtype_note": {"f32": "float32 in, float32 MFMA accumulate (exact)",
+                       "f32w": "float32 in, float32 MFMA accumulate; the 3x3 convs as Winograd F(4x4,3x3) / F(2x2,3x3): 1/4 / 1/2.25 of the multiply-adds, another summation order",
+                       "f16x3": "float32 operands as hi+lo float16 halves, 3 MFMAs per product, float32 accumulate",
+                       "bf16x3": "float32 operands as hi+lo bfloat16 halves, 3 MFMAs per product, float32 accumulate"
+                       }[args.precision],
+        "config": {"workload": "configs[%d]: %dx%dx3 synthetic batch=%d per GPU, %s backbone + RPN head, %d anchors/cell, "
+                               "decode + NMS(300), %dxMI355X" % ({"c2": 1, "c4": 3, "c5": 4}[args.config], hp["img_size"],
+                                                                  hp["img_size"], B, args.backbone, hp["anchor_count"],
+                                                                  world),
+                   "per_gpu_batch": B, "global_batch": world * B, "img_size": hp["img_size"],
+                   "anchors_per_image": prop.total_anchors, "nms_topn": prop.topn, "iou_threshold": args.iou_threshold,
+                   "weights": "random-init (seeded He-normal)",
+                   "parallelism": "image-sharded dp%d, one RCCL all-gather of proposals" % world,
+                   "nms_overlap": ("decode+NMS of step k on a second HIP stream, overlapping the convs of step k+1"
+                                   + ("; all-gather of step k-1 issued behind the convs of step k" if use_dist else ""))
+                                  if overlap else "serial on the conv stream"},
+        "device": _device_info(),
+    }
+
+
+def _dump_outputs(directory, outputs):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy -- float32 stays float32, integer arrays (valid counts,
+    anchor indices) become float64 (exact) -- so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+
+
 def main():
     args = parse_args()
+    full = args.full or args.layers
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become the launcher (one child per GPU) BEFORE anything initialises HIP in this process
         raise SystemExit(self_launch(args))
@@ -977,11 +1032,12 @@ def main():
             tot[op["kernel"]] = tot.get(op["kernel"], 0.0) + ms
         return max(tot, key=tot.get)
 
-    # untimed pre-pass, BEFORE the warm-up: every op timed, to find the dominant kernel.  The timed region then carries HIP
-    # events only around ITS launches (2 events per launch on the launch stream; events around all 20 ops cost ~2.5 % of a
-    # step).  (Until round 3 this pass -- with its host-side read-back -- sat between the warm-up and the timed region: the
-    # device idled for milliseconds right in front of the K timed steps.)
-    model.set_profiling(2)
+    # untimed pre-pass, BEFORE the warm-up (--full: every op timed, to find the dominant kernel).  The timed region then carries
+    # HIP events only around ITS launches (2 events per launch on the launch stream; events around all 20 ops cost ~2.5 % of a
+    # step); a plain run times no op.  (Until round 3 this pass -- with its host-side read-back -- sat between the warm-up and the
+    # timed region: the device idled for milliseconds right in front of the K timed steps.)
+    if full:
+        model.set_profiling(2)
     for _ in range(2):
         step()
     if overlap and use_dist:
@@ -990,20 +1046,22 @@ def main():
     # the communicator's streams exist now (the steps above ran its first all-gathers): make sure the NMS side stream still runs
     # BESIDE the conv stream (HIP assigns its four hardware queues in creation order; a shared queue serialises the two silently)
     side_stream_ok = prop.ensure_side_stream() if overlap else None
-    dom = dominant_kernel(model.profile_ms()[0])
-    dom_mask = [op["kernel"] == dom for op in ops]
-    model.set_profiling_mask(dom_mask)
-    # one of its launches per step, round robin (2 events per step), when K gives every launch >= 2 samples;
-    # otherwise all of them in every step
-    rotate = args.steps >= 2 * sum(dom_mask)
-    model.set_profiling_rotate(rotate)
-    model.set_profiling(args.steps)               # (a ring of the last K forwards: the warm-up's fall out of it)
+    if full:
+        dom = dominant_kernel(model.profile_ms()[0])
+        dom_mask = [op["kernel"] == dom for op in ops]
+        model.set_profiling_mask(dom_mask)
+        # one of its launches per step, round robin (2 events per step), when K gives every launch >= 2 samples;
+        # otherwise all of them in every step
+        rotate = args.steps >= 2 * sum(dom_mask)
+        model.set_profiling_rotate(rotate)
+        model.set_profiling(args.steps)           # (a ring of the last K forwards: the warm-up's fall out of it)
     # ---- W untimed warm-up steps, then the timed region: exactly K steps, barrier + synchronize on both sides ----------
     for _ in range(args.warmup):
         step()
     if overlap and use_dist:
         prop.flush_distributed(gather_bufs)
-    nms_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    nms_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if full else None
+    result = None                                 # what the last timed step hands its caller (--dump-outputs)
     fence()
     t0 = time.perf_counter()
     for k in range(args.steps):
@@ -1011,22 +1069,43 @@ def main():
             prop.propose_distributed_pipelined(imgs, gather_bufs)
             continue
         if overlap:
-            prop.propose_async(imgs)              # convs on this stream, decode+NMS on the side stream
+            result = prop.propose_async(imgs)     # convs on this stream, decode+NMS on the side stream
             continue
         deltas, scores = prop.forward(imgs)
-        nms_ev[k][0].record()                     # same stream as the launches (torch's current stream)
+        if full:
+            nms_ev[k][0].record()                 # same stream as the launches (torch's current stream)
         prop_out = prop._boxes[:B], prop._scores[:B], prop._idx[:B], prop._valid[:B]
         prop.decode_nms(deltas, scores, B, *prop_out)
-        nms_ev[k][1].record()
+        if full:
+            nms_ev[k][1].record()
+        result = prop_out[0], prop_out[1], prop_out[3], prop_out[2]
         if world > 1:
             rec = prop.pack_records(prop_out[0], prop_out[1], prop_out[3], out=prop._record_buffer(2, B))
             dist.all_gather_into_tensor(gathered, rec)
+            result = gathered
     if overlap and use_dist:
-        prop.flush_distributed(gather_bufs)       # the last step's NMS + all-gather finish inside the timed region
+        result = prop.flush_distributed(gather_bufs)  # the last step's NMS + all-gather finish inside the timed region
     elif overlap:
         prop.wait()                               # the last step's NMS must finish inside the timed region
     fence()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        # records of every rank (boxes, scores, valid count per image) when the step all-gathers; else (boxes, scores, valid, indices)
+        names = ("boxes", "scores", "valid", "indices")
+        arrays = Proposer.unpack_records(result, M) if isinstance(result, torch.Tensor) else result
+        _dump_outputs(args.dump_outputs, dict(zip(names, arrays)))
+    if not full:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+        if rank == 0:
+            print(json.dumps(_headline(args, hp, prop, world, use_dist, overlap, world * B * args.steps / elapsed,
+                                       1e3 * elapsed / args.steps)), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # mean durations of the dominant kernel's launches over the K timed steps (events were recorded on the launch
     # stream, read here); the other ops' durations come from an untimed post-pass with every op timed
     dom_ms, _kept = model.profile_ms()
@@ -1170,28 +1249,8 @@ def main():
                     "sum_of_op_ms_with_per_op_events": round(sum(last_ms), 3),
                     "conv_launches_per_step": sum(op["launches"] for op in ops),
                     "decode_nms_ms": round(nms_ms, 4)}
-        out = {
-            "metric": "proposal images/sec at 500x500x3 VOC batch; NMS boxes/sec",
-            "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
-            "dtype_note": {"f32": "float32 in, float32 MFMA accumulate (exact)",
-                           "f32w": "float32 in, float32 MFMA accumulate; the 3x3 convs as Winograd F(4x4,3x3) / F(2x2,3x3): 1/4 / 1/2.25 of the multiply-adds, another summation order",
-                           "f16x3": "float32 operands as hi+lo float16 halves, 3 MFMAs per product, float32 accumulate",
-                           "bf16x3": "float32 operands as hi+lo bfloat16 halves, 3 MFMAs per product, float32 accumulate"
-                           }[args.precision],
-            "config": {"workload": "configs[%d]: %dx%dx3 synthetic batch=%d per GPU, %s backbone + RPN head, %d anchors/cell, "
-                                   "decode + NMS(300), %dxMI355X" % ({"c2": 1, "c4": 3, "c5": 4}[args.config], hp["img_size"],
-                                                                      hp["img_size"], B, args.backbone, hp["anchor_count"],
-                                                                      world),
-                       "per_gpu_batch": B, "global_batch": world * B, "img_size": hp["img_size"],
-                       "anchors_per_image": prop.total_anchors, "nms_topn": M, "iou_threshold": args.iou_threshold,
-                       "weights": "random-init (seeded He-normal)",
-                       "parallelism": "image-sharded dp%d, one RCCL all-gather of proposals" % world,
-                       "nms_overlap": ("decode+NMS of step k on a second HIP stream, overlapping the convs of step k+1"
-                                       + ("; all-gather of step k-1 issued behind the convs of step k" if use_dist else ""))
-                                      if overlap else "serial on the conv stream"},
-            "device": _device_info(),
+        out = _headline(args, hp, prop, world, use_dist, overlap, value, ms_per_step)
+        out.update({
             "allgather_ms": None if gather_ms is None else round(gather_ms, 4),
             "rccl_ranks": dist.get_world_size() if dist.is_initialized() else 1,
             "nms_stream_concurrent": side_stream_ok,      # measured (predictor._streams_overlap), rank 0
@@ -1200,7 +1259,7 @@ def main():
             "sustained_images_per_s": None if sustained is None else sustained["images_per_s"],
             "checks": checks,
             "roofline": roofline,
-        }
+        })
         if dist_legs is not None:
             out["multi_gpu_configs"] = dist_legs
         cpu_workers = None

@@ -4,7 +4,7 @@ TAG=$1; A=$2; B=$3; shift 3
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for rep in 1 2; do for L in $A $B; do
   n=$(basename $L .so)
-  RPN_HIP_LIB=$PWD/$L timeout 300 python bench.py --steps 30 --warmup 3 --layers --no-cpu-baseline "$@" > $OUT/bench_$n.json 2> $OUT/layers_$n.txt
+  RPN_HIP_LIB=$PWD/$L timeout 300 python bench.py --full --steps 30 --warmup 3 --layers --no-cpu-baseline "$@" > $OUT/bench_$n.json 2> $OUT/layers_$n.txt
   echo "$n: $(python -c "import json;d=json.load(open('$OUT/bench_$n.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"
 done; done
 RPN_HIP_LIB=$PWD/$A timeout 900 python -m pytest tests/test_gpu_conv.py -m gpu -q --tb=short -p no:cacheprovider -x > $OUT/pytest.log 2>&1; tail -1 $OUT/pytest.log

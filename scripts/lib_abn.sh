@@ -4,7 +4,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for L in "$@"; do
   n=$(basename $L .so)
-  RPN_HIP_LIB=$PWD/$L timeout 300 python bench.py --steps 30 --warmup 3 --layers --no-cpu-baseline --no-extra-legs > $OUT/bench_$n.json 2> $OUT/layers_$n.txt
+  RPN_HIP_LIB=$PWD/$L timeout 300 python bench.py --full --steps 30 --warmup 3 --layers --no-cpu-baseline --no-extra-legs > $OUT/bench_$n.json 2> $OUT/layers_$n.txt
   echo "$n: $(python -c "import json;d=json.load(open('$OUT/bench_$n.json'));print(d['value'], d['ms_per_step'], d['roofline']['frac'])")"
 done
 first=$(basename $1 .so)

@@ -4,8 +4,9 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 export TMPDIR=/tmp
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
-BENCH="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs --sustained-seconds 0 $*"
+BENCH="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra-legs --sustained-seconds 0 $*"
 run() {  # name, counters...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o pmc -- $BENCH > $OUT/$name.json 2> $OUT/$name.log

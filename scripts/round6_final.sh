@@ -19,7 +19,7 @@ if [ "$PART" = "A" ]; then
   timeout -k 10 200 python bench.py --backbone mobilenet_v2 --no-cpu-baseline --no-extra-legs --layers > $OUT/bench_mn8.json 2> $OUT/bench_mn8_layers.txt
   timeout -k 10 200 python bench.py --precision f32 --steps 30 --warmup 3 --no-cpu-baseline --no-extra-legs --layers > $OUT/bench_f32.json 2> $OUT/bench_f32_layers.txt
   timeout -k 10 200 python bench.py --precision f32w --steps 30 --warmup 3 --no-cpu-baseline --no-extra-legs --layers > $OUT/bench_f32w.json 2> $OUT/bench_f32w_layers.txt
-  timeout -k 10 300 python bench.py --force-dist --no-cpu-baseline --no-extra-legs --sustained-seconds 0 > $OUT/bench_forcedist.json 2> /dev/null
+  timeout -k 10 300 python bench.py --full --force-dist --no-cpu-baseline --no-extra-legs --sustained-seconds 0 > $OUT/bench_forcedist.json 2> /dev/null
   [ -f tf_rpn_amd/csrc/librpn_hip_wnstamp.so ] && RPN_HIP_LIB=$PWD/tf_rpn_amd/csrc/librpn_hip_wnstamp.so timeout -k 10 200 python scripts/wn_stamp_probe.py 8,125,256,256 8,250,128,128 8,250,64,128 2>&1 | grep -v amdgpu.ids > $OUT/wn_stamps.txt
   [ -x ab/mfma_rate ] && timeout -k 5 60 ./ab/mfma_rate > $OUT/mfma_f32_rate.txt 2>&1
   timeout -k 10 200 python scripts/bench_bbox.py > $OUT/bbox_c3.json 2> $OUT/bbox_c3.err

@@ -285,11 +285,11 @@ def test_predictor_cli_on_a_folder_of_images(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--force-dist", "--no-extra-legs"], ["--serial-nms", "--steps", "4", "--no-extra-legs"]])
 def test_bench_prints_one_json_line(extra):
-    """The driver's contract: rank 0 prints ONE JSON line on stdout (RCCL's version banner must not land there), with the
-    roofline object; `--force-dist` runs the N > 1 code path on a world-size-1 RCCL group."""
+    """The driver's contract: rank 0 prints ONE JSON line on stdout (RCCL's version banner must not land there); with `--full`
+    it carries the roofline object; `--force-dist` runs the N > 1 code path on a world-size-1 RCCL group."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--steps", "16", "--warmup", "1"] + extra
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "16", "--warmup", "1"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -331,3 +331,41 @@ def test_bench_prints_one_json_line(extra):
     assert set(oc) == {"c1", "c4", "c5", "mobilenet_v2_b8"}
     assert oc["c4"]["value"] > 100 and "batch 32" in oc["c4"]["workload"] and "1024x1024, 15 anchors" in oc["c5"]["workload"]
     assert all(v["unit"] == "images/s" and v["value"] > 0 and v["conv_launches_per_step"] <= 20 for v in oc.values())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [[], ["--force-dist"], ["--serial-nms"]])
+def test_bench_plain_line_and_dumped_outputs(extra, tmp_path):
+    """A plain run (no --full) prints only the headline line, times exactly --steps steps, and --dump-outputs writes the last
+    timed step's proposals: float32 / float64 arrays that equal what the same Proposer returns for the same seeded images."""
+    import json, os, subprocess, sys
+    from tf_rpn_amd.utils import train_utils
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)] + extra
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["dtype"] == "f16x3" and d["unit"] == "images/s" and d["higher_is_better"]
+    assert d["value"] > 100 and abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for key in ("roofline", "sustained", "checks", "c3", "exact_f32", "other_configs", "cpu_baseline", "multi_gpu_configs"):
+        assert key not in d, key
+    names = {"boxes", "scores", "valid"} if "--force-dist" in extra else {"boxes", "scores", "valid", "indices"}
+    assert {f[:-4] for f in os.listdir(str(out))} == names
+    got = {n: np.load(str(out / (n + ".npy"))) for n in names}
+    assert got["boxes"].dtype == np.float32 and got["scores"].dtype == np.float32 and got["valid"].dtype == np.float64
+    # the same images (bench.py: torch.Generator(device="cuda").manual_seed(rank)) through a fresh handle
+    hp = dict(train_utils.get_hyper_params("vgg16", img_size=500, feature_map_shape=31, anchor_ratios=[1.0, 2.0, 0.5],
+                                           anchor_scales=[128, 256, 512]))            # (the table is a mutated global)
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)
+    imgs = torch.rand((8, hp["img_size"], hp["img_size"], 3), generator=gen, device="cuda", dtype=torch.float32)
+    prop = Proposer("vgg16", hyper_params=hp, weights=synthetic_weights("vgg16", hp, seed=1), precision="f16x3", max_batch=8,
+                    iou_threshold=0.7)
+    boxes, scores, valid, idx = prop.propose(imgs)
+    assert np.array_equal(got["valid"], valid.cpu().numpy().astype(np.float64)) and (got["valid"] >= 1).all()
+    assert np.array_equal(got["boxes"], boxes.cpu().numpy()) and np.array_equal(got["scores"], scores.cpu().numpy())
+    if "indices" in names:
+        assert np.array_equal(got["indices"], idx.cpu().numpy().astype(np.float64))

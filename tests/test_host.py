@@ -323,6 +323,20 @@ def test_bench_spawn_ranks_environment_and_failure_handling():
     assert rc == 124 and time.time() - t0 < 30
 
 
+def test_bench_dump_outputs_writes_float32_and_exact_float64(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per returned array; float32 stays float32, integers become float64 exactly."""
+    bench = _bench_module()
+    boxes = torch.rand((2, 300, 4))
+    valid = torch.tensor([300, 7], dtype=torch.int32)
+    idx = torch.arange(600, dtype=torch.int32).reshape(2, 300) * 16 + 2 ** 24
+    bench._dump_outputs(str(tmp_path / "d"), {"boxes": boxes, "valid": valid, "indices": idx})
+    assert sorted(os.listdir(str(tmp_path / "d"))) == ["boxes.npy", "indices.npy", "valid.npy"]
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in ("boxes", "valid", "indices")}
+    assert got["boxes"].dtype == np.float32 and np.array_equal(got["boxes"], boxes.numpy())
+    assert got["valid"].dtype == np.float64 and got["valid"].tolist() == [300.0, 7.0]
+    assert got["indices"].dtype == np.float64 and np.array_equal(got["indices"], idx.numpy().astype(np.int64))
+
+
 def test_bench_gpus_n_without_launcher_fails_cleanly_without_devices():
     """`python bench.py --gpus 2` on a box with fewer than 2 HIP devices: non-zero exit, a message, no hang, no JSON."""
     import subprocess
