@@ -253,6 +253,60 @@ int rpn_model_op_info(const rpn_model *m, int i, char *name, int name_len, char 
 int rpn_model_get_profile(rpn_model *m, float *ms, int n, int *n_forwards);
 
 /* ------------------------------------------------------------------------------------
+ * Training of the RPN head on a FROZEN backbone                   trainer.py:54-69
+ *   The reference fine-tunes the whole Keras model (its base model is trainable); here only rpn_conv, rpn_reg and
+ *   rpn_cls are trained -- there is no backward pass through VGG16 / MobileNetV2.  The loss and Adam forms are TF 2.0.0's,
+ *   restated from its sources as recalled (tf_rpn_amd/csrc/train_kernels.hip).  Every reduction has a fixed order and
+ *   there are no floating-point atomics: a call is bit-identical from run to run.
+ *
+ * reg_loss(y_true, y_pred) + cls_loss(y_true, y_pred)      utils/train_utils.py:164-185, :146-162
+ *   d_reg_true (B,A,4) bbox_deltas, d_reg_pred (B,F,F,4K) = (B,A,4); d_cls_true (B,A) labels in {1, 0, -1},
+ *   d_cls_pred (B,A) probabilities.  d_losses <- [reg_loss, cls_loss]:
+ *     reg: Huber (delta 1) per element, summed over the 4 coordinates, over the anchors whose true deltas are not all
+ *          zero, / max(1, n_pos);
+ *     cls: keras BinaryCrossentropy on probabilities (clip to [1e-7, 1 - 1e-7], log(. + 1e-7)) averaged over every
+ *          entry of the batch with label != -1; NaN when there is none (its gradient is then zero).
+ *   d_grad_reg (B,A,4) / d_grad_cls (B,A) (each may be NULL): the gradients of the two losses with respect to d_reg_pred
+ *   and d_cls_pred (d/dp; zero where the clip is active).  d_ws: rpn_rpn_losses_workspace_bytes(B, A) bytes.
+ * ---------------------------------------------------------------------------------- */
+size_t rpn_rpn_losses_workspace_bytes(int B, int A);
+int rpn_rpn_losses(const float *d_reg_true, const float *d_reg_pred, const float *d_cls_true, const float *d_cls_pred,
+                   int B, int A, float *d_losses, float *d_grad_reg, float *d_grad_cls, void *d_ws, size_t ws_bytes,
+                   void *stream);
+/* weight gradient of a 3x3 stride-1 'same' conv (the backward of rpn_conv's Conv2D, models/rpn_vgg16.py:18), single-layer entry
+ * like rpn_conv2d: d_x (B,H,W,Cin), d_dy (B,H,W,Cout) -> d_dw (3,3,Cin,Cout) HWIO with
+ * dw[r][s][ci][co] = sum_{b,y,x} x[b][y+r-1][x+s-1][ci] dy[b][y][x][co] (zero padding), d_db (Cout) = sum of dy, or NULL.
+ * Exact float32 products on the float32 MFMA, float32 sums over four fixed ranges of pixels added as (l0 + l1) + (l2 + l3).
+ * Cin, Cout multiples of 4.  d_ws: rpn_conv3x3_wgrad_workspace_bytes(...) bytes. */
+size_t rpn_conv3x3_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout);
+int rpn_conv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw,
+                      float *d_db, void *d_ws, size_t ws_bytes, void *stream);
+/* rpn_model.compile(optimizer=Adam, loss=[reg_loss, cls_loss]) + train_on_batch / test_on_batch      trainer.py:54-56, :64-69
+ *   The trainer holds float32 master weights of the three head layers, Adam's m and v (zero at creation) and the step
+ *   count t (applied steps only); sizes come from the model handle (Cin 512 / 576, F, K, max_batch).  It borrows the
+ *   handle: the backbone runs on the handle's ops at the handle's precision, so the handle must outlive the trainer and
+ *   its activation arena is overwritten by a step.  The head runs in exact float32 from the master weights whatever the
+ *   handle's precision; the handle's own head weights are NOT changed by a step (copy them with get_layer + set_layer).
+ *   set_layer / get_layer: HOST arrays, kernel HWIO + bias, names "rpn_conv" | "rpn_reg" | "rpn_cls" (any other name is
+ *   RPN_ERR_INVALID: the backbone is frozen); get_layer synchronises `stream`.
+ *   step: d_imgs (B,img,img,3), d_bbox_deltas (B,A,4), d_bbox_labels (B,F,F,K); d_losses <- [reg + cls, reg, cls] computed
+ *   with the weights before the update (Keras train_on_batch order).  update = 0: losses only (test_on_batch, t unchanged);
+ *   update = 1: backward + one Adam step (t += 1; alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t) on the device, no host
+ *   synchronisation).  steps: t.  outputs: the (reg, cls) head outputs of the last step, whose batch was B. */
+typedef struct rpn_head_trainer rpn_head_trainer;
+int rpn_head_trainer_create(rpn_model *m, rpn_head_trainer **out);
+void rpn_head_trainer_destroy(rpn_head_trainer *t);
+int rpn_head_trainer_set_layer(rpn_head_trainer *t, const char *name, const float *kernel, const float *bias);
+int rpn_head_trainer_get_layer(rpn_head_trainer *t, const char *name, float *kernel, float *bias, void *stream);
+/* the gradient of the total loss with respect to a head layer at the last update step (HOST kernel HWIO + bias) */
+int rpn_head_trainer_get_gradient(rpn_head_trainer *t, const char *name, float *kernel, float *bias, void *stream);
+int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
+                          const float *d_bbox_labels, int update, float lr, float beta_1, float beta_2, float epsilon,
+                          float *d_losses, void *stream);
+long long rpn_head_trainer_steps(const rpn_head_trainer *t);
+int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, int B, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * single conv layer, for kernel-level parity tests and micro-benchmarks.
  *   x (B,H,W,Cin) NHWC, w HWIO (device), bias (Cout, device, may be NULL).
  *   pad_t / pad_l: zero rows/cols added before the first row/col; OH/OW given by the caller.

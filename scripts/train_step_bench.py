@@ -1,0 +1,103 @@
+"""Milliseconds per head-training step (rpn_model.train_on_batch, trainer.py:64-69) and per kernel entry at batch 8, both backbones.
+
+    python scripts/train_step_bench.py [--batch 8] [--steps 20] [--warmup 3]
+
+Times on the device with HIP events around (a) a whole training step (backbone at the handle's precision + float32 head forward,
+losses, backward, Adam), (b) an evaluation step (no backward), (c) the 3x3 weight-gradient entry rpn_conv3x3_wgrad on the
+step's shape (its MFMA kernel + the leaf reduction) with its rate against the 157.3 TF/s float32-MFMA peak, (d) rpn_rpn_losses.
+Prints one JSON line per backbone.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from tf_rpn_amd import _lib as L  # noqa: E402
+from tf_rpn_amd.models import rpn_mobilenet_v2, rpn_vgg16  # noqa: E402
+from tf_rpn_amd.utils import bbox_utils, train_utils  # noqa: E402
+
+PEAK_F32_MFMA = 157.3e12
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(steps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / steps
+
+
+def bench(backbone, precision, B, steps, warmup):
+    mod = rpn_vgg16 if backbone == "vgg16" else rpn_mobilenet_v2
+    hp = train_utils.get_hyper_params(backbone)
+    model, _ = mod.get_model(hp, precision=precision, max_batch=B)
+    F, K = model.feature_map_shape, model.anchor_count
+    rng = np.random.RandomState(0)
+    imgs = torch.from_numpy(rng.uniform(0, 1, size=(B, hp["img_size"], hp["img_size"], 3)).astype(np.float32)).cuda()
+    anchors = bbox_utils.generate_anchors(hp)
+    gt = np.zeros((B, 4, 4), np.float32)
+    gt[:, :, :2] = rng.uniform(0, 0.5, size=(B, 4, 2))
+    gt[:, :, 2:] = gt[:, :, :2] + rng.uniform(0.2, 0.5, size=(B, 4, 2))
+    labels = np.ones((B, 4), np.int32)
+    deltas, lab = train_utils.calculate_rpn_actual_outputs(anchors, torch.from_numpy(gt).cuda(), torch.from_numpy(labels).cuda(), hp)
+    deltas, lab = deltas.contiguous(), lab.contiguous()
+    model.compile(learning_rate=1e-5)
+    lib = L.lib()
+    losses = torch.empty(3, device="cuda")
+
+    def step(update):
+        L.check(lib.rpn_head_trainer_step(model._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(lab), update, 1e-5, 0.9, 0.999, 1e-7,
+                                          L.ptr(losses), L.stream_ptr()), "rpn_head_trainer_step")
+
+    ms_train = timed(lambda: step(1), steps, warmup)
+    ms_eval = timed(lambda: step(0), steps, warmup)
+    cin = 512 if backbone == "vgg16" else 576
+    x = torch.randn((B, F, F, cin), device="cuda")
+    dy = torch.randn((B, F, F, 512), device="cuda")
+    dw = torch.empty((3, 3, cin, 512), device="cuda")
+    n = lib.rpn_conv3x3_wgrad_workspace_bytes(B, F, F, cin, 512)
+    ws = torch.empty(n, dtype=torch.uint8, device="cuda")
+    ms_wgrad = timed(lambda: L.check(lib.rpn_conv3x3_wgrad(L.ptr(x), L.ptr(dy), B, F, F, cin, 512, L.ptr(dw), None, L.ptr(ws), n,
+                                                           L.stream_ptr()), "rpn_conv3x3_wgrad"), steps, warmup)
+    flops = 2.0 * 9 * cin * 512 * B * F * F
+    A = F * F * K
+    reg_pred = torch.randn((B, A, 4), device="cuda")
+    cls_pred = torch.rand((B, A), device="cuda")
+    out = torch.empty(2, device="cuda")
+    gr, gc = torch.empty_like(reg_pred), torch.empty_like(cls_pred)
+    nl = lib.rpn_rpn_losses_workspace_bytes(B, A)
+    wl = torch.empty(nl, dtype=torch.uint8, device="cuda")
+    ms_loss = timed(lambda: L.check(lib.rpn_rpn_losses(L.ptr(deltas), L.ptr(reg_pred), L.ptr(lab), L.ptr(cls_pred), B, A, L.ptr(out),
+                                                       L.ptr(gr), L.ptr(gc), L.ptr(wl), nl, L.stream_ptr()), "rpn_rpn_losses"),
+                    steps, warmup)
+    return {"backbone": backbone, "precision": precision, "batch": B, "ms_train_step": round(ms_train, 4),
+            "ms_eval_step": round(ms_eval, 4), "ms_wgrad": round(ms_wgrad, 4), "wgrad_gflop": round(flops / 1e9, 2),
+            "wgrad_tflops": round(flops / ms_wgrad / 1e9, 2), "wgrad_frac_of_f32_mfma_peak": round(flops / ms_wgrad / 1e-3 / PEAK_F32_MFMA, 3),
+            "ms_losses": round(ms_loss, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--precision", default="f16x3")
+    args = ap.parse_args()
+    L.require_gpu()
+    for backbone in ("vgg16", "mobilenet_v2"):
+        print(json.dumps(bench(backbone, args.precision, args.batch, args.steps, args.warmup)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

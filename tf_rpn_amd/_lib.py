@@ -69,6 +69,18 @@ _SIGNATURES = {
     "rpn_model_op_info": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "rpn_model_get_profile": (ctypes.c_int, [vp, c_float_p, ctypes.c_int, c_int_p]),
+    "rpn_rpn_losses_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "rpn_rpn_losses": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_conv3x3_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "rpn_conv3x3_wgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_head_trainer_create": (ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    "rpn_head_trainer_destroy": (None, [vp]),
+    "rpn_head_trainer_set_layer": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p]),
+    "rpn_head_trainer_get_layer": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p, vp]),
+    "rpn_head_trainer_get_gradient": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p, vp]),
+    "rpn_head_trainer_step": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int] + [ctypes.c_float] * 4 + [vp, vp]),
+    "rpn_head_trainer_steps": (ctypes.c_longlong, [vp]),
+    "rpn_head_trainer_outputs": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, vp]),
     "rpn_conv2d": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 10 + [vp, vp]),
     "rpn_maxpool2x2": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_dwconv3x3": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),

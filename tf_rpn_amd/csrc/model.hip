@@ -903,15 +903,13 @@ extern "C" int rpn_model_set_layer(rpn_model *m, const char *name, const float *
     return RPN_OK;
 }
 
-extern "C" int rpn_model_forward(rpn_model *m, const float *d_imgs, int B, float *d_reg, float *d_cls, void *stream)
+namespace rpn {
+
+// The first `n_ops` ops of the graph on stream s (all of them: the forward; fewer: the backbone of a training step, which keeps
+// the per-op timing out of it).  The caller has validated the arguments and called ensure_device.
+static int run_ops(rpn_model *m, const float *d_imgs, int B, float *d_reg, float *d_cls, hipStream_t s, size_t n_ops)
 {
-    RPN_REQUIRE(m && d_imgs && d_reg && d_cls, "rpn_model_forward: null argument");
-    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_forward: batch %d outside [1, %d]", B, m->max_batch);
-    for (const Param &p : m->params)
-        RPN_REQUIRE(p.loaded, "rpn_model_forward: weights of layer '%s' were never set", p.name.c_str());
-    const int st = ensure_device(m);
-    if (st != RPN_OK) return st;
-    hipStream_t s = as_stream(stream);
+    const bool whole = n_ops == m->ops.size();
     m->last_input = d_imgs;
     struct StatusScope {                   // the split-format writers launched below flag float16 range violations here
         explicit StatusScope(unsigned *p) { set_range_status(p); }
@@ -919,7 +917,7 @@ extern "C" int rpn_model_forward(rpn_model *m, const float *d_imgs, int B, float
     } status_scope(m->f16 ? m->d_status : nullptr);
     hipEvent_t *evs = nullptr;
     int sel_op = -1;
-    if (m->profiling > 0) {
+    if (m->profiling > 0 && whole) {
         const size_t per = m->ops.size() + 1;
         if (m->events.size() != per * (size_t)m->profiling) {
             for (auto &ev : m->events) (void)hipEventDestroy(ev);
@@ -967,7 +965,7 @@ extern "C" int rpn_model_forward(rpn_model *m, const float *d_imgs, int B, float
         const int f = conv3x3_split16_ksplit(B, o.H, o.W, o.Cin, o.Cout, split_cout_pad(o.Cout));
         return (size_t)f * B <= (size_t)m->tensors[o.out].slabs * m->max_batch ? f : 1;
     };
-    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
+    for (size_t oi = 0; oi < n_ops; ++oi) {
         const Op &op = m->ops[oi];
         const float *x = tensor_ptr(m, op.in, d_imgs);
         hipError_t e = hipSuccess;
@@ -1077,6 +1075,55 @@ extern "C" int rpn_model_forward(rpn_model *m, const float *d_imgs, int B, float
     }
     return RPN_OK;
 }
+
+}  // namespace rpn
+
+extern "C" int rpn_model_forward(rpn_model *m, const float *d_imgs, int B, float *d_reg, float *d_cls, void *stream)
+{
+    RPN_REQUIRE(m && d_imgs && d_reg && d_cls, "rpn_model_forward: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_forward: batch %d outside [1, %d]", B, m->max_batch);
+    for (const Param &p : m->params)
+        RPN_REQUIRE(p.loaded, "rpn_model_forward: weights of layer '%s' were never set", p.name.c_str());
+    const int st = ensure_device(m);
+    if (st != RPN_OK) return st;
+    return run_ops(m, d_imgs, B, d_reg, d_cls, as_stream(stream), m->ops.size());
+}
+
+namespace rpn {
+
+void model_train_dims(const rpn_model *m, int *cin, int *F, int *K, int *max_batch)
+{
+    const Tensor &t = m->tensors[m->feat_tensor];
+    *cin = t.C; *F = m->F; *K = m->K; *max_batch = m->max_batch;
+}
+
+// The backbone of a training step (the head is trained on frozen features): the ops up to the one that writes feat_tensor, at the
+// handle's own precision, then the features as NHWC float32 into d_feat (B, F, F, Cin) -- converted from the split form when the
+// tensor is kept that way, as rpn_model_get_activation does.
+int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s)
+{
+    for (const Param &p : m->params)
+        if (p.name != "rpn_conv" && p.name != "rpn_reg" && p.name != "rpn_cls")
+            RPN_REQUIRE(p.loaded, "rpn_head_trainer_step: weights of layer '%s' were never set", p.name.c_str());
+    const int st = ensure_device(m);
+    if (st != RPN_OK) return st;
+    size_t n = 0;
+    for (size_t i = 0; i < m->ops.size(); ++i)
+        if (m->ops[i].out == m->feat_tensor) n = i + 1;
+    const int e0 = run_ops(m, d_imgs, B, nullptr, nullptr, s, n);
+    if (e0 != RPN_OK) return e0;
+    const Tensor &t = m->tensors[m->feat_tensor];
+    const float *src = tensor_ptr(m, m->feat_tensor, d_imgs);
+    if (t.split_fmt) {
+        const hipError_t e = launch_split_to_f32(src, (long long)B * t.H * t.W, t.C, m->f16, d_feat, s);
+        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: features: %s", hipGetErrorString(e));
+        return RPN_OK;
+    }
+    RPN_HIP_CHECK(hipMemcpyAsync(d_feat, src, (size_t)B * t.H * t.W * t.C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return RPN_OK;
+}
+
+}  // namespace rpn
 
 extern "C" int rpn_model_status(rpn_model *m, unsigned *flags, int reset, void *stream)
 {

@@ -53,3 +53,11 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
     } while (0)
 
 #define RPN_CHECK_LAUNCH() RPN_HIP_CHECK(hipGetLastError())
+
+// ---- the model handle as the head trainer sees it (model.hip) ----------------------------------------------------------------
+namespace rpn {
+// channels of the backbone features, feature-map side F, anchors per position K, the handle's largest batch
+void model_train_dims(const rpn_model *m, int *cin, int *F, int *K, int *max_batch);
+// the ops up to the backbone features on stream s, then the features as NHWC float32 (B, F, F, cin) into d_feat
+int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s);
+}  // namespace rpn

@@ -1,0 +1,721 @@
+// train_kernels.hip -- training of the RPN head (rpn_conv, rpn_cls, rpn_reg) on a frozen backbone: the counterpart of the
+// reference's trainer.py:54-69 (compile with Adam(1e-5) and loss=[reg_loss, cls_loss], then fit).
+//
+// Unlike the reference, whose Keras base model is trainable, only the head is trained here: backward through VGG16 /
+// MobileNetV2 is not implemented.  The step is
+//   backbone (the handle's own ops and precision) -> X (B,F,F,Cin) float32
+//   rpn_conv (exact float32, ReLU) -> S (P,512), P = B F F;  fused 1x1 head -> reg (P,4K) linear | cls (P,K) sigmoid
+//   losses + their gradients (one pass, fixed-order reductions)
+//   dZ = [dreg | dcls * p (1 - p)] (P,5K);  dW_head = S^T dZ, db_head = sum dZ;  dS = (dZ W_head^T) * [S > 0]
+//   dW_conv = 3x3 weight gradient of X and dS on the float32 MFMA (split K, fixed tree), db_conv = sum dS
+//   Adam over the six parameter tensors in one launch
+// No floating-point atomics anywhere: every sum has a fixed order, so a step is bit-identical from run to run.
+//
+// Loss and optimizer forms (TF 2.0.0, restated from its sources as recalled -- nothing here can run TF):
+//   cls_loss (utils/train_utils.py:146-162): keras BinaryCrossentropy on probabilities (backend.binary_crossentropy with
+//     from_logits=False): p' = clip(p, 1e-7, 1 - 1e-7), bce = -(t log(p' + 1e-7) + (1 - t) log(1 - p' + 1e-7)), mean over the kept
+//     entries (y_true != -1) of the whole batch; NaN when nothing is kept.  The gradient is zero where the clip is active.
+//   reg_loss (utils/train_utils.py:164-185): Huber (delta 1) per element -- TF 2.0's huber_loss has no mean over the last axis --
+//     summed over the 4 coordinates, masked by "any y_true coordinate != 0", summed, divided by max(1, n_pos).
+//   Adam (training_ops ApplyAdam): alpha = lr sqrt(1 - b2^t) / (1 - b1^t); m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2);
+//     w -= alpha m / (sqrt(v) + eps), t = the number of applied steps.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "conv_kernels.h"
+#include "rpn_common.h"
+
+namespace rpn {
+
+constexpr int kLossThreads = 256;
+constexpr int kLossMaxBlocks = 512;
+constexpr int kChunkRows = 64;          // rows per partial of the column sums / the head weight gradient
+constexpr int kLeaves = 4;              // K leaves of the 3x3 weight gradient: the value is (l0 + l1) + (l2 + l3) at every grid
+constexpr float kClipLo = 1e-7f, kClipHi = 1.0f - 1e-7f;   // keras epsilon() and 1 - epsilon() as float32 constants
+constexpr double kLogEps = (double)1e-7f;
+
+static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
+static int loss_blocks(long long n) { return (int)std::min<long long>((n + kLossThreads - 1) / kLossThreads, kLossMaxBlocks); }
+
+// ---- losses: pass 1 ---------------------------------------------------------------------------------------------------
+// Per element of (B, A): the Huber sum of the 4 coordinates (counted when any true coordinate is non-zero) and the BCE of the
+// kept labels, both in float64; the UNSCALED gradients (clip(pred - true, -1, 1) * mask, d bce / d p) go to graw_*; the block's
+// partial sums (reg, cls, n_pos, n_valid) go to part[block] after a fixed LDS tree.
+__global__ void __launch_bounds__(kLossThreads) rpn_loss_kernel(const float4 *__restrict__ reg_true, const float4 *__restrict__ reg_pred,
+                                                              const float *__restrict__ cls_true, const float *__restrict__ cls_pred,
+                                                              long long n, float4 *__restrict__ graw_reg, float *__restrict__ graw_cls,
+                                                              double4 *__restrict__ part)
+{
+    double reg = 0.0, cls = 0.0, npos = 0.0, nval = 0.0;
+    for (long long i = (long long)blockIdx.x * kLossThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kLossThreads) {
+        const float4 t = reg_true[i], p = reg_pred[i];
+        const bool pos = t.x != 0.0f || t.y != 0.0f || t.z != 0.0f || t.w != 0.0f;
+        const double d[4] = {(double)p.x - t.x, (double)p.y - t.y, (double)p.z - t.z, (double)p.w - t.w};
+        double h = 0.0;
+        float g[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const double a = fabs(d[c]), q = fmin(a, 1.0);
+            h += 0.5 * q * q + (a - q);
+            g[c] = pos ? (float)fmax(-1.0, fmin(1.0, d[c])) : 0.0f;
+        }
+        if (pos) { reg += h; npos += 1.0; }
+        if (graw_reg) graw_reg[i] = make_float4(g[0], g[1], g[2], g[3]);
+        const float y = cls_true[i];
+        float gc = 0.0f;
+        if (y != -1.0f) {
+            const float pr = cls_pred[i];
+            const double pc = (double)fminf(fmaxf(pr, kClipLo), kClipHi), yd = y;
+            cls -= yd * log(pc + kLogEps) + (1.0 - yd) * log(1.0 - pc + kLogEps);
+            nval += 1.0;
+            if (pr >= kClipLo && pr <= kClipHi) gc = (float)(-(yd / (pc + kLogEps)) + (1.0 - yd) / (1.0 - pc + kLogEps));
+        }
+        if (graw_cls) graw_cls[i] = gc;
+    }
+    __shared__ double4 red[kLossThreads];
+    red[threadIdx.x] = make_double4(reg, cls, npos, nval);
+    __syncthreads();
+    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            const double4 a = red[threadIdx.x], b = red[threadIdx.x + w];
+            red[threadIdx.x] = make_double4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// ---- losses: pass 2 (one workgroup) -- the partials in a fixed tree, the two losses and the gradient scales -----------------
+// out: [reg, cls] or, with_total, [reg + cls, reg, cls]; scale = {1 / max(1, n_pos), n_valid ? 1 / n_valid : 0}
+__global__ void __launch_bounds__(kLossThreads) rpn_loss_finish_kernel(const double4 *__restrict__ part, int nparts, float *__restrict__ out,
+                                                                     int with_total, float *__restrict__ scale)
+{
+    __shared__ double4 red[kLossThreads];
+    double4 s = make_double4(0.0, 0.0, 0.0, 0.0);
+    for (int i = threadIdx.x; i < nparts; i += kLossThreads) {
+        const double4 a = part[i];
+        s = make_double4(s.x + a.x, s.y + a.y, s.z + a.z, s.w + a.w);
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = kLossThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            const double4 a = red[threadIdx.x], b = red[threadIdx.x + w];
+            red[threadIdx.x] = make_double4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double4 t = red[0];
+        const float reg = (float)(t.x / fmax(1.0, t.z));
+        const float cls = t.w > 0.0 ? (float)(t.y / t.w) : __builtin_nanf("");    // mean of an empty tensor
+        if (with_total) { out[0] = reg + cls; out[1] = reg; out[2] = cls; }
+        else { out[0] = reg; out[1] = cls; }
+        scale[0] = (float)(1.0 / fmax(1.0, t.z));
+        scale[1] = t.w > 0.0 ? (float)(1.0 / t.w) : 0.0f;
+    }
+}
+
+__global__ void __launch_bounds__(256) rpn_loss_scale_kernel(float *__restrict__ g_reg, float *__restrict__ g_cls, long long n,
+                                                           const float *__restrict__ scale)
+{
+    const float sr = scale[0], sc = scale[1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        if (g_reg) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) g_reg[4 * i + c] *= sr;
+        }
+        if (g_cls) g_cls[i] *= sc;
+    }
+}
+
+// ---- head backward ------------------------------------------------------------------------------------------------------
+// dZ (P, 5K) = [graw_reg * s_reg | graw_cls * s_cls * p (1 - p)] (the sigmoid of the cls columns folded in here)
+__global__ void __launch_bounds__(256) head_dz_kernel(const float *__restrict__ graw_reg, const float *__restrict__ graw_cls,
+                                                    const float *__restrict__ cls, const float *__restrict__ scale, long long P, int K,
+                                                    float *__restrict__ dz)
+{
+    const int nc = 5 * K;
+    const float sr = scale[0], sc = scale[1];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P * nc; i += (long long)gridDim.x * 256) {
+        const long long row = i / nc;
+        const int c = (int)(i - row * nc);
+        float v;
+        if (c < 4 * K) {
+            v = graw_reg[row * 4 * K + c] * sr;
+        } else {
+            const float p = cls[row * K + c - 4 * K];
+            v = graw_cls[row * K + c - 4 * K] * sc * (p * (1.0f - p));
+        }
+        dz[i] = v;
+    }
+}
+
+// partial of dW_head = S^T dZ (rows 0 .. 511) and db_head = sum dZ (row 512) over the kChunkRows rows of chunk blockIdx.x:
+// part[chunk][513][nc].  Thread t owns input channels t and t + 256; rows in order.
+template <int NC>
+__global__ void __launch_bounds__(256) head_wgrad_kernel(const float *__restrict__ S, const float *__restrict__ dz, long long P,
+                                                       float *__restrict__ part)
+{
+    __shared__ float zs[kChunkRows][NC];
+    const long long r0 = (long long)blockIdx.x * kChunkRows;
+    const int rows = (int)std::min<long long>(kChunkRows, P - r0);
+    for (int i = threadIdx.x; i < rows * NC; i += 256) zs[i / NC][i % NC] = dz[r0 * NC + i];
+    __syncthreads();
+    float acc0[NC], acc1[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc0[c] = acc1[c] = 0.0f;
+    for (int r = 0; r < rows; ++r) {
+        const float s0 = S[(r0 + r) * 512 + threadIdx.x], s1 = S[(r0 + r) * 512 + threadIdx.x + 256];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            acc0[c] = fmaf(s0, zs[r][c], acc0[c]);
+            acc1[c] = fmaf(s1, zs[r][c], acc1[c]);
+        }
+    }
+    float *dst = part + (size_t)blockIdx.x * 513 * NC;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        dst[threadIdx.x * NC + c] = acc0[c];
+        dst[(threadIdx.x + 256) * NC + c] = acc1[c];
+    }
+    if (threadIdx.x < NC) {
+        float b = 0.0f;
+        for (int r = 0; r < rows; ++r) b += zs[r][threadIdx.x];
+        dst[512 * NC + threadIdx.x] = b;
+    }
+}
+
+// dS (P, 512) = (dZ W_head^T) * [S > 0]; w_head (512, NC) row-major.  16 rows per workgroup of 512 threads, thread t: channel t.
+template <int NC>
+__global__ void __launch_bounds__(512) head_dgrad_kernel(const float *__restrict__ S, const float *__restrict__ dz,
+                                                       const float *__restrict__ w_head, long long P, float *__restrict__ dS)
+{
+    constexpr int RB = 16;
+    __shared__ float zs[RB][NC];
+    const long long r0 = (long long)blockIdx.x * RB;
+    const int rows = (int)std::min<long long>(RB, P - r0);
+    for (int i = threadIdx.x; i < rows * NC; i += 512) zs[i / NC][i % NC] = dz[r0 * NC + i];
+    __syncthreads();
+    float w[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) w[c] = w_head[threadIdx.x * NC + c];
+#pragma unroll 1
+    for (int r = 0; r < rows; ++r) {
+        float a = 0.0f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a = fmaf(zs[r][c], w[c], a);
+        const long long o = (r0 + r) * 512 + threadIdx.x;
+        dS[o] = S[o] > 0.0f ? a : 0.0f;
+    }
+}
+
+// column sums of x (rows, C) over chunks of kChunkRows rows, rows in order: part[chunk][C]
+__global__ void __launch_bounds__(256) colsum_partial_kernel(const float *__restrict__ x, long long rows, int C, float *__restrict__ part)
+{
+    const long long r0 = (long long)blockIdx.x * kChunkRows;
+    const int nr = (int)std::min<long long>(kChunkRows, rows - r0);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float s = 0.0f;
+        for (int r = 0; r < nr; ++r) s += x[(r0 + r) * C + c];
+        part[(size_t)blockIdx.x * C + c] = s;
+    }
+}
+
+// out[j] = sum over the chunks, in chunk order, of part[chunk][j]
+__global__ void __launch_bounds__(256) reduce_chunks_kernel(const float *__restrict__ part, int nchunks, long long len, float *__restrict__ out)
+{
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256) {
+        float s = 0.0f;
+        for (int c = 0; c < nchunks; ++c) s += part[(size_t)c * len + j];
+        out[j] = s;
+    }
+}
+
+// ---- 3x3 stride-1 'same' weight gradient on the float32 MFMA -----------------------------------------------------------------
+// dW[r][s][ci][co] = sum_{b,y,x} X[b][y+r-1][x+s-1][ci] * dY[b][y][x][co] (zero padding): a GEMM C (M x N) = A^T B with
+// M = 9 Cin (row m = (3 r + s) Cin + ci), N = Cout, K = the P = B H W pixels; both operands are pixel-major (A^T[p][m] is a
+// shifted row of X, B[p][n] a row of dY), so a K slice of either is a contiguous run of channels per pixel.
+// Workgroup: a 128 x 128 tile of C over ONE of kLeaves fixed ranges of pixels (leaf l: [l P / 4, (l + 1) P / 4)); four waves of
+// 64 x 64 (2 x 2 v_mfma_f32_32x32x2_f32 blocks).  K slices of 16 pixels are staged global -> registers -> LDS (double-buffered,
+// one barrier per slice, the next slice's loads in flight under the current slice's MFMAs), as conv_igemm_f32 stages its
+// operands.  Each leaf's tile goes to its own slab of the workspace; wgrad_reduce_kernel adds (l0 + l1) + (l2 + l3).  The
+// leaves do not depend on the grid: the same bits at every launch.
+constexpr int kWgBM = 128, kWgBN = 128, kWgBK = 16, kWgLd = 160;   // LDS row stride: the two half-waves of a fragment read hit disjoint banks
+
+using f32x16w = __attribute__((ext_vector_type(16))) float;
+
+__global__ void __launch_bounds__(256) conv3x3_wgrad_f32_kernel(const float *__restrict__ X, const float *__restrict__ dY, int B, int H,
+                                                              int W, int Cin, int Cout, float *__restrict__ part)
+{
+    __shared__ float As[2][kWgBK][kWgLd];
+    __shared__ float Bs[2][kWgBK][kWgLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int M = 9 * Cin, n0 = blockIdx.x * kWgBN, m0 = blockIdx.y * kWgBM, leaf = blockIdx.z;
+    const long long P = (long long)B * H * W;
+    const long long pbeg = P * leaf / kLeaves, pend = P * (leaf + 1) / kLeaves;
+    const int nsteps = (int)((pend - pbeg + kWgBK - 1) / kWgBK);
+
+    // loader: thread -> (pixel row kr and kr + 8 of the slice, 4-channel quad q); the same (tap, ci) / n for every slice
+    const int kr = tid >> 5, q = tid & 31;
+    const int m = m0 + 4 * q, n = n0 + 4 * q;
+    const bool m_ok = m < M, n_ok = n < Cout;
+    const int tap = m_ok ? m / Cin : 0, ci = m_ok ? m - tap * Cin : 0;
+    const int dr = tap / 3 - 1, ds = tap % 3 - 1;
+    // pixel coordinates of this thread's two rows at the current slice, advanced by 16 pixels per slice
+    int pb[2], py[2], px[2];
+    long long pp[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        pp[u] = pbeg + kr + 8 * u;
+        const long long hw = (long long)H * W;
+        pb[u] = (int)(pp[u] / hw);
+        const int rem = (int)(pp[u] - (long long)pb[u] * hw);
+        py[u] = rem / W;
+        px[u] = rem - py[u] * W;
+    }
+    float4 ra[2], rb[2];
+    auto load_global = [&]() {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            ra[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            rb[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (pp[u] < pend) {
+                const int yy = py[u] + dr, xx = px[u] + ds;
+                if (m_ok && yy >= 0 && yy < H && xx >= 0 && xx < W)
+                    ra[u] = *reinterpret_cast<const float4 *>(X + (((size_t)pb[u] * H + yy) * W + xx) * Cin + ci);
+                if (n_ok) rb[u] = *reinterpret_cast<const float4 *>(dY + (size_t)pp[u] * Cout + n);
+            }
+        }
+    };
+    auto advance = [&]() {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            pp[u] += kWgBK;
+            px[u] += kWgBK;
+            while (px[u] >= W) {
+                px[u] -= W;
+                if (++py[u] == H) { py[u] = 0; ++pb[u]; }
+            }
+        }
+    };
+    auto store_lds = [&](int buf) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            *reinterpret_cast<float4 *>(&As[buf][kr + 8 * u][4 * q]) = ra[u];
+            *reinterpret_cast<float4 *>(&Bs[buf][kr + 8 * u][4 * q]) = rb[u];
+        }
+    };
+
+    f32x16w acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+    const int am = wm * 64 + (lane & 31), bn = wn * 64 + (lane & 31), kh = lane >> 5;
+
+    load_global();
+    store_lds(0);
+    __syncthreads();
+    int cur = 0;
+    for (int step = 0; step < nsteps; ++step) {
+        const bool more = step + 1 < nsteps;
+        if (more) {
+            advance();
+            load_global();
+        }
+#pragma unroll
+        for (int kk = 0; kk < kWgBK / 2; ++kk) {
+            float av[2], bv[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) av[i] = As[cur][2 * kk + kh][am + 32 * i];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bv[j] = Bs[cur][2 * kk + kh][bn + 32 * j];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        if (more) store_lds(cur ^ 1);
+        __syncthreads();
+        cur ^= 1;
+    }
+    // accumulator element e of block (i, j): row 8 (e / 4) + 4 kh + e % 4, column lane % 32
+    float *slab = part + (size_t)leaf * M * Cout;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = n0 + wn * 64 + 32 * j + (lane & 31);
+            if (col >= Cout) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = m0 + wm * 64 + 32 * i + 8 * (e >> 2) + 4 * kh + (e & 3);
+                if (row < M) slab[(size_t)row * Cout + col] = acc[i][j][e];
+            }
+        }
+}
+
+// dW = (l0 + l1) + (l2 + l3) over the four leaf slabs of len floats each
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float *__restrict__ part, long long len, float *__restrict__ dw)
+{
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256)
+        dw[j] = (part[j] + part[len + j]) + (part[2 * len + j] + part[3 * len + j]);
+}
+
+// ---- Adam (ApplyAdam) over one flat float32 buffer holding every trained tensor ------------------------------------------------
+__global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ mom,
+                                                 float *__restrict__ vel, long long n, long long t, float lr, float b1, float b2, float eps)
+{
+    const float alpha = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float gi = g[i];
+        const float mi = mom[i] + (gi - mom[i]) * (1.0f - b1);
+        const float vi = vel[i] + (gi * gi - vel[i]) * (1.0f - b2);
+        mom[i] = mi;
+        vel[i] = vi;
+        w[i] -= alpha * mi / (sqrtf(vi) + eps);
+    }
+}
+
+static int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 2048)); }
+
+// ---- host launchers ----------------------------------------------------------------------------------------------------------
+static size_t losses_ws_bytes(long long n) { return a256((size_t)loss_blocks(n) * sizeof(double4)) + 256; }
+
+// pass 1 + pass 2; the gradient scales land at the end of the workspace (losses_scale)
+static float *losses_scale(void *ws, long long n) { return reinterpret_cast<float *>((char *)ws + a256((size_t)loss_blocks(n) * sizeof(double4))); }
+
+static hipError_t launch_losses(const float *reg_true, const float *reg_pred, const float *cls_true, const float *cls_pred, long long n,
+                         float *graw_reg, float *graw_cls, float *out, int with_total, void *ws, hipStream_t s)
+{
+    const int nb = loss_blocks(n);
+    double4 *part = reinterpret_cast<double4 *>(ws);
+    hipLaunchKernelGGL(rpn_loss_kernel, dim3(nb), dim3(kLossThreads), 0, s, reinterpret_cast<const float4 *>(reg_true),
+                       reinterpret_cast<const float4 *>(reg_pred), cls_true, cls_pred, n, reinterpret_cast<float4 *>(graw_reg),
+                       graw_cls, part);
+    hipLaunchKernelGGL(rpn_loss_finish_kernel, dim3(1), dim3(kLossThreads), 0, s, part, nb, out, with_total, losses_scale(ws, n));
+    return hipGetLastError();
+}
+
+static size_t colsum_ws_floats(long long rows, int C) { return (size_t)((rows + kChunkRows - 1) / kChunkRows) * C; }
+
+static hipError_t launch_colsum(const float *x, long long rows, int C, float *part, float *out, hipStream_t s)
+{
+    const int nchunks = (int)((rows + kChunkRows - 1) / kChunkRows);
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(nchunks), dim3(256), 0, s, x, rows, C, part);
+    hipLaunchKernelGGL(reduce_chunks_kernel, dim3(grid_for(C)), dim3(256), 0, s, part, nchunks, (long long)C, out);
+    return hipGetLastError();
+}
+
+static size_t wgrad_ws_floats(int Cin, int Cout) { return (size_t)kLeaves * 9 * Cin * Cout; }
+
+static hipError_t launch_wgrad(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, hipStream_t s)
+{
+    const int M = 9 * Cin;
+    hipLaunchKernelGGL(conv3x3_wgrad_f32_kernel, dim3((Cout + kWgBN - 1) / kWgBN, (M + kWgBM - 1) / kWgBM, kLeaves), dim3(256), 0, s, x,
+                       dy, B, H, W, Cin, Cout, part);
+    const long long len = (long long)M * Cout;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(len)), dim3(256), 0, s, part, len, dw);
+    return hipGetLastError();
+}
+
+}  // namespace rpn
+
+using namespace rpn;
+
+// ---- C ABI: losses -----------------------------------------------------------------------------------------------------------
+extern "C" size_t rpn_rpn_losses_workspace_bytes(int B, int A)
+{
+    if (B < 1 || A < 1) return 0;
+    return losses_ws_bytes((long long)B * A);
+}
+
+extern "C" int rpn_rpn_losses(const float *d_reg_true, const float *d_reg_pred, const float *d_cls_true, const float *d_cls_pred, int B,
+                              int A, float *d_losses, float *d_grad_reg, float *d_grad_cls, void *d_ws, size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_reg_true && d_reg_pred && d_cls_true && d_cls_pred && d_losses, "rpn_rpn_losses: null pointer");
+    RPN_REQUIRE(B >= 1 && A >= 1, "rpn_rpn_losses: bad shape B=%d A=%d", B, A);
+    const long long n = (long long)B * A;
+    if (!d_ws || ws_bytes < losses_ws_bytes(n))
+        return fail(RPN_ERR_WORKSPACE, "rpn_rpn_losses: %zu bytes of workspace needed", losses_ws_bytes(n));
+    RPN_REQUIRE_DEVICE();
+    hipStream_t s = as_stream(stream);
+    hipError_t e = launch_losses(d_reg_true, d_reg_pred, d_cls_true, d_cls_pred, n, d_grad_reg, d_grad_cls, d_losses, 0, d_ws, s);
+    if (e == hipSuccess && (d_grad_reg || d_grad_cls)) {
+        hipLaunchKernelGGL(rpn_loss_scale_kernel, dim3(grid_for(n)), dim3(256), 0, s, d_grad_reg, d_grad_cls, n, losses_scale(d_ws, n));
+        e = hipGetLastError();
+    }
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_rpn_losses: %s", hipGetErrorString(e));
+}
+
+// ---- C ABI: single-layer weight gradient -------------------------------------------------------------------------------------
+extern "C" size_t rpn_conv3x3_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout)
+{
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return 0;
+    return a256(wgrad_ws_floats(Cin, Cout) * sizeof(float)) + a256(colsum_ws_floats((long long)B * H * W, Cout) * sizeof(float));
+}
+
+extern "C" int rpn_conv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw, float *d_db,
+                                 void *d_ws, size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_x && d_dy && d_dw, "rpn_conv3x3_wgrad: null pointer");
+    RPN_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cin >= 4 && Cout >= 4, "rpn_conv3x3_wgrad: bad shape");
+    RPN_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "rpn_conv3x3_wgrad: Cin and Cout must be multiples of 4");
+    RPN_REQUIRE((long long)9 * Cin * Cout <= (1ll << 30) && (long long)H * W <= (1 << 30), "rpn_conv3x3_wgrad: layer too large");
+    const size_t need = rpn_conv3x3_wgrad_workspace_bytes(B, H, W, Cin, Cout);
+    if (!d_ws || ws_bytes < need) return fail(RPN_ERR_WORKSPACE, "rpn_conv3x3_wgrad: %zu bytes of workspace needed", need);
+    RPN_REQUIRE_DEVICE();
+    hipStream_t s = as_stream(stream);
+    float *part = reinterpret_cast<float *>(d_ws);
+    hipError_t e = launch_wgrad(d_x, d_dy, B, H, W, Cin, Cout, part, d_dw, s);
+    if (e == hipSuccess && d_db)
+        e = launch_colsum(d_dy, (long long)B * H * W, Cout, part + a256(wgrad_ws_floats(Cin, Cout) * sizeof(float)) / sizeof(float), d_db, s);
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_conv3x3_wgrad: %s", hipGetErrorString(e));
+}
+
+// ---- C ABI: the head trainer -------------------------------------------------------------------------------------------------
+struct rpn_head_trainer {
+    rpn_model *m = nullptr;
+    int cin = 0, F = 0, K = 0, max_batch = 0, nc = 0;
+    // master weights, flat: [rpn_conv kernel (3,3,cin,512) | rpn_conv bias | head kernel (512, 5K): rpn_reg columns, then rpn_cls |
+    // head bias (5K)] -- gradients, Adam's m and v in the same layout
+    size_t off_ck = 0, off_cb = 0, off_hk = 0, off_hb = 0, n = 0;
+    std::vector<float> host_w;                  // the master weights until the first step moves them to the device
+    bool loaded[3] = {false, false, false};     // rpn_conv, rpn_reg, rpn_cls
+    long long t = 0;                            // applied Adam steps
+    int last_B = 0;
+    float *d_w = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;
+    float *d_pconv = nullptr, *d_phead = nullptr;
+    float *d_feat = nullptr, *d_S = nullptr, *d_reg = nullptr, *d_cls = nullptr, *d_graw = nullptr, *d_dz = nullptr, *d_dS = nullptr;
+    float *d_part = nullptr;
+    void *d_lws = nullptr;
+    PackedShape ps_conv{}, ps_head{};
+};
+
+namespace {
+
+const char *kHeadLayers[3] = {"rpn_conv", "rpn_reg", "rpn_cls"};
+
+int layer_index(const char *name)
+{
+    for (int i = 0; i < 3; ++i)
+        if (!strcmp(name, kHeadLayers[i])) return i;
+    return -1;
+}
+
+size_t trainer_part_floats(const rpn_head_trainer *t)
+{
+    const long long P = (long long)t->max_batch * t->F * t->F;
+    const size_t chunks = (size_t)((P + kChunkRows - 1) / kChunkRows);
+    return std::max(std::max(chunks * 513 * t->nc, wgrad_ws_floats(t->cin, 512)), colsum_ws_floats(P, 512));
+}
+
+int trainer_device(rpn_head_trainer *t)
+{
+    if (!have_device()) return RPN_ERR_NO_DEVICE;
+    if (t->d_w) return RPN_OK;
+    const size_t P = (size_t)t->max_batch * t->F * t->F;
+    float **bufs[] = {&t->d_w, &t->d_g, &t->d_m, &t->d_v, &t->d_pconv, &t->d_phead, &t->d_feat, &t->d_S, &t->d_reg, &t->d_cls,
+                      &t->d_graw, &t->d_dz, &t->d_dS, &t->d_part};
+    const size_t floats[] = {t->n, t->n, t->n, t->n, t->ps_conv.floats(), t->ps_head.floats(), P * t->cin, P * 512, P * 4 * t->K,
+                             P * t->K, P * 5 * t->K, P * t->nc, P * 512, trainer_part_floats(t)};
+    for (size_t i = 0; i < sizeof(floats) / sizeof(floats[0]); ++i) RPN_HIP_CHECK(hipMalloc(bufs[i], floats[i] * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_lws, losses_ws_bytes((long long)P * t->K)));
+    RPN_HIP_CHECK(hipMemcpy(t->d_w, t->host_w.data(), t->n * sizeof(float), hipMemcpyHostToDevice));
+    RPN_HIP_CHECK(hipMemset(t->d_m, 0, t->n * sizeof(float)));
+    RPN_HIP_CHECK(hipMemset(t->d_v, 0, t->n * sizeof(float)));
+    return RPN_OK;
+}
+
+void trainer_free(rpn_head_trainer *t)
+{
+    float *bufs[] = {t->d_w, t->d_g, t->d_m, t->d_v, t->d_pconv, t->d_phead, t->d_feat, t->d_S, t->d_reg, t->d_cls, t->d_graw, t->d_dz,
+                     t->d_dS, t->d_part};
+    for (float *p : bufs)
+        if (p) (void)hipFree(p);
+    if (t->d_lws) (void)hipFree(t->d_lws);
+}
+
+}  // namespace
+
+extern "C" int rpn_head_trainer_create(rpn_model *m, rpn_head_trainer **out)
+{
+    RPN_REQUIRE(m && out, "rpn_head_trainer_create: null argument");
+    int cin, F, K, mb;
+    model_train_dims(m, &cin, &F, &K, &mb);
+    RPN_REQUIRE(cin % 4 == 0 && 5 * K <= 64 && K >= 1, "rpn_head_trainer_create: unsupported head (Cin %d, K %d)", cin, K);
+    rpn_head_trainer *t = new rpn_head_trainer();
+    t->m = m; t->cin = cin; t->F = F; t->K = K; t->max_batch = mb; t->nc = 5 * K;
+    t->off_ck = 0;
+    t->off_cb = (size_t)9 * cin * 512;
+    t->off_hk = t->off_cb + 512;
+    t->off_hb = t->off_hk + (size_t)512 * t->nc;
+    t->n = t->off_hb + t->nc;
+    t->host_w.assign(t->n, 0.0f);
+    t->ps_conv = packed_shape(3, 3, cin, 512);
+    t->ps_head = packed_shape(1, 1, 512, t->nc);
+    *out = t;
+    return RPN_OK;
+}
+
+extern "C" void rpn_head_trainer_destroy(rpn_head_trainer *t)
+{
+    if (!t) return;
+    trainer_free(t);
+    delete t;
+}
+
+extern "C" int rpn_head_trainer_set_layer(rpn_head_trainer *t, const char *name, const float *kernel, const float *bias)
+{
+    RPN_REQUIRE(t && name && kernel && bias, "rpn_head_trainer_set_layer: null argument");
+    const int li = layer_index(name);
+    RPN_REQUIRE(li >= 0, "rpn_head_trainer_set_layer: '%s' is not trained (the backbone is frozen: rpn_conv, rpn_reg, rpn_cls only)",
+                name);
+    // the layer's slices of the flat master buffer: (offset, row length, row stride, rows) for the kernel, then the bias
+    std::vector<float> &w = t->host_w;
+    if (t->d_w) RPN_HIP_CHECK(hipMemcpy(w.data(), t->d_w, t->n * sizeof(float), hipMemcpyDeviceToHost));
+    if (li == 0) {
+        memcpy(&w[t->off_ck], kernel, (size_t)9 * t->cin * 512 * sizeof(float));
+        memcpy(&w[t->off_cb], bias, 512 * sizeof(float));
+    } else {
+        const int col = li == 1 ? 0 : 4 * t->K, width = li == 1 ? 4 * t->K : t->K;
+        for (int k = 0; k < 512; ++k) memcpy(&w[t->off_hk + (size_t)k * t->nc + col], kernel + (size_t)k * width, width * sizeof(float));
+        memcpy(&w[t->off_hb + col], bias, width * sizeof(float));
+    }
+    if (t->d_w) RPN_HIP_CHECK(hipMemcpy(t->d_w, w.data(), t->n * sizeof(float), hipMemcpyHostToDevice));
+    t->loaded[li] = true;
+    return RPN_OK;
+}
+
+// a head layer's slices of the master weights (grad == 0) or of the last step's gradient (grad == 1) -> HOST kernel / bias
+static int trainer_read(rpn_head_trainer *t, const char *what, const char *name, float *kernel, float *bias, int grad, void *stream)
+{
+    RPN_REQUIRE(t && name && kernel && bias, "%s: null argument", what);
+    const int li = layer_index(name);
+    RPN_REQUIRE(li >= 0, "%s: '%s' is not trained (rpn_conv, rpn_reg, rpn_cls)", what, name);
+    RPN_REQUIRE(t->loaded[li], "%s: layer '%s' was never set", what, name);
+    RPN_REQUIRE(!grad || t->t > 0, "%s: no update step has run", what);
+    std::vector<float> gbuf;
+    if (grad) gbuf.resize(t->n);
+    std::vector<float> &w = grad ? gbuf : t->host_w;
+    if (t->d_w) {
+        RPN_HIP_CHECK(hipMemcpyAsync(w.data(), grad ? t->d_g : t->d_w, t->n * sizeof(float), hipMemcpyDeviceToHost, as_stream(stream)));
+        RPN_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+    }
+    if (li == 0) {
+        memcpy(kernel, &w[t->off_ck], (size_t)9 * t->cin * 512 * sizeof(float));
+        memcpy(bias, &w[t->off_cb], 512 * sizeof(float));
+    } else {
+        const int col = li == 1 ? 0 : 4 * t->K, width = li == 1 ? 4 * t->K : t->K;
+        for (int k = 0; k < 512; ++k) memcpy(kernel + (size_t)k * width, &w[t->off_hk + (size_t)k * t->nc + col], width * sizeof(float));
+        memcpy(bias, &w[t->off_hb + col], width * sizeof(float));
+    }
+    return RPN_OK;
+}
+
+extern "C" int rpn_head_trainer_get_layer(rpn_head_trainer *t, const char *name, float *kernel, float *bias, void *stream)
+{
+    return trainer_read(t, "rpn_head_trainer_get_layer", name, kernel, bias, 0, stream);
+}
+
+extern "C" int rpn_head_trainer_get_gradient(rpn_head_trainer *t, const char *name, float *kernel, float *bias, void *stream)
+{
+    return trainer_read(t, "rpn_head_trainer_get_gradient", name, kernel, bias, 1, stream);
+}
+
+extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
+                                     const float *d_bbox_labels, int update, float lr, float beta_1, float beta_2, float epsilon,
+                                     float *d_losses, void *stream)
+{
+    RPN_REQUIRE(t && d_imgs && d_bbox_deltas && d_bbox_labels && d_losses, "rpn_head_trainer_step: null argument");
+    RPN_REQUIRE(B >= 1 && B <= t->max_batch, "rpn_head_trainer_step: batch %d outside [1, %d]", B, t->max_batch);
+    RPN_REQUIRE(update == 0 || update == 1, "rpn_head_trainer_step: update must be 0 or 1");
+    RPN_REQUIRE(!update || (std::isfinite(lr) && lr >= 0.0f && beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f &&
+                            std::isfinite(epsilon) && epsilon >= 0.0f),
+                "rpn_head_trainer_step: bad Adam hyper-parameters");
+    for (int i = 0; i < 3; ++i) RPN_REQUIRE(t->loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kHeadLayers[i]);
+    const int st = trainer_device(t);
+    if (st != RPN_OK) return st;
+    hipStream_t s = as_stream(stream);
+    const int F = t->F, K = t->K, nc = t->nc;
+    const long long P = (long long)B * F * F;
+    const int e0 = model_features(t->m, d_imgs, B, t->d_feat, s);
+    if (e0 != RPN_OK) return e0;
+    // head forward in exact float32 from the master weights
+    pack_weights_device(t->ps_conv, t->d_w + t->off_ck, t->d_pconv, s);
+    pack_weights_device(t->ps_head, t->d_w + t->off_hk, t->d_phead, s);
+    ConvArgs a{};
+    a.x = t->d_feat; a.w = t->d_pconv; a.bias = t->d_w + t->off_cb; a.residual = nullptr;
+    a.out = t->d_S; a.out2 = nullptr;
+    a.B = B; a.H = F; a.W = F; a.Cin = t->cin; a.OH = F; a.OW = F; a.Cout = 512;
+    a.R = 3; a.S = 3; a.stride = 1; a.pad_t = 1; a.pad_l = 1; a.ps = t->ps_conv;
+    a.act = ACT_RELU; a.act2 = ACT_LINEAR; a.split = 512; a.ld1 = 512; a.ld2 = 0;
+    hipError_t e = launch_conv_f32(a, s);
+    if (e == hipSuccess) {
+        ConvArgs h{};
+        h.x = t->d_S; h.w = t->d_phead; h.bias = t->d_w + t->off_hb; h.residual = nullptr;
+        h.out = t->d_reg; h.ld1 = 4 * K; h.act = ACT_LINEAR; h.split = 4 * K;
+        h.out2 = t->d_cls; h.ld2 = K; h.act2 = ACT_SIGMOID;
+        h.B = B; h.H = F; h.W = F; h.Cin = 512; h.OH = F; h.OW = F; h.Cout = nc;
+        h.R = 1; h.S = 1; h.stride = 1; h.pad_t = 0; h.pad_l = 0; h.ps = t->ps_head;
+        e = launch_conv_f32(h, s);
+    }
+    float *graw_reg = t->d_graw, *graw_cls = t->d_graw + P * 4 * K;
+    const long long n = P * K;                  // (B, A) with A = F F K
+    if (e == hipSuccess)
+        e = launch_losses(d_bbox_deltas, t->d_reg, d_bbox_labels, t->d_cls, n, update ? graw_reg : nullptr,
+                          update ? graw_cls : nullptr, d_losses, 1, t->d_lws, s);
+    if (e == hipSuccess && update) {
+        hipLaunchKernelGGL(head_dz_kernel, dim3(grid_for(P * nc)), dim3(256), 0, s, graw_reg, graw_cls, t->d_cls, losses_scale(t->d_lws, n),
+                           P, K, t->d_dz);
+        const int chunks = (int)((P + kChunkRows - 1) / kChunkRows);
+        const int dgrid = (int)((P + 15) / 16);
+        // head_{w,d}grad are instantiated for the anchor counts of the reference's configurations (5 K = 45: 3 ratios x 3 scales)
+        // and the other small tables up to K = 12
+        switch (nc) {
+#define RPN_HEAD_NC(NCV)                                                                                                          \
+    case NCV:                                                                                                                     \
+        hipLaunchKernelGGL(head_wgrad_kernel<NCV>, dim3(chunks), dim3(256), 0, s, t->d_S, t->d_dz, P, t->d_part);                \
+        hipLaunchKernelGGL(reduce_chunks_kernel, dim3(grid_for(513 * NCV)), dim3(256), 0, s, t->d_part, chunks, 513LL * NCV,      \
+                           t->d_g + t->off_hk);                                                                                   \
+        hipLaunchKernelGGL(head_dgrad_kernel<NCV>, dim3(dgrid), dim3(512), 0, s, t->d_S, t->d_dz, t->d_w + t->off_hk, P, t->d_dS); \
+        break;
+            RPN_HEAD_NC(5) RPN_HEAD_NC(10) RPN_HEAD_NC(15) RPN_HEAD_NC(20) RPN_HEAD_NC(25) RPN_HEAD_NC(30) RPN_HEAD_NC(35)
+            RPN_HEAD_NC(40) RPN_HEAD_NC(45) RPN_HEAD_NC(50) RPN_HEAD_NC(55) RPN_HEAD_NC(60)
+#undef RPN_HEAD_NC
+            default: return fail(RPN_ERR_UNSUPPORTED, "rpn_head_trainer_step: %d anchors per position", K);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = launch_wgrad(t->d_feat, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
+        if (e == hipSuccess) e = launch_colsum(t->d_dS, P, 512, t->d_part, t->d_g + t->off_cb, s);
+        if (e == hipSuccess) {
+            ++t->t;
+            hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)t->n)), dim3(256), 0, s, t->d_w, t->d_g, t->d_m, t->d_v, (long long)t->n,
+                               t->t, lr, beta_1, beta_2, epsilon);
+            e = hipGetLastError();
+        }
+    }
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: %s", hipGetErrorString(e));
+    t->last_B = B;
+    return RPN_OK;
+}
+
+extern "C" long long rpn_head_trainer_steps(const rpn_head_trainer *t) { return t ? t->t : -1; }
+
+extern "C" int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, int B, void *stream)
+{
+    RPN_REQUIRE(t && d_reg && d_cls, "rpn_head_trainer_outputs: null argument");
+    RPN_REQUIRE(B >= 1 && B == t->last_B, "rpn_head_trainer_outputs: batch %d, the last step ran %d images", B, t->last_B);
+    RPN_REQUIRE_DEVICE();
+    const size_t P = (size_t)B * t->F * t->F;
+    RPN_HIP_CHECK(hipMemcpyAsync(d_reg, t->d_reg, P * 4 * t->K * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
+    RPN_HIP_CHECK(hipMemcpyAsync(d_cls, t->d_cls, P * t->K * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
+    return RPN_OK;
+}

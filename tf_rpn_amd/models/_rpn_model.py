@@ -1,9 +1,11 @@
 """Python handle over the native ``rpn_model`` of librpn_hip.so -- the object that stands where
 the reference's Keras ``rpn_model`` stands (models/rpn_vgg16.py:21, predictor.py:41-50).
 
-Only the inference surface the proposal path touches is mirrored: ``predict_on_batch``,
-``__call__`` and ``load_weights`` (Keras ``.h5`` checkpoints through ``utils/h5_weights.py`` -- no h5py
-needed -- or a flat ``.npz``).
+The inference surface the proposal path touches is mirrored: ``predict_on_batch``, ``__call__`` and ``load_weights``
+(Keras ``.h5`` checkpoints through ``utils/h5_weights.py`` -- no h5py needed -- or a flat ``.npz``).
+Training mirrors trainer.py:54-69 (``compile`` with Adam, ``train_on_batch`` / ``test_on_batch`` / ``fit``) for the RPN head
+only: ``rpn_conv``, ``rpn_reg`` and ``rpn_cls`` are trained on a FROZEN backbone (the reference's Keras base model is
+trainable; backward through VGG16 / MobileNetV2 is not implemented here).
 """
 import ctypes
 
@@ -29,7 +31,14 @@ class FeatureExtractor(object):
         return self._model.get_activation(self.name)
 
 
+# the layers a training step updates (models/rpn_vgg16.py:18-20, models/rpn_mobilenet_v2.py:18-20)
+HEAD_LAYERS = ("rpn_conv", "rpn_cls", "rpn_reg")
+
+
 class RPNModel(object):
+    _t = None
+    _h = None
+
     def __init__(self, backbone, hyper_params, precision="f32", max_batch=8, keep_activations=False):
         if backbone not in L.BACKBONES:
             raise ValueError("unknown backbone %r" % (backbone,))
@@ -51,6 +60,10 @@ class RPNModel(object):
         self.flops_per_image = float(lib.rpn_model_flops_per_image(self._h))
         self.layers = self._enumerate_layers()
         self.tap_layer = "block5_conv3" if backbone == "vgg16" else "block_13_expand"
+        self._head = {}                 # head weights last given to set_weights / load_weights: {name: (kernel, bias)}
+        self._t = L.vp(0)               # native head trainer (compile)
+        self._opt = None
+        self._head_dirty = False        # the trainer's head differs from the handle's: copied before the next inference
 
     # ---- introspection ----------------------------------------------------------------
     def _enumerate_layers(self):
@@ -103,6 +116,10 @@ class RPNModel(object):
             else:
                 args += [None, None, None, None]
             L.check(lib.rpn_model_set_layer(self._h, name.encode(), *args), "rpn_model_set_layer(%s)" % name)
+            if name in HEAD_LAYERS:
+                self._head[name] = (kernel.copy(), bias.copy())
+                if self._t:
+                    self._trainer_set(name)
             done.append(name)
         return done
 
@@ -152,8 +169,9 @@ class RPNModel(object):
     __call__ = predict_on_batch
 
     def forward_into(self, x, reg, cls):
-        """Forward on preallocated CUDA tensors (no allocation: graph-capturable).  The C side sees raw pointers, so
-        dtype / device / layout / shape are checked here."""
+        """Forward on preallocated CUDA tensors (no allocation: graph-capturable once the head is in sync).  The C side sees
+        raw pointers, so dtype / device / layout / shape are checked here."""
+        self._sync_head()
         B = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else -1
         F, K = self.feature_map_shape, self.anchor_count
         for t, shape, what in ((x, (B, self.img_size, self.img_size, 3), "imgs"), (reg, (B, F, F, 4 * K), "reg"),
@@ -239,7 +257,164 @@ class RPNModel(object):
                                                  L.stream_ptr()), "rpn_model_get_activation")
         return out if batch is None else out[:batch]
 
+    # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
+    def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS):
+        """``rpn_model.compile(optimizer=tf.optimizers.Adam(learning_rate), loss=[reg_loss, cls_loss])`` (trainer.py:54-56).
+
+        Trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone -- unlike the reference, whose Keras
+        base model is trainable.  Adam is TF 2.0's ApplyAdam (as recalled from its sources): alpha = lr sqrt(1 - beta_2^t) /
+        (1 - beta_1^t), m += (g - m)(1 - beta_1), v += (g^2 - v)(1 - beta_2), w -= alpha m / (sqrt(v) + epsilon), m = v = 0 at
+        compile, t = the number of applied steps.  The trainer starts from the head weights last given to ``set_weights`` /
+        ``load_weights`` (or from the trained ones when compiled again)."""
+        if isinstance(trainable, str) or set(trainable) != set(HEAD_LAYERS):
+            raise ValueError("trainable=%r: only the RPN head is trained, on a frozen backbone -- trainable must be exactly %s "
+                             "(backward through the %s backbone is not implemented)" % (trainable, HEAD_LAYERS, self.backbone))
+        self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
+        if self._t:
+            self._head.update({k: (d["kernel"], d["bias"]) for k, d in self.get_weights().items()})
+            L.lib().rpn_head_trainer_destroy(self._t)
+            self._t = L.vp(0)
+        t = L.vp(0)
+        L.check(L.lib().rpn_head_trainer_create(self._h, ctypes.byref(t)), "rpn_head_trainer_create")
+        self._t = t
+        for name in self._head:
+            self._trainer_set(name)
+
+    def _trainer_set(self, name):
+        kernel, bias = self._head[name]
+        L.check(L.lib().rpn_head_trainer_set_layer(self._t, name.encode(), kernel.ctypes.data_as(L.c_float_p),
+                                                   bias.ctypes.data_as(L.c_float_p)), "rpn_head_trainer_set_layer(%s)" % name)
+
+    def get_gradients(self):
+        """{layer: {"kernel", "bias"}}: the gradient of the total loss at the last ``train_on_batch`` (test hook)."""
+        if not self._t:
+            raise RuntimeError("call compile() first")
+        out = {}
+        for layer in self.layers:
+            if layer["name"] in HEAD_LAYERS:
+                kernel = np.empty(layer["shape"], dtype=np.float32)
+                bias = np.empty((layer["shape"][3],), dtype=np.float32)
+                L.check(L.lib().rpn_head_trainer_get_gradient(self._t, layer["name"].encode(), kernel.ctypes.data_as(L.c_float_p),
+                                                              bias.ctypes.data_as(L.c_float_p), L.stream_ptr()),
+                        "rpn_head_trainer_get_gradient")
+                out[layer["name"]] = {"kernel": kernel, "bias": bias}
+        return out
+
+    def get_weights(self):
+        """{layer: {"kernel": HWIO, "bias"}} of the three head layers (the trained values once a step has run): what
+        ``save_weights`` writes and ``set_weights`` / ``load_weights`` read back."""
+        out = {}
+        for layer in self.layers:
+            name = layer["name"]
+            if name not in HEAD_LAYERS:
+                continue
+            if self._t:
+                kernel = np.empty(layer["shape"], dtype=np.float32)
+                bias = np.empty((layer["shape"][3],), dtype=np.float32)
+                L.check(L.lib().rpn_head_trainer_get_layer(self._t, name.encode(), kernel.ctypes.data_as(L.c_float_p),
+                                                           bias.ctypes.data_as(L.c_float_p),
+                                                           L.stream_ptr() if torch.cuda.is_available() else None),
+                        "rpn_head_trainer_get_layer(%s)" % name)
+            elif name in self._head:
+                kernel, bias = (a.copy() for a in self._head[name])
+            else:
+                continue
+            out[name] = {"kernel": kernel, "bias": bias}
+        return out
+
+    def _sync_head(self):
+        """After training: the trained head into the inference handle (once, before the next forward)."""
+        if not self._head_dirty:
+            return
+        lib = L.lib()
+        for name, d in self.get_weights().items():
+            L.check(lib.rpn_model_set_layer(self._h, name.encode(), d["kernel"].ctypes.data_as(L.c_float_p),
+                                            d["bias"].ctypes.data_as(L.c_float_p), None, None, None, None),
+                    "rpn_model_set_layer(%s)" % name)
+        self._head_dirty = False
+
+    def _step(self, x, y, update):
+        if not self._t:
+            raise RuntimeError("call compile() before training or evaluating the model")
+        if not isinstance(y, (tuple, list)) or len(y) != 2:
+            raise ValueError("y must be (bbox_deltas, bbox_labels), as rpn_generator yields it")
+        imgs, _ = L.to_device(x)
+        deltas, _ = L.to_device(y[0])
+        labels, _ = L.to_device(y[1])
+        B = int(imgs.shape[0]) if imgs.dim() == 4 else -1
+        F, K = self.feature_map_shape, self.anchor_count
+        if tuple(imgs.shape) != (B, self.img_size, self.img_size, 3):
+            raise ValueError("imgs must be (B,%d,%d,3) NHWC, got %s" % (self.img_size, self.img_size, tuple(imgs.shape)))
+        if deltas.numel() != B * F * F * K * 4 or labels.numel() != B * F * F * K:
+            raise ValueError("bbox_deltas must be (B,%d,4) and bbox_labels (B,%d,%d,%d); got %s, %s"
+                             % (F * F * K, F, F, K, tuple(deltas.shape), tuple(labels.shape)))
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("batch %d outside [1, %d]" % (B, self.max_batch))
+        losses = torch.empty((3,), dtype=torch.float32, device="cuda")
+        lr, b1, b2, eps = self._opt
+        L.check(L.lib().rpn_head_trainer_step(self._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(labels), 1 if update else 0, lr, b1,
+                                              b2, eps, L.ptr(losses), L.stream_ptr()), "rpn_head_trainer_step")
+        if update:
+            self._head_dirty = True
+        return losses, B
+
+    def train_on_batch(self, x, y):
+        """One Adam step on ``y = (bbox_deltas, bbox_labels)`` (what ``rpn_generator`` yields) -> [loss, rpn_reg_loss,
+        rpn_cls_loss], computed with the weights before the update (Keras order; loss = reg_loss + cls_loss, unit weights)."""
+        losses, _ = self._step(x, y, True)
+        return [float(v) for v in losses.cpu().numpy()]
+
+    def test_on_batch(self, x, y, return_outputs=False):
+        """[loss, rpn_reg_loss, rpn_cls_loss] without an update (Adam's t is not advanced).  ``return_outputs``: also the
+        float32 head outputs [rpn_reg (B,F,F,4K), rpn_cls (B,F,F,K)] of this evaluation, as CUDA tensors."""
+        losses, B = self._step(x, y, False)
+        out = [float(v) for v in losses.cpu().numpy()]
+        if not return_outputs:
+            return out
+        F, K = self.feature_map_shape, self.anchor_count
+        reg = torch.empty((B, F, F, 4 * K), dtype=torch.float32, device="cuda")
+        cls = torch.empty((B, F, F, K), dtype=torch.float32, device="cuda")
+        L.check(L.lib().rpn_head_trainer_outputs(self._t, L.ptr(reg), L.ptr(cls), B, L.stream_ptr()), "rpn_head_trainer_outputs")
+        return out, [reg, cls]
+
+    def train_steps(self):
+        """Adam's t: the number of applied steps since compile."""
+        return int(L.lib().rpn_head_trainer_steps(self._t)) if self._t else 0
+
+    def fit(self, generator, steps_per_epoch, epochs=1, validation_data=None, validation_steps=None):
+        """trainer.py:64-69 without the ModelCheckpoint callback: ``steps_per_epoch`` batches of ``generator`` per epoch, then
+        ``validation_steps`` batches of ``validation_data`` evaluated.  Returns the history dict of the per-epoch means:
+        {"loss", "rpn_reg_loss", "rpn_cls_loss"} (+ the same with a "val_" prefix)."""
+        keys = ("loss", "rpn_reg_loss", "rpn_cls_loss")
+        history = {k: [] for k in keys}
+        if validation_data is not None:
+            history.update({"val_" + k: [] for k in keys})
+        it = iter(generator)
+        vit = iter(validation_data) if validation_data is not None else None
+        for _epoch in range(int(epochs)):
+            sums = np.zeros(3)
+            for _ in range(int(steps_per_epoch)):
+                x, y = next(it)
+                sums += self.train_on_batch(x, y)
+            for k, v in zip(keys, sums / max(1, int(steps_per_epoch))):
+                history[k].append(float(v))
+            if vit is not None:
+                n = int(validation_steps) if validation_steps else 1
+                vs = np.zeros(3)
+                for _ in range(n):
+                    x, y = next(vit)
+                    vs += self.test_on_batch(x, y)
+                for k, v in zip(keys, vs / n):
+                    history["val_" + k].append(float(v))
+        return history
+
     def __del__(self):
+        try:
+            if self._t:
+                L.lib().rpn_head_trainer_destroy(self._t)
+                self._t = L.vp(0)
+        except Exception:
+            pass
         try:
             if self._h:
                 L.lib().rpn_model_destroy(self._h)

@@ -1,5 +1,5 @@
 """Configuration of the RPN proposal path: the host-side counterpart of the reference's
-``utils/train_utils.py:5-38`` (the ``RPN`` table and ``get_hyper_params``).  No device work.
+``utils/train_utils.py:5-38`` (the ``RPN`` table and ``get_hyper_params``), the device-side training targets and losses.
 
 Only the keys the forward / proposal path reads are documented here; the training-only
 counters (``total_pos_bboxes`` / ``total_neg_bboxes``) are carried so that a dict produced
@@ -122,3 +122,65 @@ def calculate_rpn_actual_outputs(anchors, gt_boxes, gt_labels, hyper_params, ran
             run(rp, draw(neg_maxval))
     labels = labels.view(B, fm, fm, K)
     return L.from_device(deltas, was_np), L.from_device(labels, was_np)
+
+
+def _loss_args(args):
+    """The reference's calling convention: (y_true, y_pred) or ((y_true, y_pred),) (utils/train_utils.py:155, :177)."""
+    if len(args) == 2:
+        return args[0], args[1]
+    if len(args) == 1 and isinstance(args[0], (tuple, list)) and len(args[0]) == 2:
+        return args[0][0], args[0][1]
+    raise TypeError("expected (y_true, y_pred) or ((y_true, y_pred),), got %d arguments" % len(args))
+
+
+def _rpn_losses(reg_true, reg_pred, cls_true, cls_pred, B, A):
+    import torch
+
+    from .. import _lib as L
+    lib = L.lib()
+    out = torch.empty((2,), dtype=torch.float32, device="cuda")
+    ws_bytes = int(lib.rpn_rpn_losses_workspace_bytes(B, A))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device="cuda")
+    L.check(lib.rpn_rpn_losses(L.ptr(reg_true), L.ptr(reg_pred), L.ptr(cls_true), L.ptr(cls_pred), B, A, L.ptr(out), None, None,
+                               L.ptr(ws), ws_bytes, L.stream_ptr()), "rpn_rpn_losses")
+    return out
+
+
+def cls_loss(*args):
+    """RPN objectness loss on the device (utils/train_utils.py:146-162): Keras ``BinaryCrossentropy()`` on PROBABILITIES over
+    the entries whose label is not -1, averaged over all of them in the batch (one pooled mean).  TF 2.0's form, restated
+    as recalled: p' = clip(p, 1e-7, 1 - 1e-7), -(t log(p' + 1e-7) + (1 - t) log(1 - p' + 1e-7)).  NaN when no label is kept
+    (mean of an empty tensor).  y_true (B,F,F,K) labels, y_pred (B,F,F,K); numpy or torch -> scalar (numpy float32 for
+    numpy input, a 0-d CUDA tensor for torch input)."""
+    import torch
+
+    from .. import _lib as L
+    y_true, y_pred = _loss_args(args)
+    t, was_np = L.to_device(y_true)
+    p, _ = L.to_device(y_pred)
+    if t.numel() != p.numel() or t.dim() < 1 or t.numel() == 0:
+        raise ValueError("y_true %s and y_pred %s must hold the same number of entries" % (tuple(t.shape), tuple(p.shape)))
+    B = int(t.shape[0])
+    A = t.numel() // B
+    zeros = torch.zeros((B, A, 4), dtype=torch.float32, device="cuda")
+    out = _rpn_losses(zeros, zeros, t, p, B, A)[1]
+    return out.cpu().numpy() if was_np else out
+
+
+def reg_loss(*args):
+    """RPN box regression loss on the device (utils/train_utils.py:164-185): y_pred (B,F,F,4K) viewed as (B,A,4); Huber
+    (delta 1) per ELEMENT (TF 2.0's huber_loss has no mean over the last axis), summed over the 4 coordinates, over the
+    anchors whose y_true (B,A,4) is not all zero, divided by max(1, n_pos).  numpy or torch -> scalar."""
+    import torch
+
+    from .. import _lib as L
+    y_true, y_pred = _loss_args(args)
+    t, was_np = L.to_device(y_true)
+    p, _ = L.to_device(y_pred)
+    if t.numel() != p.numel() or t.dim() < 1 or t.numel() == 0 or t.numel() % (4 * int(t.shape[0])):
+        raise ValueError("y_true %s must be (B,A,4) and y_pred %s hold B*A*4 entries" % (tuple(t.shape), tuple(p.shape)))
+    B = int(p.shape[0])
+    A = t.numel() // (4 * B)
+    labels = torch.full((B, A), -1.0, dtype=torch.float32, device="cuda")
+    out = _rpn_losses(t, p, labels, labels, B, A)[0]
+    return out.cpu().numpy() if was_np else out
