@@ -305,6 +305,37 @@ int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const
                           float *d_losses, void *stream);
 long long rpn_head_trainer_steps(const rpn_head_trainer *t);
 int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, int B, void *stream);
+/* the same trainer with the VGG16 backbone trained from `train_from` ("block1_conv1" .. "block5_conv3") upward: the reference's
+ * trainable Keras base model (models/rpn_vgg16.py:16-21) when train_from = "block1_conv1".  NULL: rpn_head_trainer_create.
+ * set_layer takes every VGG16 conv as well (all 13 must be set before a step): convs below train_from are frozen constants, outside
+ * Adam's buffer (get_layer returns them, get_gradient fails).  A step runs the whole VGG16 forward in exact float32 from the
+ * trainer's own weights (not the handle's ops), then the backward down to train_from; Adam updates head and trained convs in one
+ * launch.  Device memory (at the first step) is sized by max_batch and the trained span.  MobileNetV2 handles: RPN_ERR_INVALID. */
+int rpn_model_trainer_create(rpn_model *m, const char *train_from, rpn_head_trainer **out);
+
+/* backward of the VGG16 backbone, single-layer entries (float32; no floating-point atomics: bit-identical from run to run)
+ * rpn_conv3x3_dgrad: input gradient of a 3x3 stride-1 'same' conv, d_dx (B,H,W,Cin) = conv_transpose(d_dy (B,H,W,Cout), d_w HWIO),
+ *   i.e. dx[b][y][x][ci] = sum_{r,s,co} dy[b][y+1-r][x+1-s][co] w[r][s][ci][co] (zero outside); with d_mask (B,H,W,Cin) non-NULL
+ *   only the entries where mask > 0 are kept (the ReLU of the layer's input), the others are 0.  Cin % 4 == 0, Cout % 16 == 0.
+ *   d_ws: rpn_conv3x3_dgrad_workspace_bytes(Cin, Cout) bytes.
+ * rpn_maxpool2x2_backward: MaxPooling2D(2, 2) 'valid' backward fused with the ReLU mask of the pooled tensor: d_y (B,H,W,C) the
+ *   pool's input, d_dpool (B,H/2,W/2,C) -> d_dy_out (B,H,W,C): each window's gradient at its first maximum (row-major, replaced only
+ *   by a strictly greater value) when that maximum is > 0; every other entry, the rows / columns no window covers included, is 0.
+ *   C % 4 == 0, H, W >= 2.
+ * rpn_conv3x3_wgrad_wide: weight and bias gradient at backbone shapes, as rpn_conv3x3_wgrad computes them but with Cin = 3 accepted
+ *   and d_db required: the pixels are split into a power-of-two number of fixed ranges chosen from (B, H, W, Cin, Cout) alone,
+ *   summed in a fixed pairwise tree; db is one more row of the same GEMM.  Cin 3 or a multiple of 4, Cout % 4 == 0.
+ *   d_ws: rpn_conv3x3_wgrad_wide_workspace_bytes(...) bytes. */
+size_t rpn_conv3x3_dgrad_workspace_bytes(int Cin, int Cout);
+/* the input-channel width (128 | 64) of the workgroup tile rpn_conv3x3_dgrad runs on for a shape, chosen from the shape alone (the
+ * bits are the same either way); 0 for a bad shape.  Host only. */
+int rpn_conv3x3_dgrad_tile_n(int B, int H, int W, int Cin);
+int rpn_conv3x3_dgrad(const float *d_dy, const float *d_w, const float *d_mask, int B, int H, int W, int Cin, int Cout, float *d_dx,
+                      void *d_ws, size_t ws_bytes, void *stream);
+int rpn_maxpool2x2_backward(const float *d_y, const float *d_dpool, int B, int H, int W, int C, float *d_dy_out, void *stream);
+size_t rpn_conv3x3_wgrad_wide_workspace_bytes(int B, int H, int W, int Cin, int Cout);
+int rpn_conv3x3_wgrad_wide(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw, float *d_db,
+                           void *d_ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * single conv layer, for kernel-level parity tests and micro-benchmarks.

@@ -1,11 +1,18 @@
 """Milliseconds per head-training step (rpn_model.train_on_batch, trainer.py:64-69) and per kernel entry at batch 8, both backbones.
 
     python scripts/train_step_bench.py [--batch 8] [--steps 20] [--warmup 3]
+    python scripts/train_step_bench.py --train-backbone-from block1_conv1 [--batch 8] [--steps 20] [--warmup 3]
 
 Times on the device with HIP events around (a) a whole training step (backbone at the handle's precision + float32 head forward,
 losses, backward, Adam), (b) an evaluation step (no backward), (c) the 3x3 weight-gradient entry rpn_conv3x3_wgrad on the
 step's shape (its MFMA kernel + the leaf reduction) with its rate against the 157.3 TF/s float32-MFMA peak, (d) rpn_rpn_losses.
 Prints one JSON line per backbone.
+
+With --train-backbone-from LAYER (VGG16 only): (a) and (b) for the trainer that trains LAYER and every conv above it with the head
+(whole VGG16 forward in exact float32, backward down to LAYER), the step's FLOP (forward + backward, counted per layer) and its rate
+against the float32-MFMA peak, and per trained conv the single-layer entries rpn_conv3x3_dgrad (with its mask) and
+rpn_conv3x3_wgrad_wide on that layer's shape, timed with HIP events.  A rocprofv3 --kernel-trace --stats run of the same command
+gives the per-kernel totals.
 """
 import argparse
 import json
@@ -23,6 +30,12 @@ from tf_rpn_amd.models import rpn_mobilenet_v2, rpn_vgg16  # noqa: E402
 from tf_rpn_amd.utils import bbox_utils, train_utils  # noqa: E402
 
 PEAK_F32_MFMA = 157.3e12
+# (name, cin, cout, pool after) -- keras.applications.VGG16 up to block5_conv3
+VGG16 = [("block1_conv1", 3, 64, False), ("block1_conv2", 64, 64, True), ("block2_conv1", 64, 128, False),
+         ("block2_conv2", 128, 128, True), ("block3_conv1", 128, 256, False), ("block3_conv2", 256, 256, False),
+         ("block3_conv3", 256, 256, True), ("block4_conv1", 256, 512, False), ("block4_conv2", 512, 512, False),
+         ("block4_conv3", 512, 512, True), ("block5_conv1", 512, 512, False), ("block5_conv2", 512, 512, False),
+         ("block5_conv3", 512, 512, False)]
 
 
 def timed(fn, steps, warmup):
@@ -42,26 +55,11 @@ def bench(backbone, precision, B, steps, warmup):
     mod = rpn_vgg16 if backbone == "vgg16" else rpn_mobilenet_v2
     hp = train_utils.get_hyper_params(backbone)
     model, _ = mod.get_model(hp, precision=precision, max_batch=B)
-    F, K = model.feature_map_shape, model.anchor_count
-    rng = np.random.RandomState(0)
-    imgs = torch.from_numpy(rng.uniform(0, 1, size=(B, hp["img_size"], hp["img_size"], 3)).astype(np.float32)).cuda()
-    anchors = bbox_utils.generate_anchors(hp)
-    gt = np.zeros((B, 4, 4), np.float32)
-    gt[:, :, :2] = rng.uniform(0, 0.5, size=(B, 4, 2))
-    gt[:, :, 2:] = gt[:, :, :2] + rng.uniform(0.2, 0.5, size=(B, 4, 2))
-    labels = np.ones((B, 4), np.int32)
-    deltas, lab = train_utils.calculate_rpn_actual_outputs(anchors, torch.from_numpy(gt).cuda(), torch.from_numpy(labels).cuda(), hp)
-    deltas, lab = deltas.contiguous(), lab.contiguous()
+    imgs, deltas, lab = step_inputs(model, hp, B)
     model.compile(learning_rate=1e-5)
     lib = L.lib()
-    losses = torch.empty(3, device="cuda")
-
-    def step(update):
-        L.check(lib.rpn_head_trainer_step(model._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(lab), update, 1e-5, 0.9, 0.999, 1e-7,
-                                          L.ptr(losses), L.stream_ptr()), "rpn_head_trainer_step")
-
-    ms_train = timed(lambda: step(1), steps, warmup)
-    ms_eval = timed(lambda: step(0), steps, warmup)
+    ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
+    F, K = model.feature_map_shape, model.anchor_count
     cin = 512 if backbone == "vgg16" else 576
     x = torch.randn((B, F, F, cin), device="cuda")
     dy = torch.randn((B, F, F, 512), device="cuda")
@@ -87,14 +85,96 @@ def bench(backbone, precision, B, steps, warmup):
             "ms_losses": round(ms_loss, 4)}
 
 
+def step_inputs(model, hp, B):
+    rng = np.random.RandomState(0)
+    imgs = torch.from_numpy(rng.uniform(0, 1, size=(B, hp["img_size"], hp["img_size"], 3)).astype(np.float32)).cuda()
+    anchors = bbox_utils.generate_anchors(hp)
+    gt = np.zeros((B, 4, 4), np.float32)
+    gt[:, :, :2] = rng.uniform(0, 0.5, size=(B, 4, 2))
+    gt[:, :, 2:] = gt[:, :, :2] + rng.uniform(0.2, 0.5, size=(B, 4, 2))
+    labels = np.ones((B, 4), np.int32)
+    deltas, lab = train_utils.calculate_rpn_actual_outputs(anchors, torch.from_numpy(gt).cuda(), torch.from_numpy(labels).cuda(), hp)
+    return imgs, deltas.contiguous(), lab.contiguous()
+
+
+def step_times(model, imgs, deltas, lab, B, steps, warmup):
+    """ms per training step (update = 1) and per evaluation step (update = 0)."""
+    lib = L.lib()
+    losses = torch.empty(3, device="cuda")
+
+    def step(update):
+        L.check(lib.rpn_head_trainer_step(model._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(lab), update, 1e-5, 0.9, 0.999, 1e-7,
+                                          L.ptr(losses), L.stream_ptr()), "rpn_head_trainer_step")
+
+    return timed(lambda: step(1), steps, warmup), timed(lambda: step(0), steps, warmup)
+
+
+def frac(flop, ms):
+    return round(flop / (ms * 1e-3) / PEAK_F32_MFMA, 3)
+
+
+def bench_backbone(train_from, precision, B, steps, warmup):
+    hp = train_utils.get_hyper_params("vgg16")
+    model, _ = rpn_vgg16.get_model(hp, precision=precision, max_batch=B)
+    imgs, deltas, lab = step_inputs(model, hp, B)
+    model.compile(learning_rate=1e-5, train_backbone_from=train_from)
+    ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
+    lib = L.lib()
+    F, K = model.feature_map_shape, model.anchor_count
+    first = [v[0] for v in VGG16].index(train_from)
+    # FLOP: the forward of the whole model, then per trained conv its wgrad and (above the first trained one) its dgrad; rpn_conv's
+    # wgrad and dgrad; the 1x1 head's two backward GEMMs
+    fwd = model.flops_per_image * B
+    bwd = 2.0 * 2 * 9 * 512 * 512 * B * F * F + 2.0 * 2 * 512 * 5 * K * B * F * F
+    layers = []
+    H = hp["img_size"]
+    for i, (name, cin, cout, pool) in enumerate(VGG16):
+        f = 2.0 * 9 * cin * cout * B * H * H
+        if i >= first:
+            bwd += f + (f if i > first else 0.0)
+            x = torch.randn((B, H, H, cin), device="cuda")
+            dy = torch.randn((B, H, H, cout), device="cuda")
+            mask = torch.randn((B, H, H, cin), device="cuda")
+            dw = torch.empty((3, 3, cin, cout), device="cuda")
+            db = torch.empty((cout,), device="cuda")
+            nw = lib.rpn_conv3x3_wgrad_wide_workspace_bytes(B, H, H, cin, cout)
+            ws = torch.empty(nw, dtype=torch.uint8, device="cuda")
+            ms_w = timed(lambda: L.check(lib.rpn_conv3x3_wgrad_wide(L.ptr(x), L.ptr(dy), B, H, H, cin, cout, L.ptr(dw), L.ptr(db),
+                                                                    L.ptr(ws), nw, L.stream_ptr()), "rpn_conv3x3_wgrad_wide"),
+                         steps, warmup)
+            row = {"layer": name, "H": H, "cin": cin, "cout": cout, "gflop": round(f / 1e9, 2), "ms_wgrad": round(ms_w, 4),
+                   "wgrad_frac_of_f32_mfma_peak": frac(f, ms_w)}
+            if i > first:
+                dx = torch.empty((B, H, H, cin), device="cuda")
+                nd = lib.rpn_conv3x3_dgrad_workspace_bytes(cin, cout)
+                wsd = torch.empty(nd, dtype=torch.uint8, device="cuda")
+                ms_d = timed(lambda: L.check(lib.rpn_conv3x3_dgrad(L.ptr(dy), L.ptr(dw), L.ptr(mask), B, H, H, cin, cout, L.ptr(dx),
+                                                                   L.ptr(wsd), nd, L.stream_ptr()), "rpn_conv3x3_dgrad"),
+                             steps, warmup)
+                row.update({"ms_dgrad": round(ms_d, 4), "dgrad_frac_of_f32_mfma_peak": frac(f, ms_d)})
+            layers.append(row)
+            del x, dy, mask, ws
+        if pool:
+            H //= 2
+    total = fwd + bwd
+    return {"backbone": "vgg16", "train_backbone_from": train_from, "precision": precision, "batch": B,
+            "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "step_tflop": round(total / 1e12, 3),
+            "step_tflops": round(total / (ms_train * 1e-3) / 1e12, 2), "step_frac_of_f32_mfma_peak": frac(total, ms_train),
+            "layers": layers}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", default="f16x3")
+    ap.add_argument("--train-backbone-from", default=None, help="a VGG16 conv: time the trainer that trains it and the convs above")
     args = ap.parse_args()
     L.require_gpu()
+    if args.train_backbone_from:
+        print(json.dumps(bench_backbone(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        return
     for backbone in ("vgg16", "mobilenet_v2"):
         print(json.dumps(bench(backbone, args.precision, args.batch, args.steps, args.warmup)), flush=True)
 

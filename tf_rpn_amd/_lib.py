@@ -81,6 +81,13 @@ _SIGNATURES = {
     "rpn_head_trainer_step": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int] + [ctypes.c_float] * 4 + [vp, vp]),
     "rpn_head_trainer_steps": (ctypes.c_longlong, [vp]),
     "rpn_head_trainer_outputs": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, vp]),
+    "rpn_model_trainer_create": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(vp)]),
+    "rpn_conv3x3_dgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "rpn_conv3x3_dgrad_tile_n": (ctypes.c_int, [ctypes.c_int] * 4),
+    "rpn_conv3x3_dgrad": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, ctypes.c_size_t, vp]),
+    "rpn_maxpool2x2_backward": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
+    "rpn_conv3x3_wgrad_wide_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "rpn_conv3x3_wgrad_wide": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]),
     "rpn_conv2d": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 10 + [vp, vp]),
     "rpn_maxpool2x2": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_dwconv3x3": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),

@@ -1097,6 +1097,11 @@ void model_train_dims(const rpn_model *m, int *cin, int *F, int *K, int *max_bat
     *cin = t.C; *F = m->F; *K = m->K; *max_batch = m->max_batch;
 }
 
+void model_train_backbone(const rpn_model *m, int *backbone, int *img_size)
+{
+    *backbone = m->backbone; *img_size = m->img_size;
+}
+
 // The backbone of a training step (the head is trained on frozen features): the ops up to the one that writes feat_tensor, at the
 // handle's own precision, then the features as NHWC float32 into d_feat (B, F, F, Cin) -- converted from the split form when the
 // tensor is kept that way, as rpn_model_get_activation does.

@@ -58,6 +58,8 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 namespace rpn {
 // channels of the backbone features, feature-map side F, anchors per position K, the handle's largest batch
 void model_train_dims(const rpn_model *m, int *cin, int *F, int *K, int *max_batch);
+// the handle's backbone (RPN_BACKBONE_*) and input side
+void model_train_backbone(const rpn_model *m, int *backbone, int *img_size);
 // the ops up to the backbone features on stream s, then the features as NHWC float32 (B, F, F, cin) into d_feat
 int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s);
 }  // namespace rpn

@@ -1,8 +1,10 @@
 // train_kernels.hip -- training of the RPN head (rpn_conv, rpn_cls, rpn_reg) on a frozen backbone: the counterpart of the
 // reference's trainer.py:54-69 (compile with Adam(1e-5) and loss=[reg_loss, cls_loss], then fit).
 //
-// Unlike the reference, whose Keras base model is trainable, only the head is trained here: backward through VGG16 /
-// MobileNetV2 is not implemented.  The step is
+// rpn_head_trainer_create trains the head on a frozen backbone; rpn_model_trainer_create also trains the VGG16 convs from a given one
+// up (the reference's Keras base model is trainable): the step then runs the whole VGG16 forward in exact float32 from the trainer's
+// weights (backbone_forward) and, after the head's backward below, the backbone's (backbone_backward; kernels in
+// train_backbone_kernels.hip).  MobileNetV2 trains its head only.  The head-only step is
 //   backbone (the handle's own ops and precision) -> X (B,F,F,Cin) float32
 //   rpn_conv (exact float32, ReLU) -> S (P,512), P = B F F;  fused 1x1 head -> reg (P,4K) linear | cls (P,K) sigmoid
 //   losses + their gradients (one pass, fixed-order reductions)
@@ -27,6 +29,7 @@
 
 #include "conv_kernels.h"
 #include "rpn_common.h"
+#include "train_backbone.h"
 
 namespace rpn {
 
@@ -497,6 +500,17 @@ struct rpn_head_trainer {
     float *d_part = nullptr;
     void *d_lws = nullptr;
     PackedShape ps_conv{}, ps_head{};
+    // ---- the VGG16 backbone (rpn_model_trainer_create; train_kernels.hip: backbone_*) ----
+    // bb_from: the first trained conv (index into kVgg), -1 on a head-only trainer.  Trained convs bb_from .. 12 follow the head in
+    // the flat buffers (kernel HWIO, then bias, at off_bk / off_bb); the frozen ones live in host_frozen / d_frozen at the same offsets.
+    int bb_from = -1, img = 0;
+    int hs[13] = {};                             // spatial side of each conv's input and output
+    size_t off_bk[13] = {}, off_bb[13] = {};
+    bool bb_loaded[13] = {};
+    std::vector<float> host_frozen;
+    PackedShape ps_bb[13]{};
+    float *d_frozen = nullptr, *d_pack = nullptr, *d_wt = nullptr, *d_wpart = nullptr, *d_img4 = nullptr;
+    float *d_act[13] = {}, *d_pool[13] = {}, *d_ping[2] = {}, *d_grad[2] = {};
 };
 
 namespace {
@@ -510,6 +524,35 @@ int layer_index(const char *name)
     return -1;
 }
 
+// the 13 convs of VGG16 (models/rpn_vgg16.py: keras.applications.VGG16 up to block5_conv3), each 3x3 'same' + ReLU;
+// pool: MaxPooling2D(2, 2) 'valid' after the conv
+struct VggConv {
+    const char *name;
+    int cin, cout;
+    bool pool;
+};
+const VggConv kVgg[13] = {{"block1_conv1", 3, 64, false},    {"block1_conv2", 64, 64, true},    {"block2_conv1", 64, 128, false},
+                          {"block2_conv2", 128, 128, true},  {"block3_conv1", 128, 256, false}, {"block3_conv2", 256, 256, false},
+                          {"block3_conv3", 256, 256, true},  {"block4_conv1", 256, 512, false}, {"block4_conv2", 512, 512, false},
+                          {"block4_conv3", 512, 512, true},  {"block5_conv1", 512, 512, false}, {"block5_conv2", 512, 512, false},
+                          {"block5_conv3", 512, 512, false}};
+
+int vgg_index(const char *name)
+{
+    for (int i = 0; i < 13; ++i)
+        if (!strcmp(name, kVgg[i].name)) return i;
+    return -1;
+}
+
+size_t vgg_kernel_floats(int i) { return (size_t)9 * kVgg[i].cin * kVgg[i].cout; }
+// a backbone conv's kernel and bias on the device: the master weights when trained, the frozen constants otherwise
+const float *vgg_w(const rpn_head_trainer *t, int i) { return (i >= t->bb_from ? t->d_w : t->d_frozen) + t->off_bk[i]; }
+const float *vgg_b(const rpn_head_trainer *t, int i) { return (i >= t->bb_from ? t->d_w : t->d_frozen) + t->off_bb[i]; }
+// a forward tensor the backward reads: conv i's ReLU output and its pooled form, from the input of the first trained conv upward
+bool vgg_kept(const rpn_head_trainer *t, int i) { return i >= t->bb_from - 1; }
+size_t vgg_act_floats(const rpn_head_trainer *t, int i) { return (size_t)t->max_batch * t->hs[i] * t->hs[i] * kVgg[i].cout; }
+size_t vgg_pool_floats(const rpn_head_trainer *t, int i) { return (size_t)t->max_batch * (t->hs[i] / 2) * (t->hs[i] / 2) * kVgg[i].cout; }
+
 size_t trainer_part_floats(const rpn_head_trainer *t)
 {
     const long long P = (long long)t->max_batch * t->F * t->F;
@@ -517,10 +560,66 @@ size_t trainer_part_floats(const rpn_head_trainer *t)
     return std::max(std::max(chunks * 513 * t->nc, wgrad_ws_floats(t->cin, 512)), colsum_ws_floats(P, 512));
 }
 
-int trainer_device(rpn_head_trainer *t)
+// the backbone's buffers, sized by max_batch and the trained span (about 3.5 GB at batch 8, 500 x 500, from block1_conv1)
+int backbone_device(rpn_head_trainer *t)
 {
-    if (!have_device()) return RPN_ERR_NO_DEVICE;
-    if (t->d_w) return RPN_OK;
+    size_t pack = 0, ping = 0, grad = 0, wpart = 0;
+    for (int i = 0; i < 13; ++i) {
+        if (i > 0) pack = std::max(pack, t->ps_bb[i].floats());
+        if (!vgg_kept(t, i)) ping = std::max(ping, std::max(vgg_act_floats(t, i), kVgg[i].pool ? vgg_pool_floats(t, i) : 0));
+        if (i >= t->bb_from) {
+            grad = std::max(grad, vgg_act_floats(t, i));
+            wpart = std::max(wpart, wgrad_wide_ws_floats(t->max_batch, t->hs[i], t->hs[i], kVgg[i].cin, kVgg[i].cout));
+        }
+    }
+    RPN_HIP_CHECK(hipMalloc(&t->d_frozen, std::max<size_t>(1, t->host_frozen.size()) * sizeof(float)));
+    if (!t->host_frozen.empty())
+        RPN_HIP_CHECK(hipMemcpy(t->d_frozen, t->host_frozen.data(), t->host_frozen.size() * sizeof(float), hipMemcpyHostToDevice));
+    RPN_HIP_CHECK(hipMalloc(&t->d_pack, pack * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_wt, (size_t)9 * 512 * 512 * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_wpart, wpart * sizeof(float)));
+    for (int u = 0; u < 2; ++u) {
+        RPN_HIP_CHECK(hipMalloc(&t->d_grad[u], grad * sizeof(float)));
+        if (ping) RPN_HIP_CHECK(hipMalloc(&t->d_ping[u], ping * sizeof(float)));
+    }
+    if (t->bb_from == 0) RPN_HIP_CHECK(hipMalloc(&t->d_img4, (size_t)t->max_batch * t->img * t->img * 4 * sizeof(float)));
+    for (int i = 0; i < 13; ++i) {
+        if (!vgg_kept(t, i)) continue;
+        RPN_HIP_CHECK(hipMalloc(&t->d_act[i], vgg_act_floats(t, i) * sizeof(float)));
+        if (kVgg[i].pool) RPN_HIP_CHECK(hipMalloc(&t->d_pool[i], vgg_pool_floats(t, i) * sizeof(float)));
+    }
+    return RPN_OK;
+}
+
+// every device buffer of the trainer freed and its pointer reset (destroy, or a failed first-step allocation)
+void trainer_free(rpn_head_trainer *t)
+{
+    float *bufs[] = {t->d_w, t->d_g, t->d_m, t->d_v, t->d_pconv, t->d_phead, t->d_feat, t->d_S, t->d_reg, t->d_cls, t->d_graw, t->d_dz,
+                     t->d_dS, t->d_part};
+    for (float *p : bufs)
+        if (p) (void)hipFree(p);
+    if (t->d_lws) (void)hipFree(t->d_lws);
+    t->d_w = t->d_g = t->d_m = t->d_v = t->d_pconv = t->d_phead = t->d_feat = t->d_S = t->d_reg = t->d_cls = nullptr;
+    t->d_graw = t->d_dz = t->d_dS = t->d_part = nullptr;
+    t->d_lws = nullptr;
+    float *bb[] = {t->d_frozen, t->d_pack, t->d_wt, t->d_wpart, t->d_img4, t->d_ping[0], t->d_ping[1], t->d_grad[0], t->d_grad[1]};
+    for (float *p : bb)
+        if (p) (void)hipFree(p);
+    for (int i = 0; i < 13; ++i) {
+        if (t->d_act[i]) (void)hipFree(t->d_act[i]);
+        if (t->d_pool[i]) (void)hipFree(t->d_pool[i]);
+        t->d_act[i] = t->d_pool[i] = nullptr;
+    }
+    t->d_frozen = t->d_pack = t->d_wt = t->d_wpart = t->d_img4 = nullptr;
+    t->d_ping[0] = t->d_ping[1] = t->d_grad[0] = t->d_grad[1] = nullptr;
+}
+
+int trainer_alloc(rpn_head_trainer *t)
+{
+    if (t->bb_from >= 0) {
+        const int st = backbone_device(t);
+        if (st != RPN_OK) return st;
+    }
     const size_t P = (size_t)t->max_batch * t->F * t->F;
     float **bufs[] = {&t->d_w, &t->d_g, &t->d_m, &t->d_v, &t->d_pconv, &t->d_phead, &t->d_feat, &t->d_S, &t->d_reg, &t->d_cls,
                       &t->d_graw, &t->d_dz, &t->d_dS, &t->d_part};
@@ -534,13 +633,83 @@ int trainer_device(rpn_head_trainer *t)
     return RPN_OK;
 }
 
-void trainer_free(rpn_head_trainer *t)
+// all device buffers at the first step; d_w is set only when every allocation and upload succeeded (a failure frees what was
+// allocated, so a later step starts over instead of running on a half-built trainer)
+int trainer_device(rpn_head_trainer *t)
 {
-    float *bufs[] = {t->d_w, t->d_g, t->d_m, t->d_v, t->d_pconv, t->d_phead, t->d_feat, t->d_S, t->d_reg, t->d_cls, t->d_graw, t->d_dz,
-                     t->d_dS, t->d_part};
-    for (float *p : bufs)
-        if (p) (void)hipFree(p);
-    if (t->d_lws) (void)hipFree(t->d_lws);
+    if (!have_device()) return RPN_ERR_NO_DEVICE;
+    if (t->d_w) return RPN_OK;
+    const int st = trainer_alloc(t);
+    if (st != RPN_OK) trainer_free(t);
+    return st;
+}
+
+// The whole VGG16 forward in exact float32 from the trainer's weights (the frozen prefix included), keeping what the backward
+// reads -> the block5_conv3 output (B, F, F, 512).  Weights are packed on the device at every step: the trained ones move.
+hipError_t backbone_forward(rpn_head_trainer *t, const float *d_imgs, int B, hipStream_t s, const float **feat)
+{
+    const float *in = d_imgs;
+    int ping = 0;
+    auto next = [&](float *kept) -> float * {
+        if (kept) return kept;
+        float *p = t->d_ping[ping];
+        ping ^= 1;
+        return p;
+    };
+    if (t->bb_from == 0) {
+        const hipError_t e = launch_pad_channels3to4(d_imgs, (long long)B * t->img * t->img, t->d_img4, s);
+        if (e != hipSuccess) return e;
+    }
+    for (int i = 0; i < 13; ++i) {
+        const int H = t->hs[i];
+        float *out = next(t->d_act[i]);
+        hipError_t e;
+        if (i == 0) {
+            e = launch_conv_cin3(in, vgg_w(t, 0), vgg_b(t, 0), out, B, H, H, H, H, kVgg[0].cout, 1, 1, 1, ACT_RELU, 0, false, s);
+        } else {
+            pack_weights_device(t->ps_bb[i], vgg_w(t, i), t->d_pack, s);
+            ConvArgs a{};
+            a.x = in; a.w = t->d_pack; a.bias = vgg_b(t, i); a.residual = nullptr;
+            a.out = out; a.out2 = nullptr;
+            a.B = B; a.H = H; a.W = H; a.Cin = kVgg[i].cin; a.OH = H; a.OW = H; a.Cout = kVgg[i].cout;
+            a.R = 3; a.S = 3; a.stride = 1; a.pad_t = 1; a.pad_l = 1; a.ps = t->ps_bb[i];
+            a.act = ACT_RELU; a.act2 = ACT_LINEAR; a.split = kVgg[i].cout; a.ld1 = kVgg[i].cout; a.ld2 = 0;
+            e = launch_conv_f32(a, s);
+        }
+        if (e != hipSuccess) return e;
+        in = out;
+        if (kVgg[i].pool) {
+            float *po = next(t->d_pool[i]);
+            e = launch_maxpool2x2(in, B, H, H, kVgg[i].cout, po, s);
+            if (e != hipSuccess) return e;
+            in = po;
+        }
+    }
+    *feat = in;
+    return hipSuccess;
+}
+
+// From dS (rpn_conv's pre-activation gradient) down to the first trained conv: dgrad (+ the ReLU mask of its input) or dgrad + the
+// max-pool backward (+ the mask of the pooled conv) between layers, the weight and bias gradient of each trained conv.
+hipError_t backbone_backward(rpn_head_trainer *t, int B, hipStream_t s)
+{
+    float *g = t->d_grad[0], *h = t->d_grad[1];
+    const int F = t->hs[12];
+    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, t->d_act[12], B, F, F, t->cin, 512, t->d_wt, g, s);
+    for (int i = 12; i >= t->bb_from && e == hipSuccess; --i) {
+        const int H = t->hs[i];
+        const float *x = i == 0 ? t->d_img4 : (kVgg[i - 1].pool ? t->d_pool[i - 1] : t->d_act[i - 1]);
+        e = launch_wgrad_wide(x, g, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wpart, t->d_g + t->off_bk[i], t->d_g + t->off_bb[i], s);
+        if (e != hipSuccess || i == t->bb_from) break;
+        if (kVgg[i - 1].pool) {
+            e = launch_conv3x3_dgrad(g, vgg_w(t, i), nullptr, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wt, h, s);
+            if (e == hipSuccess) e = launch_maxpool2x2_backward(t->d_act[i - 1], h, B, t->hs[i - 1], t->hs[i - 1], kVgg[i - 1].cout, g, s);
+        } else {
+            e = launch_conv3x3_dgrad(g, vgg_w(t, i), t->d_act[i - 1], B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wt, h, s);
+            std::swap(g, h);
+        }
+    }
+    return e;
 }
 
 }  // namespace
@@ -565,6 +734,46 @@ extern "C" int rpn_head_trainer_create(rpn_model *m, rpn_head_trainer **out)
     return RPN_OK;
 }
 
+extern "C" int rpn_model_trainer_create(rpn_model *m, const char *train_from, rpn_head_trainer **out)
+{
+    RPN_REQUIRE(m && out, "rpn_model_trainer_create: null argument");
+    if (!train_from) return rpn_head_trainer_create(m, out);
+    int backbone, img;
+    model_train_backbone(m, &backbone, &img);
+    RPN_REQUIRE(backbone == RPN_BACKBONE_VGG16,
+                "rpn_model_trainer_create: backbone training needs VGG16 (MobileNetV2 trains its head only: its backward needs "
+                "depthwise convs and BatchNorm in training mode)");
+    const int from = vgg_index(train_from);
+    RPN_REQUIRE(from >= 0, "rpn_model_trainer_create: '%s' is not a VGG16 conv (block1_conv1 .. block5_conv3)", train_from);
+    int hs[13];
+    for (int i = 0, h = img; i < 13; ++i) {
+        hs[i] = h;
+        if (kVgg[i].pool) h /= 2;
+    }
+    rpn_head_trainer *t = nullptr;
+    const int st = rpn_head_trainer_create(m, &t);
+    if (st != RPN_OK) return st;
+    if (t->cin != 512 || t->F != hs[12] || hs[12] < 1) {
+        rpn_head_trainer_destroy(t);
+        return fail(RPN_ERR_UNSUPPORTED, "rpn_model_trainer_create: unexpected VGG16 graph (features %d, F %d)", t->cin, t->F);
+    }
+    t->bb_from = from;
+    t->img = img;
+    size_t frozen = 0;
+    for (int i = 0; i < 13; ++i) {
+        t->hs[i] = hs[i];
+        size_t &off = i >= from ? t->n : frozen;
+        t->off_bk[i] = off;
+        t->off_bb[i] = off + vgg_kernel_floats(i);
+        off = t->off_bb[i] + kVgg[i].cout;
+        if (i > 0) t->ps_bb[i] = packed_shape(3, 3, kVgg[i].cin, kVgg[i].cout);
+    }
+    t->host_w.assign(t->n, 0.0f);
+    t->host_frozen.assign(frozen, 0.0f);
+    *out = t;
+    return RPN_OK;
+}
+
 extern "C" void rpn_head_trainer_destroy(rpn_head_trainer *t)
 {
     if (!t) return;
@@ -576,8 +785,21 @@ extern "C" int rpn_head_trainer_set_layer(rpn_head_trainer *t, const char *name,
 {
     RPN_REQUIRE(t && name && kernel && bias, "rpn_head_trainer_set_layer: null argument");
     const int li = layer_index(name);
-    RPN_REQUIRE(li >= 0, "rpn_head_trainer_set_layer: '%s' is not trained (the backbone is frozen: rpn_conv, rpn_reg, rpn_cls only)",
+    const int bi = t->bb_from >= 0 ? vgg_index(name) : -1;
+    RPN_REQUIRE(li >= 0 || bi >= 0, "rpn_head_trainer_set_layer: '%s' is not trained (the backbone is frozen: rpn_conv, rpn_reg, rpn_cls only)",
                 name);
+    if (bi >= 0) {
+        // a trained conv: its slices of the master weights; a frozen one: the constants
+        const bool trained = bi >= t->bb_from;
+        std::vector<float> &w = trained ? t->host_w : t->host_frozen;
+        float *dev = trained ? t->d_w : t->d_frozen;
+        if (dev && trained) RPN_HIP_CHECK(hipMemcpy(w.data(), dev, w.size() * sizeof(float), hipMemcpyDeviceToHost));
+        memcpy(&w[t->off_bk[bi]], kernel, vgg_kernel_floats(bi) * sizeof(float));
+        memcpy(&w[t->off_bb[bi]], bias, kVgg[bi].cout * sizeof(float));
+        if (dev) RPN_HIP_CHECK(hipMemcpy(dev, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        t->bb_loaded[bi] = true;
+        return RPN_OK;
+    }
     // the layer's slices of the flat master buffer: (offset, row length, row stride, rows) for the kernel, then the bias
     std::vector<float> &w = t->host_w;
     if (t->d_w) RPN_HIP_CHECK(hipMemcpy(w.data(), t->d_w, t->n * sizeof(float), hipMemcpyDeviceToHost));
@@ -599,9 +821,17 @@ static int trainer_read(rpn_head_trainer *t, const char *what, const char *name,
 {
     RPN_REQUIRE(t && name && kernel && bias, "%s: null argument", what);
     const int li = layer_index(name);
-    RPN_REQUIRE(li >= 0, "%s: '%s' is not trained (rpn_conv, rpn_reg, rpn_cls)", what, name);
-    RPN_REQUIRE(t->loaded[li], "%s: layer '%s' was never set", what, name);
+    const int bi = t->bb_from >= 0 ? vgg_index(name) : -1;
+    RPN_REQUIRE(li >= 0 || bi >= 0, "%s: '%s' is not trained (rpn_conv, rpn_reg, rpn_cls)", what, name);
+    RPN_REQUIRE(li >= 0 ? t->loaded[li] : t->bb_loaded[bi], "%s: layer '%s' was never set", what, name);
+    RPN_REQUIRE(!grad || bi < 0 || bi >= t->bb_from, "%s: layer '%s' is frozen (training starts at %s): it has no gradient", what, name,
+                bi >= 0 ? kVgg[std::max(t->bb_from, 0)].name : "");
     RPN_REQUIRE(!grad || t->t > 0, "%s: no update step has run", what);
+    if (bi >= 0 && bi < t->bb_from) {           // a frozen conv: its constants
+        memcpy(kernel, &t->host_frozen[t->off_bk[bi]], vgg_kernel_floats(bi) * sizeof(float));
+        memcpy(bias, &t->host_frozen[t->off_bb[bi]], kVgg[bi].cout * sizeof(float));
+        return RPN_OK;
+    }
     std::vector<float> gbuf;
     if (grad) gbuf.resize(t->n);
     std::vector<float> &w = grad ? gbuf : t->host_w;
@@ -609,7 +839,10 @@ static int trainer_read(rpn_head_trainer *t, const char *what, const char *name,
         RPN_HIP_CHECK(hipMemcpyAsync(w.data(), grad ? t->d_g : t->d_w, t->n * sizeof(float), hipMemcpyDeviceToHost, as_stream(stream)));
         RPN_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
     }
-    if (li == 0) {
+    if (bi >= 0) {
+        memcpy(kernel, &w[t->off_bk[bi]], vgg_kernel_floats(bi) * sizeof(float));
+        memcpy(bias, &w[t->off_bb[bi]], kVgg[bi].cout * sizeof(float));
+    } else if (li == 0) {
         memcpy(kernel, &w[t->off_ck], (size_t)9 * t->cin * 512 * sizeof(float));
         memcpy(bias, &w[t->off_cb], 512 * sizeof(float));
     } else {
@@ -641,18 +874,27 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
                             std::isfinite(epsilon) && epsilon >= 0.0f),
                 "rpn_head_trainer_step: bad Adam hyper-parameters");
     for (int i = 0; i < 3; ++i) RPN_REQUIRE(t->loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kHeadLayers[i]);
+    if (t->bb_from >= 0)
+        for (int i = 0; i < 13; ++i) RPN_REQUIRE(t->bb_loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kVgg[i].name);
     const int st = trainer_device(t);
     if (st != RPN_OK) return st;
     hipStream_t s = as_stream(stream);
     const int F = t->F, K = t->K, nc = t->nc;
     const long long P = (long long)B * F * F;
-    const int e0 = model_features(t->m, d_imgs, B, t->d_feat, s);
-    if (e0 != RPN_OK) return e0;
+    const float *feat = t->d_feat;
+    if (t->bb_from >= 0) {
+        // a trained backbone: the whole VGG16 in exact float32 from the trainer's weights
+        const hipError_t eb = backbone_forward(t, d_imgs, B, s, &feat);
+        if (eb != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: backbone: %s", hipGetErrorString(eb));
+    } else {
+        const int e0 = model_features(t->m, d_imgs, B, t->d_feat, s);
+        if (e0 != RPN_OK) return e0;
+    }
     // head forward in exact float32 from the master weights
     pack_weights_device(t->ps_conv, t->d_w + t->off_ck, t->d_pconv, s);
     pack_weights_device(t->ps_head, t->d_w + t->off_hk, t->d_phead, s);
     ConvArgs a{};
-    a.x = t->d_feat; a.w = t->d_pconv; a.bias = t->d_w + t->off_cb; a.residual = nullptr;
+    a.x = feat; a.w = t->d_pconv; a.bias = t->d_w + t->off_cb; a.residual = nullptr;
     a.out = t->d_S; a.out2 = nullptr;
     a.B = B; a.H = F; a.W = F; a.Cin = t->cin; a.OH = F; a.OW = F; a.Cout = 512;
     a.R = 3; a.S = 3; a.stride = 1; a.pad_t = 1; a.pad_l = 1; a.ps = t->ps_conv;
@@ -693,8 +935,9 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
             default: return fail(RPN_ERR_UNSUPPORTED, "rpn_head_trainer_step: %d anchors per position", K);
         }
         e = hipGetLastError();
-        if (e == hipSuccess) e = launch_wgrad(t->d_feat, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
+        if (e == hipSuccess) e = launch_wgrad(feat, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
         if (e == hipSuccess) e = launch_colsum(t->d_dS, P, 512, t->d_part, t->d_g + t->off_cb, s);
+        if (e == hipSuccess && t->bb_from >= 0) e = backbone_backward(t, B, s);
         if (e == hipSuccess) {
             ++t->t;
             hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)t->n)), dim3(256), 0, s, t->d_w, t->d_g, t->d_m, t->d_v, (long long)t->n,

@@ -3,9 +3,10 @@ the reference's Keras ``rpn_model`` stands (models/rpn_vgg16.py:21, predictor.py
 
 The inference surface the proposal path touches is mirrored: ``predict_on_batch``, ``__call__`` and ``load_weights``
 (Keras ``.h5`` checkpoints through ``utils/h5_weights.py`` -- no h5py needed -- or a flat ``.npz``).
-Training mirrors trainer.py:54-69 (``compile`` with Adam, ``train_on_batch`` / ``test_on_batch`` / ``fit``) for the RPN head
-only: ``rpn_conv``, ``rpn_reg`` and ``rpn_cls`` are trained on a FROZEN backbone (the reference's Keras base model is
-trainable; backward through VGG16 / MobileNetV2 is not implemented here).
+Training mirrors trainer.py:54-69 (``compile`` with Adam, ``train_on_batch`` / ``test_on_batch`` / ``fit``).  By default the RPN
+head (``rpn_conv``, ``rpn_reg``, ``rpn_cls``) is trained on a frozen backbone; ``compile(train_backbone_from="block1_conv1")``
+trains the whole VGG16 model as the reference does (its Keras base model is trainable), a later conv name the convs from there up.
+MobileNetV2 trains its head only (its backward needs depthwise convs and BatchNorm in training mode).
 """
 import ctypes
 
@@ -33,6 +34,9 @@ class FeatureExtractor(object):
 
 # the layers a training step updates (models/rpn_vgg16.py:18-20, models/rpn_mobilenet_v2.py:18-20)
 HEAD_LAYERS = ("rpn_conv", "rpn_cls", "rpn_reg")
+# the VGG16 convs in graph order (keras.applications.VGG16 up to block5_conv3): what train_backbone_from names
+VGG16_CONVS = ("block1_conv1", "block1_conv2", "block2_conv1", "block2_conv2", "block3_conv1", "block3_conv2", "block3_conv3",
+               "block4_conv1", "block4_conv2", "block4_conv3", "block5_conv1", "block5_conv2", "block5_conv3")
 
 
 class RPNModel(object):
@@ -61,8 +65,10 @@ class RPNModel(object):
         self.layers = self._enumerate_layers()
         self.tap_layer = "block5_conv3" if backbone == "vgg16" else "block_13_expand"
         self._head = {}                 # head weights last given to set_weights / load_weights: {name: (kernel, bias)}
-        self._t = L.vp(0)               # native head trainer (compile)
+        self._backbone = {}             # the same for the VGG16 convs (the handle keeps only packed / transformed copies)
+        self._t = L.vp(0)               # native trainer (compile)
         self._opt = None
+        self._train_from = None         # first trained VGG16 conv, None: the head only
         self._head_dirty = False        # the trainer's head differs from the handle's: copied before the next inference
 
     # ---- introspection ----------------------------------------------------------------
@@ -116,9 +122,9 @@ class RPNModel(object):
             else:
                 args += [None, None, None, None]
             L.check(lib.rpn_model_set_layer(self._h, name.encode(), *args), "rpn_model_set_layer(%s)" % name)
-            if name in HEAD_LAYERS:
-                self._head[name] = (kernel.copy(), bias.copy())
-                if self._t:
+            if name in HEAD_LAYERS or (self.backbone == "vgg16" and name in VGG16_CONVS):
+                (self._head if name in HEAD_LAYERS else self._backbone)[name] = (kernel.copy(), bias.copy())
+                if self._t and (name in HEAD_LAYERS or self._train_from is not None):
                     self._trainer_set(name)
             done.append(name)
         return done
@@ -258,30 +264,55 @@ class RPNModel(object):
         return out if batch is None else out[:batch]
 
     # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
-    def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS):
+    def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None):
         """``rpn_model.compile(optimizer=tf.optimizers.Adam(learning_rate), loss=[reg_loss, cls_loss])`` (trainer.py:54-56).
 
-        Trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone -- unlike the reference, whose Keras
-        base model is trainable.  Adam is TF 2.0's ApplyAdam (as recalled from its sources): alpha = lr sqrt(1 - beta_2^t) /
-        (1 - beta_1^t), m += (g - m)(1 - beta_1), v += (g^2 - v)(1 - beta_2), w -= alpha m / (sqrt(v) + epsilon), m = v = 0 at
-        compile, t = the number of applied steps.  The trainer starts from the head weights last given to ``set_weights`` /
-        ``load_weights`` (or from the trained ones when compiled again)."""
+        ``train_backbone_from=None`` (default) trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone,
+        the backbone running at the handle's precision.  A VGG16 conv name trains that conv and every conv above it (up to
+        ``block5_conv3``) with the head; ``"block1_conv1"`` trains the whole model, as the reference does (its Keras base model is
+        trainable).  Such a step runs the whole VGG16 forward in exact float32 from the trainer's own weights.  MobileNetV2 trains
+        its head only.  ``trainable`` names the head layers only and must be exactly the three of them.
+
+        Adam is TF 2.0's ApplyAdam (as recalled from its sources): alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t),
+        m += (g - m)(1 - beta_1), v += (g^2 - v)(1 - beta_2), w -= alpha m / (sqrt(v) + epsilon), m = v = 0 at compile, t = the
+        number of applied steps.  The trainer starts from the weights last given to ``set_weights`` / ``load_weights`` (or from
+        the trained ones when compiled again)."""
         if isinstance(trainable, str) or set(trainable) != set(HEAD_LAYERS):
-            raise ValueError("trainable=%r: only the RPN head is trained, on a frozen backbone -- trainable must be exactly %s "
-                             "(backward through the %s backbone is not implemented)" % (trainable, HEAD_LAYERS, self.backbone))
+            raise ValueError("trainable=%r: trainable names the RPN head, which trains on a frozen backbone -- it must be exactly %s; "
+                             "to train backbone convs too use train_backbone_from=<first trained conv>" % (trainable, HEAD_LAYERS))
+        if train_backbone_from is not None:
+            if self.backbone != "vgg16":
+                raise ValueError("train_backbone_from=%r: the %s backbone trains its head only (its backward needs depthwise "
+                                 "convs and BatchNorm in training mode)" % (train_backbone_from, self.backbone))
+            if train_backbone_from not in VGG16_CONVS:
+                raise ValueError("train_backbone_from=%r is not a VGG16 conv (one of %s)" % (train_backbone_from, VGG16_CONVS))
         self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
         if self._t:
-            self._head.update({k: (d["kernel"], d["bias"]) for k, d in self.get_weights().items()})
+            for k, d in self.get_weights().items():
+                (self._head if k in HEAD_LAYERS else self._backbone)[k] = (d["kernel"], d["bias"])
             L.lib().rpn_head_trainer_destroy(self._t)
             self._t = L.vp(0)
         t = L.vp(0)
-        L.check(L.lib().rpn_head_trainer_create(self._h, ctypes.byref(t)), "rpn_head_trainer_create")
+        if train_backbone_from is None:
+            L.check(L.lib().rpn_head_trainer_create(self._h, ctypes.byref(t)), "rpn_head_trainer_create")
+        else:
+            L.check(L.lib().rpn_model_trainer_create(self._h, train_backbone_from.encode(), ctypes.byref(t)),
+                    "rpn_model_trainer_create")
         self._t = t
+        self._train_from = train_backbone_from
         for name in self._head:
             self._trainer_set(name)
+        if train_backbone_from is not None:
+            for name in self._backbone:
+                self._trainer_set(name)
+
+    def trained_layers(self):
+        """The layers a training step updates: the head, plus the VGG16 convs from ``train_backbone_from`` up."""
+        bb = VGG16_CONVS[VGG16_CONVS.index(self._train_from):] if self._train_from is not None else ()
+        return tuple(bb) + HEAD_LAYERS
 
     def _trainer_set(self, name):
-        kernel, bias = self._head[name]
+        kernel, bias = self._head[name] if name in HEAD_LAYERS else self._backbone[name]
         L.check(L.lib().rpn_head_trainer_set_layer(self._t, name.encode(), kernel.ctypes.data_as(L.c_float_p),
                                                    bias.ctypes.data_as(L.c_float_p)), "rpn_head_trainer_set_layer(%s)" % name)
 
@@ -290,8 +321,9 @@ class RPNModel(object):
         if not self._t:
             raise RuntimeError("call compile() first")
         out = {}
+        trained = self.trained_layers()
         for layer in self.layers:
-            if layer["name"] in HEAD_LAYERS:
+            if layer["name"] in trained:
                 kernel = np.empty(layer["shape"], dtype=np.float32)
                 bias = np.empty((layer["shape"][3],), dtype=np.float32)
                 L.check(L.lib().rpn_head_trainer_get_gradient(self._t, layer["name"].encode(), kernel.ctypes.data_as(L.c_float_p),
@@ -301,12 +333,14 @@ class RPNModel(object):
         return out
 
     def get_weights(self):
-        """{layer: {"kernel": HWIO, "bias"}} of the three head layers (the trained values once a step has run): what
-        ``save_weights`` writes and ``set_weights`` / ``load_weights`` read back."""
+        """{layer: {"kernel": HWIO, "bias"}} of the trained layers -- the three head layers, plus the VGG16 convs from
+        ``train_backbone_from`` up when compiled so (the trained values once a step has run): what ``save_weights`` writes and
+        ``set_weights`` / ``load_weights`` read back."""
         out = {}
+        trained = self.trained_layers()
         for layer in self.layers:
             name = layer["name"]
-            if name not in HEAD_LAYERS:
+            if name not in trained:
                 continue
             if self._t:
                 kernel = np.empty(layer["shape"], dtype=np.float32)
@@ -317,13 +351,16 @@ class RPNModel(object):
                         "rpn_head_trainer_get_layer(%s)" % name)
             elif name in self._head:
                 kernel, bias = (a.copy() for a in self._head[name])
+            elif name in self._backbone:
+                kernel, bias = (a.copy() for a in self._backbone[name])
             else:
                 continue
             out[name] = {"kernel": kernel, "bias": bias}
         return out
 
     def _sync_head(self):
-        """After training: the trained head into the inference handle (once, before the next forward)."""
+        """After training: every trained layer into the inference handle (once, before the next forward), which repacks it at
+        its own precision."""
         if not self._head_dirty:
             return
         lib = L.lib()
