@@ -254,8 +254,8 @@ int rpn_model_get_profile(rpn_model *m, float *ms, int n, int *n_forwards);
 
 /* ------------------------------------------------------------------------------------
  * Training of the RPN head on a FROZEN backbone                   trainer.py:54-69
- *   The reference fine-tunes the whole Keras model (its base model is trainable); here only rpn_conv, rpn_reg and
- *   rpn_cls are trained -- there is no backward pass through VGG16 / MobileNetV2.  The loss and Adam forms are TF 2.0.0's,
+ *   The reference fine-tunes the whole Keras model (its base model is trainable); rpn_head_trainer_create trains rpn_conv,
+ *   rpn_reg and rpn_cls only (rpn_model_trainer_create below adds backbone layers).  The loss and Adam forms are TF 2.0.0's,
  *   restated from its sources as recalled (tf_rpn_amd/csrc/train_kernels.hip).  Every reduction has a fixed order and
  *   there are no floating-point atomics: a call is bit-identical from run to run.
  *
@@ -288,7 +288,8 @@ int rpn_conv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, 
  *   its activation arena is overwritten by a step.  The head runs in exact float32 from the master weights whatever the
  *   handle's precision; the handle's own head weights are NOT changed by a step (copy them with get_layer + set_layer).
  *   set_layer / get_layer: HOST arrays, kernel HWIO + bias, names "rpn_conv" | "rpn_reg" | "rpn_cls" (any other name is
- *   RPN_ERR_INVALID: the backbone is frozen); get_layer synchronises `stream`.
+ *   RPN_ERR_INVALID: the backbone is frozen); get_layer synchronises `stream`.  bias is NULL for the bias-less MobileNetV2 convs of
+ *   a trainer made by rpn_model_trainer_create, and only for them.
  *   step: d_imgs (B,img,img,3), d_bbox_deltas (B,A,4), d_bbox_labels (B,F,F,K); d_losses <- [reg + cls, reg, cls] computed
  *   with the weights before the update (Keras train_on_batch order).  update = 0: losses only (test_on_batch, t unchanged);
  *   update = 1: backward + one Adam step (t += 1; alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t) on the device, no host
@@ -310,8 +311,56 @@ int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, in
  * set_layer takes every VGG16 conv as well (all 13 must be set before a step): convs below train_from are frozen constants, outside
  * Adam's buffer (get_layer returns them, get_gradient fails).  A step runs the whole VGG16 forward in exact float32 from the
  * trainer's own weights (not the handle's ops), then the backward down to train_from; Adam updates head and trained convs in one
- * launch.  Device memory (at the first step) is sized by max_batch and the trained span.  MobileNetV2 handles: RPN_ERR_INVALID. */
+ * launch.  Device memory (at the first step) is sized by max_batch and the trained span.
+ * On a MobileNetV2 handle train_from is "block_7_expand" .. "block_12_expand" (the first layer of an inverted-residual block) or
+ * "block_13_expand": that layer and every layer above it -- the stride-1 blocks at the feature map's own resolution -- train with the
+ * head; any other name (a VGG16 conv, a layer inside a block, a layer below block_7_expand) is RPN_ERR_INVALID.  The layers below
+ * train_from stay frozen and run on the handle's ops at the handle's precision, BatchNorm folded (inference mode).  The trained
+ * layers run in exact float32 from the trainer's unfolded parameters: on an update step BatchNorm normalises with the batch mean and
+ * the biased batch variance over (B, F, F) (eps 1e-3) and updates the moving statistics in the same step, moving = moving * 0.999 +
+ * batch * 0.001, the variance with Bessel's correction N / (N - 1) (TF 2.0's fused BatchNorm as recalled); on an evaluation step
+ * (update = 0) it normalises with the moving statistics and changes nothing.  Per trained conv Adam updates the kernel, gamma and
+ * beta (same flat buffer, one launch); the moving statistics are state.  These convs have no bias: set_layer / get_layer /
+ * get_gradient take bias = NULL for them, and the three calls below carry the BatchNorm of a trained conv, named by the conv or by
+ * its BatchNorm layer ("<conv>_BN"): HOST arrays of Cout floats; every trained conv and BatchNorm must be set before a step. */
 int rpn_model_trainer_create(rpn_model *m, const char *train_from, rpn_head_trainer **out);
+int rpn_head_trainer_set_bn(rpn_head_trainer *t, const char *name, const float *gamma, const float *beta, const float *mean,
+                            const float *var);
+int rpn_head_trainer_get_bn(rpn_head_trainer *t, const char *name, float *gamma, float *beta, float *mean, float *var, void *stream);
+/* the gradients of gamma and beta at the last update step */
+int rpn_head_trainer_get_bn_gradient(rpn_head_trainer *t, const char *name, float *dgamma, float *dbeta, void *stream);
+
+/* backward of MobileNetV2's stride-1 blocks, single-layer entries (float32; float64 partial sums inside the BatchNorm reductions; no
+ * floating-point atomics, every reduction a fixed tree chosen from the shape alone: bit-identical from run to run).  P = B H W pixels
+ * of an NHWC tensor; channel counts are multiples of 4, and every device pointer (the workspace included) is 16-byte aligned: the
+ * kernels move four channels at a time (RPN_ERR_INVALID otherwise).
+ * rpn_batchnorm_train_forward: d_x (P,C) -> d_mean, d_var (C): the batch mean and biased variance; d_y (P,C) = gamma (x - mean) /
+ *   sqrt(var + eps) + beta, then min(max(., 0), 6) when relu6 = 1; d_moving_mean / d_moving_var (both or neither) are updated as
+ *   moving * momentum + batch * (1 - momentum), the variance with Bessel's correction.  d_ws: rpn_batchnorm_workspace_bytes(P, C).
+ * rpn_batchnorm_train_backward: with dy' = d_dy [0 < y < 6] when relu6 = 1 (TF's Relu6Grad; y recomputed from d_x), else d_dy:
+ *   d_dbeta = sum dy', d_dgamma = sum dy' xhat, d_dx = gamma / sqrt(var + eps) (dy' - dbeta / P - xhat dgamma / P).  d_mean / d_var:
+ *   what the forward returned.  d_dx may be d_dy.  Same workspace.
+ * rpn_conv1x1_wgrad: d_x (P,Cin), d_dy (P,Cout) -> d_dw (Cin,Cout) = x^T dy on the float32 MFMA, the pixels in a power-of-two number of
+ *   fixed ranges summed in a fixed tree.  d_ws: rpn_conv1x1_wgrad_workspace_bytes(...) bytes (0: none needed, d_ws may be NULL).
+ * rpn_conv1x1_dgrad: d_dx (P,Cin) = d_dy (P,Cout) d_w^T (d_w (Cin,Cout)) on the float32 MFMA, + d_add (P,Cin) when non-NULL (the
+ *   gradient that reaches a residual block's input beside its expand conv).
+ * rpn_dwconv3x3_dgrad / _wgrad: depthwise 3x3 stride-1 'same', d_w (3,3,C): dx[b][y][x][c] = sum_{r,s} dy[b][y+1-r][x+1-s][c]
+ *   w[r][s][c]; dw[r][s][c] = sum_{b,y,x} x[b][y+r-1][x+s-1][c] dy[b][y][x][c].  d_ws: rpn_dwconv3x3_wgrad_workspace_bytes(...). */
+size_t rpn_batchnorm_workspace_bytes(long long P, int C);
+int rpn_batchnorm_train_forward(const float *d_x, long long P, int C, const float *d_gamma, const float *d_beta, int relu6, float eps,
+                                float momentum, float *d_y, float *d_mean, float *d_var, float *d_moving_mean, float *d_moving_var,
+                                void *d_ws, size_t ws_bytes, void *stream);
+int rpn_batchnorm_train_backward(const float *d_x, const float *d_dy, long long P, int C, const float *d_gamma, const float *d_beta,
+                                 const float *d_mean, const float *d_var, int relu6, float eps, float *d_dx, float *d_dgamma,
+                                 float *d_dbeta, void *d_ws, size_t ws_bytes, void *stream);
+size_t rpn_conv1x1_wgrad_workspace_bytes(long long P, int Cin, int Cout);
+int rpn_conv1x1_wgrad(const float *d_x, const float *d_dy, long long P, int Cin, int Cout, float *d_dw, void *d_ws, size_t ws_bytes,
+                      void *stream);
+int rpn_conv1x1_dgrad(const float *d_dy, const float *d_w, const float *d_add, long long P, int Cin, int Cout, float *d_dx, void *stream);
+int rpn_dwconv3x3_dgrad(const float *d_dy, const float *d_w, int B, int H, int W, int C, float *d_dx, void *stream);
+size_t rpn_dwconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C);
+int rpn_dwconv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws, size_t ws_bytes,
+                        void *stream);
 
 /* backward of the VGG16 backbone, single-layer entries (float32; no floating-point atomics: bit-identical from run to run)
  * rpn_conv3x3_dgrad: input gradient of a 3x3 stride-1 'same' conv, d_dx (B,H,W,Cin) = conv_transpose(d_dy (B,H,W,Cout), d_w HWIO),

@@ -2,6 +2,7 @@
 
     python scripts/train_step_bench.py [--batch 8] [--steps 20] [--warmup 3]
     python scripts/train_step_bench.py --train-backbone-from block1_conv1 [--batch 8] [--steps 20] [--warmup 3]
+    python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone-from block_7_expand [--batch 8] ...
 
 Times on the device with HIP events around (a) a whole training step (backbone at the handle's precision + float32 head forward,
 losses, backward, Adam), (b) an evaluation step (no backward), (c) the 3x3 weight-gradient entry rpn_conv3x3_wgrad on the
@@ -163,15 +164,75 @@ def bench_backbone(train_from, precision, B, steps, warmup):
             "layers": layers}
 
 
+def bench_mobilenet_span(train_from, precision, B, steps, warmup):
+    """MobileNetV2 from `train_from` (block_7_expand .. block_13_expand): ms per training / evaluation step, and each new kernel family's
+    single-layer entry on the block_12 shape (96 -> 576 -> 96 at F x F) with its fraction of its own floor: bytes / 8 TB/s for the
+    BatchNorm and depthwise kernels, the float32-MFMA peak for the two GEMMs."""
+    hp = train_utils.get_hyper_params("mobilenet_v2")
+    model, _ = rpn_mobilenet_v2.get_model(hp, precision=precision, max_batch=B)
+    imgs, deltas, lab = step_inputs(model, hp, B)
+    model.compile(learning_rate=1e-5, train_backbone_from=train_from)
+    ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
+    lib = L.lib()
+    F = model.feature_map_shape
+    P, C, Cs = B * F * F, 576, 96
+    x, dy = torch.randn((P, C), device="cuda"), torch.randn((P, C), device="cuda")
+    y, dx = torch.empty_like(x), torch.empty_like(x)
+    xs, dxs = torch.randn((P, Cs), device="cuda"), torch.empty((P, Cs), device="cuda")
+    g, b = torch.rand(C, device="cuda") + 0.5, torch.rand(C, device="cuda")
+    mean, var, dg, db = (torch.empty(C, device="cuda") for _ in range(4))
+    w, dw = torch.randn((Cs, C), device="cuda"), torch.empty((Cs, C), device="cuda")
+    wd, dwd = torch.randn((3, 3, C), device="cuda"), torch.empty((3, 3, C), device="cuda")
+    nb = lib.rpn_batchnorm_workspace_bytes(P, C)
+    nw = lib.rpn_conv1x1_wgrad_workspace_bytes(P, Cs, C)
+    nd = lib.rpn_dwconv3x3_wgrad_workspace_bytes(B, F, F, C)
+    ws = torch.empty(max(nb, nw, nd, 4), dtype=torch.uint8, device="cuda")
+    s = L.stream_ptr
+    calls = {
+        "batchnorm_train_forward": (lambda: lib.rpn_batchnorm_train_forward(L.ptr(x), P, C, L.ptr(g), L.ptr(b), 1, 1e-3, 0.999, L.ptr(y),
+                                                                            L.ptr(mean), L.ptr(var), None, None, L.ptr(ws), nb, s()),
+                                    ("bytes", 3.0 * P * C * 4)),          # x read twice (statistics, apply), y written
+        "batchnorm_train_backward": (lambda: lib.rpn_batchnorm_train_backward(L.ptr(x), L.ptr(dy), P, C, L.ptr(g), L.ptr(b), L.ptr(mean),
+                                                                              L.ptr(var), 1, 1e-3, L.ptr(dx), L.ptr(dg), L.ptr(db),
+                                                                              L.ptr(ws), nb, s()),
+                                     ("bytes", 5.0 * P * C * 4)),         # x, dy read twice, dx written
+        "conv1x1_wgrad": (lambda: lib.rpn_conv1x1_wgrad(L.ptr(xs), L.ptr(dy), P, Cs, C, L.ptr(dw), L.ptr(ws), nw, s()),
+                          ("flop", 2.0 * P * Cs * C)),
+        "conv1x1_dgrad": (lambda: lib.rpn_conv1x1_dgrad(L.ptr(dy), L.ptr(w), L.ptr(xs), P, Cs, C, L.ptr(dxs), s()), ("flop", 2.0 * P * Cs * C)),
+        "dwconv3x3_dgrad": (lambda: lib.rpn_dwconv3x3_dgrad(L.ptr(dy), L.ptr(wd), B, F, F, C, L.ptr(dx), s()), ("bytes", 2.0 * P * C * 4)),
+        "dwconv3x3_wgrad": (lambda: lib.rpn_dwconv3x3_wgrad(L.ptr(x), L.ptr(dy), B, F, F, C, L.ptr(dwd), L.ptr(ws), nd, s()),
+                            ("bytes", 2.0 * P * C * 4)),
+    }
+    kernels = {}
+    for name, (fn, (kind, amount)) in calls.items():
+        def run(fn=fn, name=name):
+            L.check(fn(), name)
+        ms = timed(run, steps, warmup)
+        floor_ms = amount / (8e12 if kind == "bytes" else PEAK_F32_MFMA) * 1e3
+        kernels[name] = {"ms": round(ms, 4), "floor_ms": round(floor_ms, 5), "frac_of_floor": round(floor_ms / ms, 3)}
+    return {"backbone": "mobilenet_v2", "train_backbone_from": train_from, "precision": precision, "batch": B,
+            "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "block_12_shape": [P, Cs, C], "kernels": kernels}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", default="f16x3")
-    ap.add_argument("--train-backbone-from", default=None, help="a VGG16 conv: time the trainer that trains it and the convs above")
+    ap.add_argument("--train-backbone-from", default=None,
+                    help="a VGG16 conv, or with --backbone mobilenet_v2 block_7_expand .. block_13_expand: time the trainer that trains it "
+                         "and the layers above")
+    ap.add_argument("--backbone", default=None, choices=("vgg16", "mobilenet_v2"),
+                    help="with --train-backbone-from: the backbone (default vgg16); without: time that backbone's head-only step alone")
     args = ap.parse_args()
     L.require_gpu()
+    if args.train_backbone_from and args.backbone == "mobilenet_v2":
+        print(json.dumps(bench_mobilenet_span(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        return
+    if args.backbone and not args.train_backbone_from:
+        print(json.dumps(bench(args.backbone, args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        return
     if args.train_backbone_from:
         print(json.dumps(bench_backbone(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup)), flush=True)
         return

@@ -82,6 +82,20 @@ _SIGNATURES = {
     "rpn_head_trainer_steps": (ctypes.c_longlong, [vp]),
     "rpn_head_trainer_outputs": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, vp]),
     "rpn_model_trainer_create": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(vp)]),
+    "rpn_head_trainer_set_bn": (ctypes.c_int, [vp, ctypes.c_char_p] + [c_float_p] * 4),
+    "rpn_head_trainer_get_bn": (ctypes.c_int, [vp, ctypes.c_char_p] + [c_float_p] * 4 + [vp]),
+    "rpn_head_trainer_get_bn_gradient": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p, vp]),
+    "rpn_batchnorm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
+    "rpn_batchnorm_train_forward": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float,
+                                                   ctypes.c_float, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_batchnorm_train_backward": (ctypes.c_int, [vp, vp, ctypes.c_longlong, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, ctypes.c_float,
+                                                    vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_conv1x1_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
+    "rpn_conv1x1_wgrad": (ctypes.c_int, [vp, vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_conv1x1_dgrad": (ctypes.c_int, [vp, vp, vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "rpn_dwconv3x3_dgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
+    "rpn_dwconv3x3_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "rpn_dwconv3x3_wgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, ctypes.c_size_t, vp]),
     "rpn_conv3x3_dgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
     "rpn_conv3x3_dgrad_tile_n": (ctypes.c_int, [ctypes.c_int] * 4),
     "rpn_conv3x3_dgrad": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, ctypes.c_size_t, vp]),

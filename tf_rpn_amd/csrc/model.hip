@@ -1105,20 +1105,17 @@ void model_train_backbone(const rpn_model *m, int *backbone, int *img_size)
 // The backbone of a training step (the head is trained on frozen features): the ops up to the one that writes feat_tensor, at the
 // handle's own precision, then the features as NHWC float32 into d_feat (B, F, F, Cin) -- converted from the split form when the
 // tensor is kept that way, as rpn_model_get_activation does.
-int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s)
+static int features_of(rpn_model *m, int tensor, const float *d_imgs, int B, float *d_feat, hipStream_t s)
 {
-    for (const Param &p : m->params)
-        if (p.name != "rpn_conv" && p.name != "rpn_reg" && p.name != "rpn_cls")
-            RPN_REQUIRE(p.loaded, "rpn_head_trainer_step: weights of layer '%s' were never set", p.name.c_str());
     const int st = ensure_device(m);
     if (st != RPN_OK) return st;
     size_t n = 0;
     for (size_t i = 0; i < m->ops.size(); ++i)
-        if (m->ops[i].out == m->feat_tensor) n = i + 1;
+        if (m->ops[i].out == tensor) n = i + 1;
     const int e0 = run_ops(m, d_imgs, B, nullptr, nullptr, s, n);
     if (e0 != RPN_OK) return e0;
-    const Tensor &t = m->tensors[m->feat_tensor];
-    const float *src = tensor_ptr(m, m->feat_tensor, d_imgs);
+    const Tensor &t = m->tensors[tensor];
+    const float *src = tensor_ptr(m, tensor, d_imgs);
     if (t.split_fmt) {
         const hipError_t e = launch_split_to_f32(src, (long long)B * t.H * t.W, t.C, m->f16, d_feat, s);
         if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: features: %s", hipGetErrorString(e));
@@ -1126,6 +1123,51 @@ int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipS
     }
     RPN_HIP_CHECK(hipMemcpyAsync(d_feat, src, (size_t)B * t.H * t.W * t.C * sizeof(float), hipMemcpyDeviceToDevice, s));
     return RPN_OK;
+}
+
+int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s)
+{
+    for (const Param &p : m->params)
+        if (p.name != "rpn_conv" && p.name != "rpn_reg" && p.name != "rpn_cls")
+            RPN_REQUIRE(p.loaded, "rpn_head_trainer_step: weights of layer '%s' were never set", p.name.c_str());
+    return features_of(m, m->feat_tensor, d_imgs, B, d_feat, s);
+}
+
+static int tensor_by_name(const rpn_model *m, const char *name)
+{
+    for (size_t i = 0; i < m->tensors.size(); ++i)
+        if (m->tensors[i].name == name) return (int)i;
+    return -1;
+}
+
+bool model_has_layer(const rpn_model *m, const char *name)
+{
+    for (const Param &p : m->params)
+        if (p.name == name) return true;
+    return false;
+}
+
+int model_tensor_shape(const rpn_model *m, const char *name, int *H, int *W, int *C)
+{
+    const int ti = tensor_by_name(m, name);
+    if (ti < 0) return fail(RPN_ERR_INVALID, "the model has no tensor named '%s'", name);
+    *H = m->tensors[ti].H; *W = m->tensors[ti].W; *C = m->tensors[ti].C;
+    return RPN_OK;
+}
+
+// The frozen prefix of a step that trains the layers above tensor `name`: the ops up to the one that writes it, then the tensor
+// as NHWC float32 into d_out.  Only the layers of those ops need weights in the handle.
+int model_features_at(rpn_model *m, const char *name, const float *d_imgs, int B, float *d_out, hipStream_t s)
+{
+    const int ti = tensor_by_name(m, name);
+    if (ti < 0) return fail(RPN_ERR_INVALID, "the model has no tensor named '%s'", name);
+    size_t n = 0;
+    for (size_t i = 0; i < m->ops.size(); ++i)
+        if (m->ops[i].out == ti) n = i + 1;
+    for (const Param &p : m->params)
+        if (p.op >= 0 && (size_t)p.op < n)
+            RPN_REQUIRE(p.loaded, "rpn_head_trainer_step: weights of layer '%s' were never set", p.name.c_str());
+    return features_of(m, ti, d_imgs, B, d_out, s);
 }
 
 }  // namespace rpn

@@ -62,4 +62,8 @@ void model_train_dims(const rpn_model *m, int *cin, int *F, int *K, int *max_bat
 void model_train_backbone(const rpn_model *m, int *backbone, int *img_size);
 // the ops up to the backbone features on stream s, then the features as NHWC float32 (B, F, F, cin) into d_feat
 int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s);
+// the same up to the tensor `name` (an op's output, e.g. "block_6_project"), and that tensor's shape per image
+int model_features_at(rpn_model *m, const char *name, const float *d_imgs, int B, float *d_out, hipStream_t s);
+int model_tensor_shape(const rpn_model *m, const char *name, int *H, int *W, int *C);
+bool model_has_layer(const rpn_model *m, const char *name);
 }  // namespace rpn

@@ -4,7 +4,10 @@
 // rpn_head_trainer_create trains the head on a frozen backbone; rpn_model_trainer_create also trains the VGG16 convs from a given one
 // up (the reference's Keras base model is trainable): the step then runs the whole VGG16 forward in exact float32 from the trainer's
 // weights (backbone_forward) and, after the head's backward below, the backbone's (backbone_backward; kernels in
-// train_backbone_kernels.hip).  MobileNetV2 trains its head only.  The head-only step is
+// train_backbone_kernels.hip).  On a MobileNetV2 handle it trains the stride-16 blocks from a given expand conv up (block_7 ..
+// block_12, block_13_expand) with BatchNorm in training mode: the layers below run frozen on the handle's ops (BatchNorm folded),
+// the trained ones in exact float32 from the trainer's unfolded parameters (mn_forward / mn_backward; kernels and the recalled
+// BatchNorm form in train_mnv2_kernels.hip).  The head-only step is
 //   backbone (the handle's own ops and precision) -> X (B,F,F,Cin) float32
 //   rpn_conv (exact float32, ReLU) -> S (P,512), P = B F F;  fused 1x1 head -> reg (P,4K) linear | cls (P,K) sigmoid
 //   losses + their gradients (one pass, fixed-order reductions)
@@ -21,6 +24,9 @@
 //     summed over the 4 coordinates, masked by "any y_true coordinate != 0", summed, divided by max(1, n_pos).
 //   Adam (training_ops ApplyAdam): alpha = lr sqrt(1 - b2^t) / (1 - b1^t); m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2);
 //     w -= alpha m / (sqrt(v) + eps), t = the number of applied steps.
+//   BatchNorm in training mode (the fused BatchNorm kernels; MobileNetV2 span, train_mnv2_kernels.hip): normalise with the batch mean
+//     and the biased batch variance over (B, H, W), eps 1e-3; moving = moving * momentum + batch * (1 - momentum) with momentum 0.999,
+//     the variance with Bessel's correction N / (N - 1); Relu6Grad keeps dy where 0 < y < 6, strict on both sides.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -30,6 +36,7 @@
 #include "conv_kernels.h"
 #include "rpn_common.h"
 #include "train_backbone.h"
+#include "train_mnv2.h"
 
 namespace rpn {
 
@@ -511,6 +518,19 @@ struct rpn_head_trainer {
     PackedShape ps_bb[13]{};
     float *d_frozen = nullptr, *d_pack = nullptr, *d_wt = nullptr, *d_wpart = nullptr, *d_img4 = nullptr;
     float *d_act[13] = {}, *d_pool[13] = {}, *d_ping[2] = {}, *d_grad[2] = {};
+    // ---- MobileNetV2's stride-16 span (rpn_model_trainer_create on a MobileNetV2 handle; mn_*) ----
+    // mn_from: the first trained layer (index into mn_table(), an expand conv), -1: none.  A trained layer's kernel, gamma and beta
+    // follow the head in the flat buffers (off_mk / off_mg / off_mb); its moving mean | variance are state outside Adam's buffer
+    // (host_bn / d_bn at off_ms); d_bstat holds the statistics a step normalised with (mean | var | rstd at off_bs).
+    int mn_from = -1;
+    std::string mn_x0;                           // the handle's tensor below the span: the frozen prefix ends there
+    size_t off_mk[19] = {}, off_mg[19] = {}, off_mb[19] = {}, off_ms[19] = {}, off_bs[19] = {};
+    bool mn_loaded[19] = {}, mn_bn_loaded[19] = {};
+    std::vector<float> host_bn;
+    PackedShape ps_mn[19]{};
+    float *d_bn = nullptr, *d_bstat = nullptr, *d_x0 = nullptr, *d_mpack = nullptr, *d_mwpart = nullptr;
+    double *d_mpart = nullptr;
+    float *d_mz[19] = {}, *d_my[19] = {}, *d_mgr[2] = {}, *d_mt[3] = {};
 };
 
 namespace {
@@ -591,9 +611,92 @@ int backbone_device(rpn_head_trainer *t)
     return RPN_OK;
 }
 
+// ---- MobileNetV2: the inverted-residual blocks at the feature map's own resolution ------------------------------------------------
+// kind 0: 1x1 expand + BatchNorm + ReLU6, 1: depthwise 3x3 stride 1 'same' + BatchNorm + ReLU6, 2: 1x1 project + BatchNorm (linear)
+// (+ the block's input when res).  No conv has a bias.  Keras names; the BatchNorm layer of conv X is "X_BN".
+constexpr int kMnLayers = 19;
+constexpr float kMnBnEps = 1e-3f, kMnBnMomentum = 0.999f;      // keras.applications.MobileNetV2
+struct MnConv {
+    std::string name;
+    int kind, cin, cout;
+    bool res;
+};
+const std::vector<MnConv> &mn_table()
+{
+    static const std::vector<MnConv> tab = [] {
+        std::vector<MnConv> v;
+        const int cin[6] = {64, 64, 64, 64, 96, 96}, cout[6] = {64, 64, 64, 96, 96, 96};
+        for (int b = 0; b < 6; ++b) {
+            const std::string pre = "block_" + std::to_string(b + 7) + "_";
+            v.push_back({pre + "expand", 0, cin[b], 6 * cin[b], false});
+            v.push_back({pre + "depthwise", 1, 6 * cin[b], 6 * cin[b], false});
+            v.push_back({pre + "project", 2, 6 * cin[b], cout[b], cin[b] == cout[b]});
+        }
+        v.push_back({"block_13_expand", 0, 96, 576, false});
+        return v;
+    }();
+    return tab;
+}
+
+// index of conv `name`, or of the conv whose BatchNorm layer is `name` (with_bn)
+int mn_index(const char *name, bool with_bn = false)
+{
+    const std::vector<MnConv> &tab = mn_table();
+    for (int i = 0; i < kMnLayers; ++i)
+        if (tab[i].name == name || (with_bn && tab[i].name + "_BN" == name)) return i;
+    return -1;
+}
+
+size_t mn_kernel_floats(int i)
+{
+    const MnConv &l = mn_table()[i];
+    return l.kind == 1 ? (size_t)9 * l.cout : (size_t)l.cin * l.cout;
+}
+
+// the span's buffers, sized by max_batch and the trained layers: per trained conv its output z (kept for the BatchNorm backward)
+// and the normalised, activated tensor y (the next layer's input; the last one is d_feat)
+int mn_device(rpn_head_trainer *t)
+{
+    const std::vector<MnConv> &tab = mn_table();
+    const size_t P = (size_t)t->max_batch * t->F * t->F;
+    size_t pack = 0, wpart = 0, bstat = 0;
+    for (int i = t->mn_from; i < kMnLayers; ++i) {
+        const MnConv &l = tab[i];
+        if (l.kind != 1) pack = std::max(pack, t->ps_mn[i].floats());
+        wpart = std::max(wpart, l.kind == 1 ? dwconv3x3_wgrad_ws_floats((long long)P, l.cout) : conv1x1_wgrad_ws_floats((long long)P, l.cin, l.cout));
+        bstat = t->off_bs[i] + (size_t)3 * l.cout;
+        RPN_HIP_CHECK(hipMalloc(&t->d_mz[i], P * l.cout * sizeof(float)));
+        if (i < kMnLayers - 1) RPN_HIP_CHECK(hipMalloc(&t->d_my[i], P * l.cout * sizeof(float)));
+    }
+    RPN_HIP_CHECK(hipMalloc(&t->d_x0, P * tab[t->mn_from].cin * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mpack, std::max<size_t>(1, pack) * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mwpart, std::max<size_t>(1, wpart) * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mpart, bn_part_doubles((long long)P, 576) * sizeof(double)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_bstat, bstat * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_bn, t->host_bn.size() * sizeof(float)));
+    RPN_HIP_CHECK(hipMemcpy(t->d_bn, t->host_bn.data(), t->host_bn.size() * sizeof(float), hipMemcpyHostToDevice));
+    RPN_HIP_CHECK(hipMalloc(&t->d_wt, (size_t)9 * 512 * 576 * sizeof(float)));
+    for (int u = 0; u < 2; ++u) RPN_HIP_CHECK(hipMalloc(&t->d_mgr[u], P * 96 * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mt[0], P * 96 * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mt[1], P * 576 * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mt[2], P * 576 * sizeof(float)));
+    return RPN_OK;
+}
+
 // every device buffer of the trainer freed and its pointer reset (destroy, or a failed first-step allocation)
 void trainer_free(rpn_head_trainer *t)
 {
+    float *mn[] = {t->d_bn, t->d_bstat, t->d_x0, t->d_mpack, t->d_mwpart, t->d_mgr[0], t->d_mgr[1], t->d_mt[0], t->d_mt[1], t->d_mt[2]};
+    for (float *p : mn)
+        if (p) (void)hipFree(p);
+    if (t->d_mpart) (void)hipFree(t->d_mpart);
+    for (int i = 0; i < 19; ++i) {
+        if (t->d_mz[i]) (void)hipFree(t->d_mz[i]);
+        if (t->d_my[i] && i < 18) (void)hipFree(t->d_my[i]);           // (the last one is d_feat)
+        t->d_mz[i] = t->d_my[i] = nullptr;
+    }
+    t->d_bn = t->d_bstat = t->d_x0 = t->d_mpack = t->d_mwpart = t->d_mgr[0] = t->d_mgr[1] = t->d_mt[0] = t->d_mt[1] = t->d_mt[2] = nullptr;
+    t->d_mpart = nullptr;
     float *bufs[] = {t->d_w, t->d_g, t->d_m, t->d_v, t->d_pconv, t->d_phead, t->d_feat, t->d_S, t->d_reg, t->d_cls, t->d_graw, t->d_dz,
                      t->d_dS, t->d_part};
     for (float *p : bufs)
@@ -620,6 +723,10 @@ int trainer_alloc(rpn_head_trainer *t)
         const int st = backbone_device(t);
         if (st != RPN_OK) return st;
     }
+    if (t->mn_from >= 0) {
+        const int st = mn_device(t);
+        if (st != RPN_OK) return st;
+    }
     const size_t P = (size_t)t->max_batch * t->F * t->F;
     float **bufs[] = {&t->d_w, &t->d_g, &t->d_m, &t->d_v, &t->d_pconv, &t->d_phead, &t->d_feat, &t->d_S, &t->d_reg, &t->d_cls,
                       &t->d_graw, &t->d_dz, &t->d_dS, &t->d_part};
@@ -628,6 +735,7 @@ int trainer_alloc(rpn_head_trainer *t)
     for (size_t i = 0; i < sizeof(floats) / sizeof(floats[0]); ++i) RPN_HIP_CHECK(hipMalloc(bufs[i], floats[i] * sizeof(float)));
     RPN_HIP_CHECK(hipMalloc(&t->d_lws, losses_ws_bytes((long long)P * t->K)));
     RPN_HIP_CHECK(hipMemcpy(t->d_w, t->host_w.data(), t->n * sizeof(float), hipMemcpyHostToDevice));
+    RPN_HIP_CHECK(hipMemset(t->d_g, 0, t->n * sizeof(float)));       // no kernel writes the padding in front of an aligned slice
     RPN_HIP_CHECK(hipMemset(t->d_m, 0, t->n * sizeof(float)));
     RPN_HIP_CHECK(hipMemset(t->d_v, 0, t->n * sizeof(float)));
     return RPN_OK;
@@ -712,6 +820,100 @@ hipError_t backbone_backward(rpn_head_trainer *t, int B, hipStream_t s)
     return e;
 }
 
+// The span's forward in exact float32 from the trainer's unfolded parameters, on top of the frozen prefix (the handle's ops up to
+// mn_x0).  train: BatchNorm normalises with the batch statistics and updates the moving ones; else with the moving statistics
+// (inference mode, nothing updated).  Every conv output z and every layer output y is kept.  -> the block_13_expand output in d_feat.
+int mn_forward(rpn_head_trainer *t, const float *d_imgs, int B, bool train, hipStream_t s)
+{
+    const std::vector<MnConv> &tab = mn_table();
+    const int F = t->F;
+    const long long P = (long long)B * F * F;
+    const int e0 = model_features_at(t->m, t->mn_x0.c_str(), d_imgs, B, t->d_x0, s);
+    if (e0 != RPN_OK) return e0;
+    t->d_my[kMnLayers - 1] = t->d_feat;
+    for (int i = t->mn_from; i < kMnLayers; ++i) {
+        const MnConv &l = tab[i];
+        const float *in = i == t->mn_from ? t->d_x0 : t->d_my[i - 1];
+        const float *w = t->d_w + t->off_mk[i];
+        hipError_t e;
+        if (l.kind == 1) {
+            e = launch_dwconv3x3(in, B, F, F, l.cout, w, nullptr, 1, 1, 1, F, F, ACT_LINEAR, t->d_mz[i], s);
+        } else {
+            pack_weights_device(t->ps_mn[i], w, t->d_mpack, s);
+            ConvArgs a{};
+            a.x = in; a.w = t->d_mpack; a.bias = nullptr; a.residual = nullptr;
+            a.out = t->d_mz[i]; a.out2 = nullptr;
+            a.B = B; a.H = F; a.W = F; a.Cin = l.cin; a.OH = F; a.OW = F; a.Cout = l.cout;
+            a.R = 1; a.S = 1; a.stride = 1; a.pad_t = 0; a.pad_l = 0; a.ps = t->ps_mn[i];
+            a.act = ACT_LINEAR; a.act2 = ACT_LINEAR; a.split = l.cout; a.ld1 = l.cout; a.ld2 = 0;
+            e = launch_conv_f32(a, s);
+        }
+        float *mean = t->d_bstat + t->off_bs[i], *var = mean + l.cout, *rstd = var + l.cout;
+        float *mmean = t->d_bn + t->off_ms[i], *mvar = mmean + l.cout;
+        if (e == hipSuccess) {
+            if (train) {
+                e = launch_bn_train_stats(t->d_mz[i], P, l.cout, kMnBnEps, kMnBnMomentum, t->d_mpart, mean, var, rstd, mmean, mvar, s);
+            } else {
+                e = hipMemcpyAsync(mean, mmean, (size_t)2 * l.cout * sizeof(float), hipMemcpyDeviceToDevice, s);
+                if (e == hipSuccess) e = launch_bn_rstd(mvar, l.cout, kMnBnEps, rstd, s);
+            }
+        }
+        const float *res = (l.kind == 2 && l.res) ? (i - 2 == t->mn_from ? t->d_x0 : t->d_my[i - 3]) : nullptr;
+        if (e == hipSuccess)
+            e = launch_bn_apply(t->d_mz[i], P, l.cout, mean, rstd, t->d_w + t->off_mg[i], t->d_w + t->off_mb[i], l.kind != 2, res, t->d_my[i], s);
+        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: %s: %s", l.name.c_str(), hipGetErrorString(e));
+    }
+    return RPN_OK;
+}
+
+// From dS (rpn_conv's pre-activation gradient) down to the first trained layer.  g: the gradient of the current layer's output.  A
+// residual block's output gradient stays in d_mgr[a] until the block's expand dgrad adds it to what that conv sends to the block's
+// input (the dgrad's epilogue: no atomics, no extra pass).
+hipError_t mn_backward(rpn_head_trainer *t, int B, hipStream_t s)
+{
+    const std::vector<MnConv> &tab = mn_table();
+    const int F = t->F;
+    const long long P = (long long)B * F * F;
+    float *g = t->d_mt[1];
+    const float *gres = nullptr;
+    int a = 1;
+    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, nullptr, B, F, F, t->cin, 512, t->d_wt, g, s);
+    for (int i = kMnLayers - 1; i >= t->mn_from && e == hipSuccess; --i) {
+        const MnConv &l = tab[i];
+        const float *in = i == t->mn_from ? t->d_x0 : t->d_my[i - 1];
+        const float *w = t->d_w + t->off_mk[i];
+        const float *mean = t->d_bstat + t->off_bs[i], *rstd = mean + 2 * l.cout;
+        float *dz = g;
+        if (l.kind == 2) {
+            if (l.res) gres = g;
+            dz = t->d_mt[0];
+        }
+        e = launch_bn_backward(t->d_mz[i], g, P, l.cout, mean, rstd, t->d_w + t->off_mg[i], t->d_w + t->off_mb[i], l.kind != 2, t->d_mpart,
+                               t->d_g + t->off_mg[i], t->d_g + t->off_mb[i], dz, s);
+        if (e != hipSuccess) break;
+        if (l.kind == 1) {
+            e = launch_dwconv3x3_wgrad(in, dz, B, F, F, l.cout, t->d_mwpart, t->d_g + t->off_mk[i], s);
+            float *dx = dz == t->d_mt[1] ? t->d_mt[2] : t->d_mt[1];
+            if (e == hipSuccess) e = launch_dwconv3x3_dgrad(dz, w, B, F, F, l.cout, dx, s);
+            g = dx;
+            continue;
+        }
+        e = launch_conv1x1_wgrad(in, dz, P, l.cin, l.cout, t->d_mwpart, t->d_g + t->off_mk[i], s);
+        if (e != hipSuccess || i == t->mn_from) break;
+        if (l.kind == 2) {
+            g = t->d_mt[1];
+            e = launch_conv1x1_dgrad(dz, w, nullptr, P, l.cin, l.cout, g, s);
+        } else {
+            float *dx = t->d_mgr[a ^ 1];
+            e = launch_conv1x1_dgrad(dz, w, gres, P, l.cin, l.cout, dx, s);
+            a ^= 1;
+            g = dx;
+            gres = nullptr;
+        }
+    }
+    return e;
+}
+
 }  // namespace
 
 extern "C" int rpn_head_trainer_create(rpn_model *m, rpn_head_trainer **out)
@@ -740,9 +942,42 @@ extern "C" int rpn_model_trainer_create(rpn_model *m, const char *train_from, rp
     if (!train_from) return rpn_head_trainer_create(m, out);
     int backbone, img;
     model_train_backbone(m, &backbone, &img);
-    RPN_REQUIRE(backbone == RPN_BACKBONE_VGG16,
-                "rpn_model_trainer_create: backbone training needs VGG16 (MobileNetV2 trains its head only: its backward needs "
-                "depthwise convs and BatchNorm in training mode)");
+    if (backbone == RPN_BACKBONE_MOBILENET_V2) {
+        const std::vector<MnConv> &tab = mn_table();
+        const int from = mn_index(train_from);
+        RPN_REQUIRE(from >= 0 && tab[from].kind == 0,
+                    "rpn_model_trainer_create: '%s' does not start a trainable span of MobileNetV2: accepted are block_7_expand .. "
+                    "block_12_expand and block_13_expand (that layer and every layer above it train with the head); otherwise this "
+                    "backbone trains its head only -- the layer is a VGG16 conv, is not the first layer of a block, or lies below "
+                    "block_7_expand", train_from);
+        rpn_head_trainer *t = nullptr;
+        const int st = rpn_head_trainer_create(m, &t);
+        if (st != RPN_OK) return st;
+        t->mn_x0 = from == 0 ? "block_6_project" : tab[from - 1].name;
+        int h = 0, w = 0, c = 0;
+        if (t->cin != 576 || model_tensor_shape(m, t->mn_x0.c_str(), &h, &w, &c) != RPN_OK || h != t->F || w != t->F || c != tab[from].cin) {
+            rpn_head_trainer_destroy(t);
+            return fail(RPN_ERR_UNSUPPORTED, "rpn_model_trainer_create: unexpected MobileNetV2 graph below '%s'", train_from);
+        }
+        t->mn_from = from;
+        size_t state = 0, bstat = 0;
+        for (int i = from; i < kMnLayers; ++i) {
+            t->off_mk[i] = (t->n + 3) & ~(size_t)3;     // the kernels read these slices as float4 (every slice's length is a multiple of 4)
+            t->off_mg[i] = t->off_mk[i] + mn_kernel_floats(i);
+            t->off_mb[i] = t->off_mg[i] + tab[i].cout;
+            t->n = t->off_mb[i] + tab[i].cout;
+            t->off_ms[i] = state;
+            state += (size_t)2 * tab[i].cout;
+            t->off_bs[i] = bstat;
+            bstat += (size_t)3 * tab[i].cout;
+            if (tab[i].kind != 1) t->ps_mn[i] = packed_shape(1, 1, tab[i].cin, tab[i].cout);
+        }
+        t->host_w.assign(t->n, 0.0f);
+        t->host_bn.assign(state, 0.0f);
+        *out = t;
+        return RPN_OK;
+    }
+    RPN_REQUIRE(backbone == RPN_BACKBONE_VGG16, "rpn_model_trainer_create: unknown backbone %d", backbone);
     const int from = vgg_index(train_from);
     RPN_REQUIRE(from >= 0, "rpn_model_trainer_create: '%s' is not a VGG16 conv (block1_conv1 .. block5_conv3)", train_from);
     int hs[13];
@@ -783,7 +1018,20 @@ extern "C" void rpn_head_trainer_destroy(rpn_head_trainer *t)
 
 extern "C" int rpn_head_trainer_set_layer(rpn_head_trainer *t, const char *name, const float *kernel, const float *bias)
 {
-    RPN_REQUIRE(t && name && kernel && bias, "rpn_head_trainer_set_layer: null argument");
+    RPN_REQUIRE(t && name && kernel, "rpn_head_trainer_set_layer: null argument");
+    const int mi = t->mn_from >= 0 ? mn_index(name) : -1;
+    if (mi >= 0) {
+        // a MobileNetV2 conv of the span: the kernel alone (these convs have no bias; rpn_head_trainer_set_bn carries the BatchNorm)
+        RPN_REQUIRE(mi >= t->mn_from, "rpn_head_trainer_set_layer: '%s' is frozen (training starts at %s): it runs on the model handle", name,
+                    mn_table()[t->mn_from].name.c_str());
+        RPN_REQUIRE(!bias, "rpn_head_trainer_set_layer: '%s' has no bias (pass NULL)", name);
+        if (t->d_w) RPN_HIP_CHECK(hipMemcpy(t->host_w.data(), t->d_w, t->n * sizeof(float), hipMemcpyDeviceToHost));
+        memcpy(&t->host_w[t->off_mk[mi]], kernel, mn_kernel_floats(mi) * sizeof(float));
+        if (t->d_w) RPN_HIP_CHECK(hipMemcpy(t->d_w, t->host_w.data(), t->n * sizeof(float), hipMemcpyHostToDevice));
+        t->mn_loaded[mi] = true;
+        return RPN_OK;
+    }
+    RPN_REQUIRE(bias, "rpn_head_trainer_set_layer: null argument");
     const int li = layer_index(name);
     const int bi = t->bb_from >= 0 ? vgg_index(name) : -1;
     RPN_REQUIRE(li >= 0 || bi >= 0, "rpn_head_trainer_set_layer: '%s' is not trained (the backbone is frozen: rpn_conv, rpn_reg, rpn_cls only)",
@@ -819,9 +1067,31 @@ extern "C" int rpn_head_trainer_set_layer(rpn_head_trainer *t, const char *name,
 // a head layer's slices of the master weights (grad == 0) or of the last step's gradient (grad == 1) -> HOST kernel / bias
 static int trainer_read(rpn_head_trainer *t, const char *what, const char *name, float *kernel, float *bias, int grad, void *stream)
 {
-    RPN_REQUIRE(t && name && kernel && bias, "%s: null argument", what);
+    RPN_REQUIRE(t && name && kernel, "%s: null argument", what);
+    const int mi = t->mn_from >= 0 ? mn_index(name) : -1;
+    if (mi >= 0) {
+        RPN_REQUIRE(mi >= t->mn_from, "%s: layer '%s' is frozen (training starts at %s): it runs on the model handle", what, name,
+                    mn_table()[t->mn_from].name.c_str());
+        RPN_REQUIRE(!bias, "%s: '%s' has no bias (pass NULL)", what, name);
+        RPN_REQUIRE(t->mn_loaded[mi], "%s: layer '%s' was never set", what, name);
+        RPN_REQUIRE(!grad || t->t > 0, "%s: no update step has run", what);
+        if (t->d_w) {
+            RPN_HIP_CHECK(hipMemcpyAsync(kernel, (grad ? t->d_g : t->d_w) + t->off_mk[mi], mn_kernel_floats(mi) * sizeof(float),
+                                         hipMemcpyDeviceToHost, as_stream(stream)));
+            RPN_HIP_CHECK(hipStreamSynchronize(as_stream(stream)));
+        } else {
+            memcpy(kernel, &t->host_w[t->off_mk[mi]], mn_kernel_floats(mi) * sizeof(float));
+        }
+        return RPN_OK;
+    }
     const int li = layer_index(name);
     const int bi = t->bb_from >= 0 ? vgg_index(name) : -1;
+    if (li < 0 && bi < 0 && t->mn_from >= 0) {     // a layer of the model below the span, or no layer of it at all
+        RPN_REQUIRE(model_has_layer(t->m, name), "%s: the model has no layer named '%s'", what, name);
+        return fail(RPN_ERR_INVALID, "%s: '%s' is frozen (training starts at %s): it runs on the model handle", what, name,
+                    mn_table()[t->mn_from].name.c_str());
+    }
+    RPN_REQUIRE(bias, "%s: null argument", what);
     RPN_REQUIRE(li >= 0 || bi >= 0, "%s: '%s' is not trained (rpn_conv, rpn_reg, rpn_cls)", what, name);
     RPN_REQUIRE(li >= 0 ? t->loaded[li] : t->bb_loaded[bi], "%s: layer '%s' was never set", what, name);
     RPN_REQUIRE(!grad || bi < 0 || bi >= t->bb_from, "%s: layer '%s' is frozen (training starts at %s): it has no gradient", what, name,
@@ -863,6 +1133,73 @@ extern "C" int rpn_head_trainer_get_gradient(rpn_head_trainer *t, const char *na
     return trainer_read(t, "rpn_head_trainer_get_gradient", name, kernel, bias, 1, stream);
 }
 
+// ---- the BatchNorm of a trained MobileNetV2 conv (named by the conv or by its BatchNorm layer, "<conv>_BN") --------------------------
+extern "C" int rpn_head_trainer_set_bn(rpn_head_trainer *t, const char *name, const float *gamma, const float *beta, const float *mean,
+                                       const float *var)
+{
+    RPN_REQUIRE(t && name && gamma && beta && mean && var, "rpn_head_trainer_set_bn: null argument");
+    const int mi = t->mn_from >= 0 ? mn_index(name, true) : -1;
+    RPN_REQUIRE(mi >= 0, "rpn_head_trainer_set_bn: '%s' is not a BatchNorm this trainer trains", name);
+    RPN_REQUIRE(mi >= t->mn_from, "rpn_head_trainer_set_bn: '%s' is frozen (training starts at %s): it runs on the model handle", name,
+                mn_table()[t->mn_from].name.c_str());
+    const size_t C = (size_t)mn_table()[mi].cout;
+    if (t->d_w) {
+        RPN_HIP_CHECK(hipMemcpy(t->host_w.data(), t->d_w, t->n * sizeof(float), hipMemcpyDeviceToHost));
+        RPN_HIP_CHECK(hipMemcpy(t->host_bn.data(), t->d_bn, t->host_bn.size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    memcpy(&t->host_w[t->off_mg[mi]], gamma, C * sizeof(float));
+    memcpy(&t->host_w[t->off_mb[mi]], beta, C * sizeof(float));
+    memcpy(&t->host_bn[t->off_ms[mi]], mean, C * sizeof(float));
+    memcpy(&t->host_bn[t->off_ms[mi] + C], var, C * sizeof(float));
+    if (t->d_w) {
+        RPN_HIP_CHECK(hipMemcpy(t->d_w, t->host_w.data(), t->n * sizeof(float), hipMemcpyHostToDevice));
+        RPN_HIP_CHECK(hipMemcpy(t->d_bn, t->host_bn.data(), t->host_bn.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    t->mn_bn_loaded[mi] = true;
+    return RPN_OK;
+}
+
+// gamma, beta (grad: their gradients at the last update step) and, !grad, the moving mean / variance -> HOST arrays
+static int trainer_read_bn(rpn_head_trainer *t, const char *what, const char *name, float *a, float *b, float *mean, float *var, int grad,
+                           void *stream)
+{
+    RPN_REQUIRE(t && name && a && b && (grad || (mean && var)), "%s: null argument", what);
+    const int mi = t->mn_from >= 0 ? mn_index(name, true) : -1;
+    RPN_REQUIRE(mi >= 0, "%s: '%s' is not a BatchNorm this trainer trains", what, name);
+    RPN_REQUIRE(mi >= t->mn_from, "%s: '%s' is frozen (training starts at %s): it runs on the model handle", what, name,
+                mn_table()[t->mn_from].name.c_str());
+    RPN_REQUIRE(t->mn_bn_loaded[mi], "%s: BatchNorm '%s' was never set", what, name);
+    RPN_REQUIRE(!grad || t->t > 0, "%s: no update step has run", what);
+    const size_t C = (size_t)mn_table()[mi].cout;
+    if (t->d_w) {
+        hipStream_t s = as_stream(stream);
+        const float *src = grad ? t->d_g : t->d_w;
+        RPN_HIP_CHECK(hipMemcpyAsync(a, src + t->off_mg[mi], C * sizeof(float), hipMemcpyDeviceToHost, s));
+        RPN_HIP_CHECK(hipMemcpyAsync(b, src + t->off_mb[mi], C * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (!grad) {
+            RPN_HIP_CHECK(hipMemcpyAsync(mean, t->d_bn + t->off_ms[mi], C * sizeof(float), hipMemcpyDeviceToHost, s));
+            RPN_HIP_CHECK(hipMemcpyAsync(var, t->d_bn + t->off_ms[mi] + C, C * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        RPN_HIP_CHECK(hipStreamSynchronize(s));
+        return RPN_OK;
+    }
+    memcpy(a, &t->host_w[t->off_mg[mi]], C * sizeof(float));
+    memcpy(b, &t->host_w[t->off_mb[mi]], C * sizeof(float));
+    memcpy(mean, &t->host_bn[t->off_ms[mi]], C * sizeof(float));
+    memcpy(var, &t->host_bn[t->off_ms[mi] + C], C * sizeof(float));
+    return RPN_OK;
+}
+
+extern "C" int rpn_head_trainer_get_bn(rpn_head_trainer *t, const char *name, float *gamma, float *beta, float *mean, float *var, void *stream)
+{
+    return trainer_read_bn(t, "rpn_head_trainer_get_bn", name, gamma, beta, mean, var, 0, stream);
+}
+
+extern "C" int rpn_head_trainer_get_bn_gradient(rpn_head_trainer *t, const char *name, float *dgamma, float *dbeta, void *stream)
+{
+    return trainer_read_bn(t, "rpn_head_trainer_get_bn_gradient", name, dgamma, dbeta, nullptr, nullptr, 1, stream);
+}
+
 extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
                                      const float *d_bbox_labels, int update, float lr, float beta_1, float beta_2, float epsilon,
                                      float *d_losses, void *stream)
@@ -876,6 +1213,9 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
     for (int i = 0; i < 3; ++i) RPN_REQUIRE(t->loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kHeadLayers[i]);
     if (t->bb_from >= 0)
         for (int i = 0; i < 13; ++i) RPN_REQUIRE(t->bb_loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kVgg[i].name);
+    for (int i = std::max(t->mn_from, 0); t->mn_from >= 0 && i < kMnLayers; ++i)
+        RPN_REQUIRE(t->mn_loaded[i] && t->mn_bn_loaded[i], "rpn_head_trainer_step: layer '%s' or its BatchNorm was never set",
+                    mn_table()[i].name.c_str());
     const int st = trainer_device(t);
     if (st != RPN_OK) return st;
     hipStream_t s = as_stream(stream);
@@ -886,6 +1226,10 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
         // a trained backbone: the whole VGG16 in exact float32 from the trainer's weights
         const hipError_t eb = backbone_forward(t, d_imgs, B, s, &feat);
         if (eb != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: backbone: %s", hipGetErrorString(eb));
+    } else if (t->mn_from >= 0) {
+        // a trained MobileNetV2 span: BatchNorm in training mode on an update step, in inference mode on an evaluation
+        const int e0 = mn_forward(t, d_imgs, B, update != 0, s);
+        if (e0 != RPN_OK) return e0;
     } else {
         const int e0 = model_features(t->m, d_imgs, B, t->d_feat, s);
         if (e0 != RPN_OK) return e0;
@@ -938,6 +1282,7 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
         if (e == hipSuccess) e = launch_wgrad(feat, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
         if (e == hipSuccess) e = launch_colsum(t->d_dS, P, 512, t->d_part, t->d_g + t->off_cb, s);
         if (e == hipSuccess && t->bb_from >= 0) e = backbone_backward(t, B, s);
+        if (e == hipSuccess && t->mn_from >= 0) e = mn_backward(t, B, s);
         if (e == hipSuccess) {
             ++t->t;
             hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)t->n)), dim3(256), 0, s, t->d_w, t->d_g, t->d_m, t->d_v, (long long)t->n,

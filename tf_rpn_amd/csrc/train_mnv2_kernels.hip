@@ -1,0 +1,607 @@
+// train_mnv2_kernels.hip -- backward of MobileNetV2's stride-16 inverted-residual blocks (block_7 .. block_12, block_13_expand):
+// BatchNorm in training mode, the 1x1 convs on the float32 MFMA, the depthwise 3x3 stride-1 convs.  The trainer that strings them
+// together is in train_kernels.hip (mn_forward / mn_backward).
+//
+// BatchNorm form (TF 2.0's fused BatchNorm, restated as recalled -- nothing here can run TF): over the N = B H W pixels of a channel,
+//   mean = sum x / N, var = sum (x - mean)^2 / N (biased), xhat = (x - mean) / sqrt(var + eps), y = gamma xhat + beta;
+//   moving_mean = moving_mean * momentum + mean * (1 - momentum), moving_var likewise with var N / (N - 1) (Bessel);
+//   backward: dbeta = sum dy, dgamma = sum dy xhat, dx = gamma / sqrt(var + eps) (dy - dbeta / N - xhat dgamma / N).
+// Keras MobileNetV2: eps 1e-3, momentum 0.999.  The ReLU6 that follows is fused: forward min(max(y, 0), 6), backward dy [0 < y < 6]
+// (TF's Relu6Grad, strict on both sides), y recomputed from the kept conv output by the very expression of the forward.
+//
+// Reductions: the pixels are cut into a power-of-two number of leaves chosen from the shape alone; a leaf is summed in a fixed order
+// (16 row lanes per workgroup, each over its rows in order, then the lanes in order), the leaves in a fixed tree.  The BatchNorm sums
+// are carried in float64 (sum and sum of squares: var = E[x^2] - mean^2 is formed in float64, where a channel of mean 100 and spread
+// 0.1 still keeps 10 significant digits).  No floating-point atomics, no scratch memory.
+#include <algorithm>
+#include <cstdint>
+
+#include "rpn_common.h"
+#include "train_mnv2.h"
+
+namespace rpn {
+
+constexpr int kRedQuads = 16, kRedLanes = 16;   // a reduction workgroup: 16 channel quads x 16 row lanes
+constexpr int kMaxLeaves = 32;
+
+static size_t a256m(size_t v) { return (v + 255) & ~(size_t)255; }
+static int grid_1dm(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
+
+int mn_reduce_leaves(long long P)
+{
+    int L = 1;
+    while (L < kMaxLeaves && P / (2 * L) >= 16) L *= 2;
+    return L;
+}
+
+// sum of `leaves` (a power of two <= 32) values stride apart, in a fixed tree: absent leaves are zeros, which change no bit
+template <class T>
+__device__ inline T tree_sum32(const T *p, size_t stride, int leaves)
+{
+    T v[kMaxLeaves];
+#pragma unroll
+    for (int i = 0; i < kMaxLeaves; ++i) v[i] = i < leaves ? p[(size_t)i * stride] : T(0);
+#pragma unroll
+    for (int w = kMaxLeaves / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int i = 0; i < w; ++i) v[i] = v[i] + v[i + w];
+    return v[0];
+}
+
+__device__ inline float bn_rstd_of(float var, float eps) { return (float)(1.0 / sqrt((double)var + (double)eps)); }
+// the forward's value of one element: xhat, then y before the activation
+__device__ inline float bn_xhat(float x, float mean, float rstd) { return (x - mean) * rstd; }
+__device__ inline float bn_y(float xhat, float gamma, float beta) { return fmaf(xhat, gamma, beta); }
+
+// ---- BatchNorm statistics ------------------------------------------------------------------------------------------------------
+// part[leaf][0][C] = sum x, part[leaf][1][C] = sum x^2 over the leaf's pixels, float64.  grid (ceil(C / 64), leaves).
+__global__ void __launch_bounds__(256) bn_stats_partial_kernel(const float *__restrict__ x, long long P, int C, int leaves,
+                                                              double *__restrict__ part)
+{
+    __shared__ double red[kRedLanes][2 * kRedQuads * 4];
+    const int q = threadIdx.x & (kRedQuads - 1), rl = threadIdx.x / kRedQuads;
+    const int C4 = C / 4, cq = blockIdx.x * kRedQuads + q, leaf = blockIdx.y;
+    const long long pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
+    if (cq < C4) {
+        for (long long p = pbeg + rl; p < pend; p += kRedLanes) {
+            const float4 v = reinterpret_cast<const float4 *>(x)[p * C4 + cq];
+            const double d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s[j] += d[j];
+                ss[j] = fma(d[j], d[j], ss[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        red[rl][4 * q + j] = s[j];
+        red[rl][kRedQuads * 4 + 4 * q + j] = ss[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * kRedQuads * 4) {
+        const int which = threadIdx.x / (kRedQuads * 4), ch = blockIdx.x * kRedQuads * 4 + (threadIdx.x % (kRedQuads * 4));
+        double a = 0.0;
+        for (int r = 0; r < kRedLanes; ++r) a += red[r][threadIdx.x];
+        if (ch < C) part[((size_t)leaf * 2 + which) * C + ch] = a;
+    }
+}
+
+__global__ void __launch_bounds__(256) bn_stats_finish_kernel(const double *__restrict__ part, int leaves, int C, long long P, float eps,
+                                                             float momentum, float *__restrict__ mean, float *__restrict__ var,
+                                                             float *__restrict__ rstd, float *__restrict__ mmean, float *__restrict__ mvar)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const double s = tree_sum32<double>(part + c, (size_t)2 * C, leaves);
+    const double ss = tree_sum32<double>(part + C + c, (size_t)2 * C, leaves);
+    const double n = (double)P, m = s / n, v = fmax(0.0, ss / n - m * m);
+    const float mf = (float)m, vf = (float)v;
+    mean[c] = mf;
+    var[c] = vf;
+    rstd[c] = bn_rstd_of(vf, eps);
+    if (mmean) {
+        const float unbiased = (float)(P > 1 ? v * n / (n - 1.0) : v);
+        mmean[c] = mmean[c] * momentum + mf * (1.0f - momentum);
+        mvar[c] = mvar[c] * momentum + unbiased * (1.0f - momentum);
+    }
+}
+
+__global__ void __launch_bounds__(256) bn_rstd_kernel(const float *__restrict__ var, int C, float eps, float *__restrict__ rstd)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < C) rstd[c] = bn_rstd_of(var[c], eps);
+}
+
+// ---- BatchNorm apply (+ ReLU6, + residual): one pass, a float4 of channels per lane ------------------------------------------
+__global__ void __launch_bounds__(256) bn_apply_kernel(const float4 *__restrict__ x, long long total4, int C4, const float4 *__restrict__ mean,
+                                                      const float4 *__restrict__ rstd, const float4 *__restrict__ gamma,
+                                                      const float4 *__restrict__ beta, int relu6, const float4 *__restrict__ res,
+                                                      float4 *__restrict__ y)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        const float4 v = x[i], m = mean[c], r = rstd[c], g = gamma[c], b = beta[c];
+        float o[4] = {bn_y(bn_xhat(v.x, m.x, r.x), g.x, b.x), bn_y(bn_xhat(v.y, m.y, r.y), g.y, b.y),
+                      bn_y(bn_xhat(v.z, m.z, r.z), g.z, b.z), bn_y(bn_xhat(v.w, m.w, r.w), g.w, b.w)};
+        if (relu6) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = fminf(fmaxf(o[j], 0.0f), 6.0f);
+        }
+        if (res) {
+            const float4 e = res[i];
+            o[0] += e.x; o[1] += e.y; o[2] += e.z; o[3] += e.w;
+        }
+        y[i] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// ---- BatchNorm backward, pass 1: part[leaf][0][C] = sum dy', part[leaf][1][C] = sum dy' xhat (float64) ------------------------
+__global__ void __launch_bounds__(256) bn_bwd_partial_kernel(const float *__restrict__ x, const float *__restrict__ dy, long long P, int C,
+                                                            const float4 *__restrict__ mean, const float4 *__restrict__ rstd,
+                                                            const float4 *__restrict__ gamma, const float4 *__restrict__ beta, int relu6,
+                                                            int leaves, double *__restrict__ part)
+{
+    __shared__ double red[kRedLanes][2 * kRedQuads * 4];
+    const int q = threadIdx.x & (kRedQuads - 1), rl = threadIdx.x / kRedQuads;
+    const int C4 = C / 4, cq = blockIdx.x * kRedQuads + q, leaf = blockIdx.y;
+    const long long pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
+    double sb[4] = {0.0, 0.0, 0.0, 0.0}, sg[4] = {0.0, 0.0, 0.0, 0.0};
+    if (cq < C4) {
+        const float4 m4 = mean[cq], r4 = rstd[cq], g4 = gamma[cq], b4 = beta[cq];
+        const float m[4] = {m4.x, m4.y, m4.z, m4.w}, r[4] = {r4.x, r4.y, r4.z, r4.w}, g[4] = {g4.x, g4.y, g4.z, g4.w},
+                    b[4] = {b4.x, b4.y, b4.z, b4.w};
+        for (long long p = pbeg + rl; p < pend; p += kRedLanes) {
+            const float4 v4 = reinterpret_cast<const float4 *>(x)[p * C4 + cq], d4 = reinterpret_cast<const float4 *>(dy)[p * C4 + cq];
+            const float v[4] = {v4.x, v4.y, v4.z, v4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float xh = bn_xhat(v[j], m[j], r[j]), yv = bn_y(xh, g[j], b[j]);
+                const float dj = (!relu6 || (yv > 0.0f && yv < 6.0f)) ? d[j] : 0.0f;
+                sb[j] += (double)dj;
+                sg[j] = fma((double)dj, (double)xh, sg[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        red[rl][4 * q + j] = sb[j];
+        red[rl][kRedQuads * 4 + 4 * q + j] = sg[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * kRedQuads * 4) {
+        const int which = threadIdx.x / (kRedQuads * 4), ch = blockIdx.x * kRedQuads * 4 + (threadIdx.x % (kRedQuads * 4));
+        double a = 0.0;
+        for (int r = 0; r < kRedLanes; ++r) a += red[r][threadIdx.x];
+        if (ch < C) part[((size_t)leaf * 2 + which) * C + ch] = a;
+    }
+}
+
+__global__ void __launch_bounds__(256) bn_bwd_finish_kernel(const double *__restrict__ part, int leaves, int C, float *__restrict__ dgamma,
+                                                           float *__restrict__ dbeta)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    dbeta[c] = (float)tree_sum32<double>(part + c, (size_t)2 * C, leaves);
+    dgamma[c] = (float)tree_sum32<double>(part + C + c, (size_t)2 * C, leaves);
+}
+
+// ---- BatchNorm backward, pass 2: dx = gamma rstd (dy' - dbeta / N - xhat dgamma / N) -------------------------------------------
+__global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float4 *__restrict__ x, const float4 *dy, long long total4, int C4,
+                                                          const float4 *__restrict__ mean, const float4 *__restrict__ rstd,
+                                                          const float4 *__restrict__ gamma, const float4 *__restrict__ beta,
+                                                          const float4 *__restrict__ dgamma, const float4 *__restrict__ dbeta, float inv_n,
+                                                          int relu6, float4 *dx)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        const float4 v4 = x[i], d4 = dy[i], m4 = mean[c], r4 = rstd[c], g4 = gamma[c], b4 = beta[c], dg4 = dgamma[c], db4 = dbeta[c];
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w}, m[4] = {m4.x, m4.y, m4.z, m4.w},
+                    r[4] = {r4.x, r4.y, r4.z, r4.w}, g[4] = {g4.x, g4.y, g4.z, g4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w},
+                    dg[4] = {dg4.x, dg4.y, dg4.z, dg4.w}, db[4] = {db4.x, db4.y, db4.z, db4.w};
+        float o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float xh = bn_xhat(v[j], m[j], r[j]), yv = bn_y(xh, g[j], b[j]);
+            const float dj = (!relu6 || (yv > 0.0f && yv < 6.0f)) ? d[j] : 0.0f;
+            o[j] = g[j] * r[j] * (dj - db[j] * inv_n - xh * (dg[j] * inv_n));
+        }
+        dx[i] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+size_t bn_part_doubles(long long P, int C) { return (size_t)mn_reduce_leaves(P) * 2 * C; }
+
+hipError_t launch_bn_train_stats(const float *x, long long P, int C, float eps, float momentum, double *part, float *mean, float *var,
+                                 float *rstd, float *mmean, float *mvar, hipStream_t s)
+{
+    const int leaves = mn_reduce_leaves(P);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3((C + 63) / 64, leaves), dim3(256), 0, s, x, P, C, leaves, part);
+    hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, leaves, C, P, eps, momentum, mean, var, rstd,
+                       mmean, mvar);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_rstd(const float *var, int C, float eps, float *rstd, hipStream_t s)
+{
+    hipLaunchKernelGGL(bn_rstd_kernel, dim3((C + 255) / 256), dim3(256), 0, s, var, C, eps, rstd);
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_apply(const float *x, long long P, int C, const float *mean, const float *rstd, const float *gamma,
+                           const float *beta, int relu6, const float *res, float *y, hipStream_t s)
+{
+    const long long total4 = P * (C / 4);
+    auto f4 = [](const float *p) { return reinterpret_cast<const float4 *>(p); };
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_1dm(total4)), dim3(256), 0, s, f4(x), total4, C / 4, f4(mean), f4(rstd), f4(gamma),
+                       f4(beta), relu6, f4(res), reinterpret_cast<float4 *>(y));
+    return hipGetLastError();
+}
+
+hipError_t launch_bn_backward(const float *x, const float *dy, long long P, int C, const float *mean, const float *rstd,
+                              const float *gamma, const float *beta, int relu6, double *part, float *dgamma, float *dbeta, float *dx,
+                              hipStream_t s)
+{
+    const int leaves = mn_reduce_leaves(P);
+    const long long total4 = P * (C / 4);
+    auto f4 = [](const float *p) { return reinterpret_cast<const float4 *>(p); };
+    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((C + 63) / 64, leaves), dim3(256), 0, s, x, dy, P, C, f4(mean), f4(rstd), f4(gamma),
+                       f4(beta), relu6, leaves, part);
+    hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, leaves, C, dgamma, dbeta);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_1dm(total4)), dim3(256), 0, s, f4(x), f4(dy), total4, C / 4, f4(mean), f4(rstd),
+                       f4(gamma), f4(beta), f4(dgamma), f4(dbeta), (float)(1.0 / (double)P), relu6, reinterpret_cast<float4 *>(dx));
+    return hipGetLastError();
+}
+
+// ---- 1x1 conv backward: one GEMM kernel on v_mfma_f32_32x32x2_f32 -------------------------------------------------------------------
+// C (M x N) = sum_k A(m, k) B(k, n) over k in leaf blockIdx.z of `leaves` fixed ranges of K.
+//   KCONTIG = false (weight gradient: A = x (P, Cin), B = dy (P, Cout), K = the pixels): A[k][m], B[k][n], a K slice of either is a
+//     contiguous run of channels per pixel;
+//   KCONTIG = true (input gradient: A = dy (P, Cout), B = w (Cin, Cout), K = Cout): A[m][k], B[n][k], rows run along K and are
+//     transposed on their way into LDS.
+// Workgroup: a 64 x 64 tile, four waves of 32 x 32 (one MFMA block each); K slices of 16 staged global -> registers -> LDS, double
+// buffered with one barrier per slice, as conv3x3_wgrad_f32_kernel stages its operands.  Each leaf writes its own slab of `out`
+// (out + leaf M N); `add` (M x N, leaves == 1 only) is added in the epilogue.  M, N, the row lengths and K (KCONTIG) are multiples of 4.
+constexpr int kGmT = 64, kGmK = 16, kGmLd = 96;   // LDS row stride 96: the two half-waves of a fragment read hit disjoint banks
+
+using f32x16m = __attribute__((ext_vector_type(16))) float;
+
+template <bool KCONTIG>
+__global__ void __launch_bounds__(256) gemm1x1_f32_kernel(const float *__restrict__ A, const float *__restrict__ Bm, int M, int N, long long K,
+                                                         int lda, int ldb, int leaves, const float *__restrict__ add, float *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) float As[2][kGmK][kGmLd];
+    __shared__ __attribute__((aligned(16))) float Bs[2][kGmK][kGmLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n0 = blockIdx.x * kGmT, m0 = blockIdx.y * kGmT, leaf = blockIdx.z;
+    const long long kbeg = K * leaf / leaves, kend = K * (leaf + 1) / leaves;
+    const int nsteps = (int)((kend - kbeg + kGmK - 1) / kGmK);
+    // loader.  !KCONTIG: thread -> (K row kr of the slice, channel quad q).  KCONTIG: thread -> (tile row r, K quad kq)
+    const int kr = tid >> 4, q = tid & 15, r = tid >> 2, kq = tid & 3;
+    float4 ra, rb;
+    auto load_global = [&](long long k0) {
+        ra = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        rb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!KCONTIG) {
+            const long long k = k0 + kr;
+            if (k < kend) {
+                if (m0 + 4 * q < M) ra = *reinterpret_cast<const float4 *>(A + (size_t)k * lda + m0 + 4 * q);
+                if (n0 + 4 * q < N) rb = *reinterpret_cast<const float4 *>(Bm + (size_t)k * ldb + n0 + 4 * q);
+            }
+        } else {
+            const long long k = k0 + 4 * kq;
+            if (k < kend) {
+                if (m0 + r < M) ra = *reinterpret_cast<const float4 *>(A + (size_t)(m0 + r) * lda + k);
+                if (n0 + r < N) rb = *reinterpret_cast<const float4 *>(Bm + (size_t)(n0 + r) * ldb + k);
+            }
+        }
+    };
+    auto store_lds = [&](int buf) {
+        if (!KCONTIG) {
+            *reinterpret_cast<float4 *>(&As[buf][kr][4 * q]) = ra;
+            *reinterpret_cast<float4 *>(&Bs[buf][kr][4 * q]) = rb;
+        } else {
+            As[buf][4 * kq + 0][r] = ra.x; As[buf][4 * kq + 1][r] = ra.y; As[buf][4 * kq + 2][r] = ra.z; As[buf][4 * kq + 3][r] = ra.w;
+            Bs[buf][4 * kq + 0][r] = rb.x; Bs[buf][4 * kq + 1][r] = rb.y; Bs[buf][4 * kq + 2][r] = rb.z; Bs[buf][4 * kq + 3][r] = rb.w;
+        }
+    };
+    f32x16m acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    const int am = wm * 32 + (lane & 31), bn = wn * 32 + (lane & 31), kh = lane >> 5;
+
+    load_global(kbeg);
+    store_lds(0);
+    __syncthreads();
+    int cur = 0;
+    for (int step = 0; step < nsteps; ++step) {
+        const bool more = step + 1 < nsteps;
+        if (more) load_global(kbeg + (long long)(step + 1) * kGmK);
+#pragma unroll
+        for (int kk = 0; kk < kGmK / 2; ++kk)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[cur][2 * kk + kh][am], Bs[cur][2 * kk + kh][bn], acc, 0, 0, 0);
+        if (more) store_lds(cur ^ 1);
+        __syncthreads();
+        cur ^= 1;
+    }
+    // accumulator element e: row 8 (e / 4) + 4 kh + e % 4, column lane % 32
+    const int col = n0 + bn;
+    if (col >= N) return;
+    float *slab = out + (size_t)leaf * M * N;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * 32 + 8 * (e >> 2) + 4 * kh + (e & 3);
+        if (row < M) {
+            const size_t o = (size_t)row * N + col;
+            slab[o] = add ? acc[e] + add[o] : acc[e];
+        }
+    }
+}
+
+// out[j] = the fixed tree over the `leaves` slabs of len floats
+__global__ void __launch_bounds__(256) leaf_tree_kernel(const float *__restrict__ part, long long len, int leaves, float *__restrict__ out)
+{
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256)
+        out[j] = tree_sum32<float>(part + j, (size_t)len, leaves);
+}
+
+int conv1x1_wgrad_leaves(long long P, int Cin, int Cout)
+{
+    const long long tiles = (long long)((Cin + kGmT - 1) / kGmT) * ((Cout + kGmT - 1) / kGmT);
+    int L = 1;
+    while (L < kMaxLeaves && P / (2 * L) >= 64 && tiles * L < 512) L *= 2;
+    return L;
+}
+
+size_t conv1x1_wgrad_ws_floats(long long P, int Cin, int Cout)
+{
+    const int L = conv1x1_wgrad_leaves(P, Cin, Cout);
+    return L > 1 ? (size_t)L * Cin * Cout : 0;
+}
+
+hipError_t launch_conv1x1_wgrad(const float *x, const float *dy, long long P, int Cin, int Cout, float *part, float *dw, hipStream_t s)
+{
+    const int L = conv1x1_wgrad_leaves(P, Cin, Cout);
+    hipLaunchKernelGGL(gemm1x1_f32_kernel<false>, dim3((Cout + kGmT - 1) / kGmT, (Cin + kGmT - 1) / kGmT, L), dim3(256), 0, s, x, dy, Cin, Cout,
+                       P, Cin, Cout, L, (const float *)nullptr, L > 1 ? part : dw);
+    if (L > 1) {
+        const long long len = (long long)Cin * Cout;
+        hipLaunchKernelGGL(leaf_tree_kernel, dim3(grid_1dm(len)), dim3(256), 0, s, part, len, L, dw);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_conv1x1_dgrad(const float *dy, const float *w, const float *add, long long P, int Cin, int Cout, float *dx,
+                                hipStream_t s)
+{
+    hipLaunchKernelGGL(gemm1x1_f32_kernel<true>, dim3((Cin + kGmT - 1) / kGmT, (unsigned)((P + kGmT - 1) / kGmT), 1), dim3(256), 0, s, dy, w,
+                       (int)P, Cin, (long long)Cout, Cout, Cout, 1, add, dx);
+    return hipGetLastError();
+}
+
+// ---- depthwise 3x3 stride-1 'same' backward ------------------------------------------------------------------------------------------
+// dgrad: the depthwise conv of dy with the taps flipped; a float4 of channels per lane, as dwconv3x3_kernel
+__global__ void __launch_bounds__(256) dwconv3x3_dgrad_kernel(const float4 *__restrict__ dy, const float4 *__restrict__ w, int H, int W, int C4,
+                                                             long long total, float4 *__restrict__ dx)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        long long t = i / C4;
+        const int ox = (int)(t % W);
+        t /= W;
+        const int oy = (int)(t % H);
+        const long long b = t / H;
+        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int iy = oy + 1 - r;
+            if (iy < 0 || iy >= H) continue;
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const int ix = ox + 1 - s;
+                if (ix < 0 || ix >= W) continue;
+                const float4 v = dy[((b * H + iy) * W + ix) * C4 + c];
+                const float4 k = w[(r * 3 + s) * C4 + c];
+                acc.x = fmaf(v.x, k.x, acc.x);
+                acc.y = fmaf(v.y, k.y, acc.y);
+                acc.z = fmaf(v.z, k.z, acc.z);
+                acc.w = fmaf(v.w, k.w, acc.w);
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
+// wgrad: part[leaf][9][C] = the nine per-channel sums over the leaf's pixels.  grid (ceil(C / 64), leaves)
+__global__ void __launch_bounds__(256) dwconv3x3_wgrad_partial_kernel(const float4 *__restrict__ x, const float4 *__restrict__ dy, int B, int H,
+                                                                     int W, int C, int leaves, float *__restrict__ part)
+{
+    __shared__ float red[kRedLanes][kRedQuads * 36];
+    const int q = threadIdx.x & (kRedQuads - 1), rl = threadIdx.x / kRedQuads;
+    const int C4 = C / 4, cq = blockIdx.x * kRedQuads + q, leaf = blockIdx.y;
+    const long long P = (long long)B * H * W, pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
+    float4 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (cq < C4) {
+        for (long long p = pbeg + rl; p < pend; p += kRedLanes) {
+            const int px = (int)(p % W), py = (int)((p / W) % H);
+            const long long b = p / ((long long)W * H);
+            const float4 d = dy[p * C4 + cq];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int iy = py + r - 1;
+                if (iy < 0 || iy >= H) continue;
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    const int ix = px + s - 1;
+                    if (ix < 0 || ix >= W) continue;
+                    const float4 v = x[((b * H + iy) * W + ix) * C4 + cq];
+                    float4 &a = acc[r * 3 + s];
+                    a.x = fmaf(v.x, d.x, a.x);
+                    a.y = fmaf(v.y, d.y, a.y);
+                    a.z = fmaf(v.z, d.z, a.z);
+                    a.w = fmaf(v.w, d.w, a.w);
+                }
+            }
+        }
+    }
+    // red[lane][tap][64 channels of the tile]
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        red[rl][t * 64 + 4 * q + 0] = acc[t].x;
+        red[rl][t * 64 + 4 * q + 1] = acc[t].y;
+        red[rl][t * 64 + 4 * q + 2] = acc[t].z;
+        red[rl][t * 64 + 4 * q + 3] = acc[t].w;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < 9 * 64; o += 256) {
+        const int t = o / 64, ch = blockIdx.x * 64 + (o % 64);
+        float a = 0.0f;
+        for (int l = 0; l < kRedLanes; ++l) a += red[l][o];
+        if (ch < C) part[((size_t)leaf * 9 + t) * C + ch] = a;
+    }
+}
+
+hipError_t launch_dwconv3x3_dgrad(const float *dy, const float *w, int B, int H, int W, int C, float *dx, hipStream_t s)
+{
+    const long long total = (long long)B * H * W * (C / 4);
+    hipLaunchKernelGGL(dwconv3x3_dgrad_kernel, dim3(grid_1dm(total)), dim3(256), 0, s, reinterpret_cast<const float4 *>(dy),
+                       reinterpret_cast<const float4 *>(w), H, W, C / 4, total, reinterpret_cast<float4 *>(dx));
+    return hipGetLastError();
+}
+
+size_t dwconv3x3_wgrad_ws_floats(long long P, int C) { return (size_t)mn_reduce_leaves(P) * 9 * C; }
+
+hipError_t launch_dwconv3x3_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *part, float *dw, hipStream_t s)
+{
+    const int leaves = mn_reduce_leaves((long long)B * H * W);
+    hipLaunchKernelGGL(dwconv3x3_wgrad_partial_kernel, dim3((C + 63) / 64, leaves), dim3(256), 0, s, reinterpret_cast<const float4 *>(x),
+                       reinterpret_cast<const float4 *>(dy), B, H, W, C, leaves, part);
+    hipLaunchKernelGGL(leaf_tree_kernel, dim3(grid_1dm(9LL * C)), dim3(256), 0, s, part, 9LL * C, leaves, dw);
+    return hipGetLastError();
+}
+
+}  // namespace rpn
+
+using namespace rpn;
+
+// ---- C ABI: single-layer entries ---------------------------------------------------------------------------------------------------
+// the kernels read and write their tensors as float4
+template <typename... T> static bool al16(const T *...p) { return ((... | (uintptr_t)p) & 15) == 0; }
+#define MN_ALIGNED(what, ...) RPN_REQUIRE(al16(__VA_ARGS__), what ": every device pointer must be 16-byte aligned")
+
+static bool pc_ok(long long P, int C) { return P >= 1 && P <= (1ll << 31) && C >= 4 && C % 4 == 0 && C <= (1 << 16); }
+static size_t bn_ws_bytes(long long P, int C) { return a256m(bn_part_doubles(P, C) * sizeof(double)) + a256m((size_t)C * sizeof(float)); }
+
+extern "C" size_t rpn_batchnorm_workspace_bytes(long long P, int C) { return pc_ok(P, C) ? bn_ws_bytes(P, C) : 0; }
+
+extern "C" int rpn_batchnorm_train_forward(const float *d_x, long long P, int C, const float *d_gamma, const float *d_beta, int relu6,
+                                           float eps, float momentum, float *d_y, float *d_mean, float *d_var, float *d_moving_mean,
+                                           float *d_moving_var, void *d_ws, size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_x && d_gamma && d_beta && d_y && d_mean && d_var, "rpn_batchnorm_train_forward: null pointer");
+    RPN_REQUIRE(pc_ok(P, C), "rpn_batchnorm_train_forward: bad shape (P %lld, C %d: C must be a multiple of 4)", P, C);
+    RPN_REQUIRE((d_moving_mean == nullptr) == (d_moving_var == nullptr), "rpn_batchnorm_train_forward: moving mean and variance go together");
+    MN_ALIGNED("rpn_batchnorm_train_forward", d_x, d_gamma, d_beta, d_y, d_mean, d_var, d_moving_mean, d_moving_var, (const char *)d_ws);
+    RPN_REQUIRE(relu6 == 0 || relu6 == 1, "rpn_batchnorm_train_forward: relu6 must be 0 or 1");
+    RPN_REQUIRE(eps > 0.0f && momentum >= 0.0f && momentum <= 1.0f, "rpn_batchnorm_train_forward: bad eps / momentum");
+    if (!d_ws || ws_bytes < bn_ws_bytes(P, C))
+        return fail(RPN_ERR_WORKSPACE, "rpn_batchnorm_train_forward: %zu bytes of workspace needed", bn_ws_bytes(P, C));
+    RPN_REQUIRE_DEVICE();
+    hipStream_t s = as_stream(stream);
+    double *part = reinterpret_cast<double *>(d_ws);
+    float *rstd = reinterpret_cast<float *>((char *)d_ws + a256m(bn_part_doubles(P, C) * sizeof(double)));
+    hipError_t e = launch_bn_train_stats(d_x, P, C, eps, momentum, part, d_mean, d_var, rstd, d_moving_mean, d_moving_var, s);
+    if (e == hipSuccess) e = launch_bn_apply(d_x, P, C, d_mean, rstd, d_gamma, d_beta, relu6, nullptr, d_y, s);
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_batchnorm_train_forward: %s", hipGetErrorString(e));
+}
+
+extern "C" int rpn_batchnorm_train_backward(const float *d_x, const float *d_dy, long long P, int C, const float *d_gamma,
+                                            const float *d_beta, const float *d_mean, const float *d_var, int relu6, float eps, float *d_dx,
+                                            float *d_dgamma, float *d_dbeta, void *d_ws, size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_x && d_dy && d_gamma && d_beta && d_mean && d_var && d_dx && d_dgamma && d_dbeta, "rpn_batchnorm_train_backward: null pointer");
+    RPN_REQUIRE(pc_ok(P, C), "rpn_batchnorm_train_backward: bad shape (P %lld, C %d: C must be a multiple of 4)", P, C);
+    RPN_REQUIRE(relu6 == 0 || relu6 == 1, "rpn_batchnorm_train_backward: relu6 must be 0 or 1");
+    MN_ALIGNED("rpn_batchnorm_train_backward", d_x, d_dy, d_gamma, d_beta, d_mean, d_var, d_dx, d_dgamma, d_dbeta, (const char *)d_ws);
+    RPN_REQUIRE(eps > 0.0f, "rpn_batchnorm_train_backward: bad eps");
+    if (!d_ws || ws_bytes < bn_ws_bytes(P, C))
+        return fail(RPN_ERR_WORKSPACE, "rpn_batchnorm_train_backward: %zu bytes of workspace needed", bn_ws_bytes(P, C));
+    RPN_REQUIRE_DEVICE();
+    hipStream_t s = as_stream(stream);
+    double *part = reinterpret_cast<double *>(d_ws);
+    float *rstd = reinterpret_cast<float *>((char *)d_ws + a256m(bn_part_doubles(P, C) * sizeof(double)));
+    hipError_t e = launch_bn_rstd(d_var, C, eps, rstd, s);
+    if (e == hipSuccess) e = launch_bn_backward(d_x, d_dy, P, C, d_mean, rstd, d_gamma, d_beta, relu6, part, d_dgamma, d_dbeta, d_dx, s);
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_batchnorm_train_backward: %s", hipGetErrorString(e));
+}
+
+static bool gemm_ok(long long P, int Cin, int Cout)
+{
+    return P >= 1 && P <= (1ll << 21) && Cin >= 4 && Cout >= 4 && Cin % 4 == 0 && Cout % 4 == 0 && Cin <= 4096 && Cout <= 4096;
+}
+
+extern "C" size_t rpn_conv1x1_wgrad_workspace_bytes(long long P, int Cin, int Cout)
+{
+    return gemm_ok(P, Cin, Cout) ? a256m(conv1x1_wgrad_ws_floats(P, Cin, Cout) * sizeof(float)) : 0;
+}
+
+extern "C" int rpn_conv1x1_wgrad(const float *d_x, const float *d_dy, long long P, int Cin, int Cout, float *d_dw, void *d_ws, size_t ws_bytes,
+                                 void *stream)
+{
+    RPN_REQUIRE(d_x && d_dy && d_dw, "rpn_conv1x1_wgrad: null pointer");
+    RPN_REQUIRE(gemm_ok(P, Cin, Cout), "rpn_conv1x1_wgrad: bad shape (P %lld, Cin %d, Cout %d: channels must be multiples of 4)", P, Cin, Cout);
+    MN_ALIGNED("rpn_conv1x1_wgrad", d_x, d_dy, d_dw, (const char *)d_ws);
+    const size_t need = rpn_conv1x1_wgrad_workspace_bytes(P, Cin, Cout);
+    if (need && (!d_ws || ws_bytes < need)) return fail(RPN_ERR_WORKSPACE, "rpn_conv1x1_wgrad: %zu bytes of workspace needed", need);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_conv1x1_wgrad(d_x, d_dy, P, Cin, Cout, reinterpret_cast<float *>(d_ws), d_dw, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_conv1x1_wgrad: %s", hipGetErrorString(e));
+}
+
+extern "C" int rpn_conv1x1_dgrad(const float *d_dy, const float *d_w, const float *d_add, long long P, int Cin, int Cout, float *d_dx,
+                                 void *stream)
+{
+    RPN_REQUIRE(d_dy && d_w && d_dx, "rpn_conv1x1_dgrad: null pointer");
+    RPN_REQUIRE(gemm_ok(P, Cin, Cout), "rpn_conv1x1_dgrad: bad shape (P %lld, Cin %d, Cout %d: channels must be multiples of 4)", P, Cin, Cout);
+    MN_ALIGNED("rpn_conv1x1_dgrad", d_dy, d_w, d_add, d_dx);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_conv1x1_dgrad(d_dy, d_w, d_add, P, Cin, Cout, d_dx, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_conv1x1_dgrad: %s", hipGetErrorString(e));
+}
+
+static bool dw_ok(int B, int H, int W, int C)
+{
+    return B >= 1 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0 && C <= (1 << 16) && (long long)B * H * W <= (1ll << 31);
+}
+
+extern "C" int rpn_dwconv3x3_dgrad(const float *d_dy, const float *d_w, int B, int H, int W, int C, float *d_dx, void *stream)
+{
+    RPN_REQUIRE(d_dy && d_w && d_dx, "rpn_dwconv3x3_dgrad: null pointer");
+    RPN_REQUIRE(dw_ok(B, H, W, C), "rpn_dwconv3x3_dgrad: bad shape (C must be a multiple of 4)");
+    MN_ALIGNED("rpn_dwconv3x3_dgrad", d_dy, d_w, d_dx);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_dwconv3x3_dgrad(d_dy, d_w, B, H, W, C, d_dx, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_dwconv3x3_dgrad: %s", hipGetErrorString(e));
+}
+
+extern "C" size_t rpn_dwconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C)
+{
+    return dw_ok(B, H, W, C) ? a256m(dwconv3x3_wgrad_ws_floats((long long)B * H * W, C) * sizeof(float)) : 0;
+}
+
+extern "C" int rpn_dwconv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws, size_t ws_bytes,
+                                   void *stream)
+{
+    RPN_REQUIRE(d_x && d_dy && d_dw, "rpn_dwconv3x3_wgrad: null pointer");
+    RPN_REQUIRE(dw_ok(B, H, W, C), "rpn_dwconv3x3_wgrad: bad shape (C must be a multiple of 4)");
+    MN_ALIGNED("rpn_dwconv3x3_wgrad", d_x, d_dy, d_dw, (const char *)d_ws);
+    const size_t need = rpn_dwconv3x3_wgrad_workspace_bytes(B, H, W, C);
+    if (!d_ws || ws_bytes < need) return fail(RPN_ERR_WORKSPACE, "rpn_dwconv3x3_wgrad: %zu bytes of workspace needed", need);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_dwconv3x3_wgrad(d_x, d_dy, B, H, W, C, reinterpret_cast<float *>(d_ws), d_dw, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_dwconv3x3_wgrad: %s", hipGetErrorString(e));
+}

@@ -6,7 +6,9 @@ The inference surface the proposal path touches is mirrored: ``predict_on_batch`
 Training mirrors trainer.py:54-69 (``compile`` with Adam, ``train_on_batch`` / ``test_on_batch`` / ``fit``).  By default the RPN
 head (``rpn_conv``, ``rpn_reg``, ``rpn_cls``) is trained on a frozen backbone; ``compile(train_backbone_from="block1_conv1")``
 trains the whole VGG16 model as the reference does (its Keras base model is trainable), a later conv name the convs from there up.
-MobileNetV2 trains its head only (its backward needs depthwise convs and BatchNorm in training mode).
+On MobileNetV2 ``train_backbone_from`` names the first layer of a stride-16 inverted-residual block (``"block_7_expand"`` ..
+``"block_12_expand"``) or ``"block_13_expand"``: that layer and everything above it train with the head, BatchNorm in training mode;
+the layers below (the stride-2 depthwise convs, the stem, the large low-level activations) stay frozen.
 """
 import ctypes
 
@@ -37,6 +39,12 @@ HEAD_LAYERS = ("rpn_conv", "rpn_cls", "rpn_reg")
 # the VGG16 convs in graph order (keras.applications.VGG16 up to block5_conv3): what train_backbone_from names
 VGG16_CONVS = ("block1_conv1", "block1_conv2", "block2_conv1", "block2_conv2", "block3_conv1", "block3_conv2", "block3_conv3",
                "block4_conv1", "block4_conv2", "block4_conv3", "block5_conv1", "block5_conv2", "block5_conv3")
+# MobileNetV2's convs at the feature map's own resolution (stride 16), in graph order: the span train_backbone_from can open.
+# Conv X is followed by the BatchNormalization layer "X_BN"; none has a bias.
+MOBILENET_V2_SPAN = tuple("block_%d_%s" % (b, part) for b in range(7, 13) for part in ("expand", "depthwise", "project")) + ("block_13_expand",)
+# ... and the names it accepts: the first layer of a block, or block_13_expand alone
+MOBILENET_V2_TRAIN_FROM = tuple("block_%d_expand" % b for b in range(7, 14))
+BN_KEYS = ("gamma", "beta", "mean", "var")
 
 
 class RPNModel(object):
@@ -66,9 +74,11 @@ class RPNModel(object):
         self.tap_layer = "block5_conv3" if backbone == "vgg16" else "block_13_expand"
         self._head = {}                 # head weights last given to set_weights / load_weights: {name: (kernel, bias)}
         self._backbone = {}             # the same for the VGG16 convs (the handle keeps only packed / transformed copies)
+        self._mn = {}                   # MobileNetV2's stride-16 span, UNFOLDED (the handle folds BatchNorm at load):
+                                        # {conv: {"kernel", "gamma", "beta", "mean", "var"}}
         self._t = L.vp(0)               # native trainer (compile)
         self._opt = None
-        self._train_from = None         # first trained VGG16 conv, None: the head only
+        self._train_from = None         # first trained backbone layer, None: the head only
         self._head_dirty = False        # the trainer's head differs from the handle's: copied before the next inference
 
     # ---- introspection ----------------------------------------------------------------
@@ -122,7 +132,11 @@ class RPNModel(object):
             else:
                 args += [None, None, None, None]
             L.check(lib.rpn_model_set_layer(self._h, name.encode(), *args), "rpn_model_set_layer(%s)" % name)
-            if name in HEAD_LAYERS or (self.backbone == "vgg16" and name in VGG16_CONVS):
+            if self.backbone == "mobilenet_v2" and name in MOBILENET_V2_SPAN:
+                self._mn[name] = dict({"kernel": kernel.copy()}, **{k: a.copy() for k, a in zip(BN_KEYS, keep[2:])})
+                if self._t and name in self.trained_layers():
+                    self._trainer_set(name)
+            elif name in HEAD_LAYERS or (self.backbone == "vgg16" and name in VGG16_CONVS):
                 (self._head if name in HEAD_LAYERS else self._backbone)[name] = (kernel.copy(), bias.copy())
                 if self._t and (name in HEAD_LAYERS or self._train_from is not None):
                     self._trainer_set(name)
@@ -270,8 +284,18 @@ class RPNModel(object):
         ``train_backbone_from=None`` (default) trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone,
         the backbone running at the handle's precision.  A VGG16 conv name trains that conv and every conv above it (up to
         ``block5_conv3``) with the head; ``"block1_conv1"`` trains the whole model, as the reference does (its Keras base model is
-        trainable).  Such a step runs the whole VGG16 forward in exact float32 from the trainer's own weights.  MobileNetV2 trains
-        its head only.  ``trainable`` names the head layers only and must be exactly the three of them.
+        trainable).  Such a step runs the whole VGG16 forward in exact float32 from the trainer's own weights.
+
+        On MobileNetV2 the name is one of ``MOBILENET_V2_TRAIN_FROM``: ``"block_7_expand"`` .. ``"block_12_expand"`` (the first
+        layer of an inverted-residual block) or ``"block_13_expand"``; it and every layer above it -- the stride-1 blocks at the
+        feature map's own resolution -- train with the head: per conv the kernel and its BatchNorm's gamma and beta.  The layers
+        below stay frozen and run as in inference (BatchNorm folded, the handle's ops and precision).  In ``train_on_batch`` the
+        trained layers run in exact float32 with BatchNorm in TRAINING mode -- batch mean and biased batch variance over (B, F, F),
+        eps 1e-3, and the moving statistics updated in the same step with momentum 0.999 and Bessel's correction (TF 2.0's fused
+        BatchNorm as recalled); ``test_on_batch`` normalises with the moving statistics and updates nothing (Keras ``evaluate``).
+        The stride-2 blocks, the stem and ``expanded_conv`` do not train yet; with any other name the backbone trains its head only.
+
+        ``trainable`` names the head layers only and must be exactly the three of them.
 
         Adam is TF 2.0's ApplyAdam (as recalled from its sources): alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t),
         m += (g - m)(1 - beta_1), v += (g^2 - v)(1 - beta_2), w -= alpha m / (sqrt(v) + epsilon), m = v = 0 at compile, t = the
@@ -282,14 +306,23 @@ class RPNModel(object):
                              "to train backbone convs too use train_backbone_from=<first trained conv>" % (trainable, HEAD_LAYERS))
         if train_backbone_from is not None:
             if self.backbone != "vgg16":
-                raise ValueError("train_backbone_from=%r: the %s backbone trains its head only (its backward needs depthwise "
-                                 "convs and BatchNorm in training mode)" % (train_backbone_from, self.backbone))
-            if train_backbone_from not in VGG16_CONVS:
+                if train_backbone_from not in MOBILENET_V2_TRAIN_FROM:
+                    raise ValueError("train_backbone_from=%r: on %s the accepted names are %s (that layer and every layer above it "
+                                     "train with the head); otherwise the backbone trains its head only -- the named layer is a VGG16 "
+                                     "conv, is not the first layer of a block, or lies below block_7_expand, where the stride-2 "
+                                     "depthwise convs and the stem have no backward yet"
+                                     % (train_backbone_from, self.backbone, MOBILENET_V2_TRAIN_FROM))
+            elif train_backbone_from not in VGG16_CONVS:
                 raise ValueError("train_backbone_from=%r is not a VGG16 conv (one of %s)" % (train_backbone_from, VGG16_CONVS))
         self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
         if self._t:
-            for k, d in self.get_weights().items():
-                (self._head if k in HEAD_LAYERS else self._backbone)[k] = (d["kernel"], d["bias"])
+            self._sync_head()       # layers the new trainer freezes run on the handle: they keep what the old one trained
+            got = self.get_weights()
+            for k, d in got.items():
+                if k in MOBILENET_V2_SPAN and self.backbone == "mobilenet_v2":
+                    self._mn[k] = dict({"kernel": d["kernel"]}, **got[k + "_BN"])
+                elif "kernel" in d:
+                    (self._head if k in HEAD_LAYERS else self._backbone)[k] = (d["kernel"], d["bias"])
             L.lib().rpn_head_trainer_destroy(self._t)
             self._t = L.vp(0)
         t = L.vp(0)
@@ -305,25 +338,53 @@ class RPNModel(object):
         if train_backbone_from is not None:
             for name in self._backbone:
                 self._trainer_set(name)
+            for name in self._mn:
+                if name in self.trained_layers():
+                    self._trainer_set(name)
 
     def trained_layers(self):
-        """The layers a training step updates: the head, plus the VGG16 convs from ``train_backbone_from`` up."""
-        bb = VGG16_CONVS[VGG16_CONVS.index(self._train_from):] if self._train_from is not None else ()
-        return tuple(bb) + HEAD_LAYERS
+        """The layers a training step updates: the head, plus the backbone convs from ``train_backbone_from`` up (each
+        MobileNetV2 conv with its BatchNorm)."""
+        if self._train_from is None:
+            return HEAD_LAYERS
+        order = VGG16_CONVS if self.backbone == "vgg16" else MOBILENET_V2_SPAN
+        return tuple(order[order.index(self._train_from):]) + HEAD_LAYERS
+
+    def _is_mn(self, name):
+        return self.backbone == "mobilenet_v2" and name in MOBILENET_V2_SPAN
 
     def _trainer_set(self, name):
+        if self._is_mn(name):
+            d = self._mn[name]
+            L.check(L.lib().rpn_head_trainer_set_layer(self._t, name.encode(), d["kernel"].ctypes.data_as(L.c_float_p), None),
+                    "rpn_head_trainer_set_layer(%s)" % name)
+            L.check(L.lib().rpn_head_trainer_set_bn(self._t, name.encode(), *[d[k].ctypes.data_as(L.c_float_p) for k in BN_KEYS]),
+                    "rpn_head_trainer_set_bn(%s)" % name)
+            return
         kernel, bias = self._head[name] if name in HEAD_LAYERS else self._backbone[name]
         L.check(L.lib().rpn_head_trainer_set_layer(self._t, name.encode(), kernel.ctypes.data_as(L.c_float_p),
                                                    bias.ctypes.data_as(L.c_float_p)), "rpn_head_trainer_set_layer(%s)" % name)
 
     def get_gradients(self):
-        """{layer: {"kernel", "bias"}}: the gradient of the total loss at the last ``train_on_batch`` (test hook)."""
+        """{layer: {"kernel", "bias"}}: the gradient of the total loss at the last ``train_on_batch`` (test hook).  A trained
+        MobileNetV2 conv gives {conv: {"kernel"}} and {conv_BN: {"gamma", "beta"}}."""
         if not self._t:
             raise RuntimeError("call compile() first")
         out = {}
         trained = self.trained_layers()
+        fpp = lambda a: a.ctypes.data_as(L.c_float_p)
         for layer in self.layers:
-            if layer["name"] in trained:
+            if layer["name"] in trained and self._is_mn(layer["name"]):
+                name, C = layer["name"], layer["shape"][2] if layer["kind"] == 2 else layer["shape"][3]
+                kernel = np.empty(layer["shape"], dtype=np.float32)
+                dg, db = np.empty((C,), np.float32), np.empty((C,), np.float32)
+                L.check(L.lib().rpn_head_trainer_get_gradient(self._t, name.encode(), fpp(kernel), None, L.stream_ptr()),
+                        "rpn_head_trainer_get_gradient")
+                L.check(L.lib().rpn_head_trainer_get_bn_gradient(self._t, name.encode(), fpp(dg), fpp(db), L.stream_ptr()),
+                        "rpn_head_trainer_get_bn_gradient")
+                out[name] = {"kernel": kernel}
+                out[layer["bn_name"]] = {"gamma": dg, "beta": db}
+            elif layer["name"] in trained:
                 kernel = np.empty(layer["shape"], dtype=np.float32)
                 bias = np.empty((layer["shape"][3],), dtype=np.float32)
                 L.check(L.lib().rpn_head_trainer_get_gradient(self._t, layer["name"].encode(), kernel.ctypes.data_as(L.c_float_p),
@@ -335,12 +396,32 @@ class RPNModel(object):
     def get_weights(self):
         """{layer: {"kernel": HWIO, "bias"}} of the trained layers -- the three head layers, plus the VGG16 convs from
         ``train_backbone_from`` up when compiled so (the trained values once a step has run): what ``save_weights`` writes and
-        ``set_weights`` / ``load_weights`` read back."""
+        ``set_weights`` / ``load_weights`` read back.  A trained MobileNetV2 conv gives {conv: {"kernel"}} and {conv_BN: {"gamma",
+        "beta", "mean", "var"}} (unfolded; mean / var are the moving statistics)."""
         out = {}
         trained = self.trained_layers()
+        stream = L.stream_ptr() if torch.cuda.is_available() else None
+        fpp = lambda a: a.ctypes.data_as(L.c_float_p)
         for layer in self.layers:
             name = layer["name"]
             if name not in trained:
+                continue
+            if self._is_mn(name):
+                if self._t:
+                    C = layer["shape"][2] if layer["kind"] == 2 else layer["shape"][3]
+                    kernel = np.empty(layer["shape"], dtype=np.float32)
+                    bn = {k: np.empty((C,), np.float32) for k in BN_KEYS}
+                    L.check(L.lib().rpn_head_trainer_get_layer(self._t, name.encode(), fpp(kernel), None, stream),
+                            "rpn_head_trainer_get_layer(%s)" % name)
+                    L.check(L.lib().rpn_head_trainer_get_bn(self._t, name.encode(), *([fpp(bn[k]) for k in BN_KEYS] + [stream])),
+                            "rpn_head_trainer_get_bn(%s)" % name)
+                elif name in self._mn:
+                    kernel = self._mn[name]["kernel"].copy()
+                    bn = {k: self._mn[name][k].copy() for k in BN_KEYS}
+                else:
+                    continue
+                out[name] = {"kernel": kernel}
+                out[layer["bn_name"]] = bn
                 continue
             if self._t:
                 kernel = np.empty(layer["shape"], dtype=np.float32)
@@ -364,7 +445,15 @@ class RPNModel(object):
         if not self._head_dirty:
             return
         lib = L.lib()
-        for name, d in self.get_weights().items():
+        got = self.get_weights()
+        for name, d in got.items():
+            if "kernel" not in d:           # a BatchNorm entry: goes with its conv
+                continue
+            if self._is_mn(name):           # refolded from kernel + gamma / beta / the updated moving statistics
+                bn = [got[name + "_BN"][k].ctypes.data_as(L.c_float_p) for k in BN_KEYS]
+                L.check(lib.rpn_model_set_layer(self._h, name.encode(), d["kernel"].ctypes.data_as(L.c_float_p), None, *bn),
+                        "rpn_model_set_layer(%s)" % name)
+                continue
             L.check(lib.rpn_model_set_layer(self._h, name.encode(), d["kernel"].ctypes.data_as(L.c_float_p),
                                             d["bias"].ctypes.data_as(L.c_float_p), None, None, None, None),
                     "rpn_model_set_layer(%s)" % name)
