@@ -324,6 +324,12 @@ int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, in
  * get_gradient take bias = NULL for them, and the three calls below carry the BatchNorm of a trained conv, named by the conv or by
  * its BatchNorm layer ("<conv>_BN"): HOST arrays of Cout floats; every trained conv and BatchNorm must be set before a step. */
 int rpn_model_trainer_create(rpn_model *m, const char *train_from, rpn_head_trainer **out);
+/* the trainer that trains EVERY layer of the model, as the reference's trainer.py does (its Keras base model is trainable).  VGG16:
+ * rpn_model_trainer_create(m, "block1_conv1", out).  MobileNetV2: all 40 convs -- Conv1 (BatchNorm "bn_Conv1"), expanded_conv_depthwise,
+ * expanded_conv_project, block_1_expand .. block_12_project, block_13_expand -- each with its BatchNorm, and the head; there is no frozen
+ * prefix (the span's input is the image batch), every layer runs at its own resolution in exact float32 as described above, and
+ * set_layer / set_bn / get_* take all 40 names.  rpn_model_trainer_create keeps refusing names below block_7_expand. */
+int rpn_model_trainer_create_full(rpn_model *m, rpn_head_trainer **out);
 int rpn_head_trainer_set_bn(rpn_head_trainer *t, const char *name, const float *gamma, const float *beta, const float *mean,
                             const float *var);
 int rpn_head_trainer_get_bn(rpn_head_trainer *t, const char *name, float *gamma, float *beta, float *mean, float *var, void *stream);
@@ -361,6 +367,25 @@ int rpn_dwconv3x3_dgrad(const float *d_dy, const float *d_w, int B, int H, int W
 size_t rpn_dwconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C);
 int rpn_dwconv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws, size_t ws_bytes,
                         void *stream);
+
+/* backward of MobileNetV2's stride-2 layers, single-layer entries (same conventions: float32, each output written once, no atomics,
+ * fixed trees, C % 4 == 0, 16-byte aligned pointers).  The padding is Keras' ZeroPadding2D(correct_pad(3)) followed by a 'valid'
+ * stride-2 conv, per spatial dim of n input pixels: before = n % 2 (even side 0, odd side 1), after = 1, out = (n + before + 1 - 3) /
+ * 2 + 1; pt / pl are `before` of H / W, OH / OW the two output sides.
+ * rpn_dwconv3x3_s2_dgrad: d_dy (B,OH,OW,C), d_w (3,3,C) -> d_dx (B,H,W,C): dx[b][y][x][c] = sum_{r,s} dy[b][(y+pt-r)/2][(x+pl-s)/2][c]
+ *   w[r][s][c] over the taps where both quotients are exact and in range; every element is written (zeros where no output reads).
+ * rpn_dwconv3x3_s2_wgrad: d_x (B,H,W,C), d_dy (B,OH,OW,C) -> d_dw (3,3,C): dw[r][s][c] = sum_{b,oy,ox} x[b][2oy+r-pt][2ox+s-pl][c]
+ *   dy[b][oy][ox][c].  d_ws: rpn_dwconv3x3_s2_wgrad_workspace_bytes(B, H, W, C) (the INPUT's shape).
+ * rpn_conv3x3_s2_cin3_wgrad: the stem (Conv1), d_x (B,H,W,3) the image batch, d_dy (B,OH,OW,Cout) -> d_dw (3,3,3,Cout): dw[r][s][ci][co] =
+ *   sum_{b,oy,ox} x[b][2oy+r-pt][2ox+s-pl][ci] dy[b][oy][ox][co]; the pixels in up to 256 fixed ranges added in a fixed two-level tree.
+ *   d_ws: rpn_conv3x3_s2_cin3_wgrad_workspace_bytes(B, H, W, Cout).  (The stem needs no data gradient.) */
+int rpn_dwconv3x3_s2_dgrad(const float *d_dy, const float *d_w, int B, int H, int W, int C, float *d_dx, void *stream);
+size_t rpn_dwconv3x3_s2_wgrad_workspace_bytes(int B, int H, int W, int C);
+int rpn_dwconv3x3_s2_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws, size_t ws_bytes,
+                           void *stream);
+size_t rpn_conv3x3_s2_cin3_wgrad_workspace_bytes(int B, int H, int W, int Cout);
+int rpn_conv3x3_s2_cin3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int Cout, float *d_dw, void *d_ws,
+                              size_t ws_bytes, void *stream);
 
 /* backward of the VGG16 backbone, single-layer entries (float32; no floating-point atomics: bit-identical from run to run)
  * rpn_conv3x3_dgrad: input gradient of a 3x3 stride-1 'same' conv, d_dx (B,H,W,Cin) = conv_transpose(d_dy (B,H,W,Cout), d_w HWIO),

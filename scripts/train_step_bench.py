@@ -3,6 +3,7 @@
     python scripts/train_step_bench.py [--batch 8] [--steps 20] [--warmup 3]
     python scripts/train_step_bench.py --train-backbone-from block1_conv1 [--batch 8] [--steps 20] [--warmup 3]
     python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone-from block_7_expand [--batch 8] ...
+    python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone [--batch 8] ...     (the whole model; also vgg16)
 
 Times on the device with HIP events around (a) a whole training step (backbone at the handle's precision + float32 head forward,
 losses, backward, Adam), (b) an evaluation step (no backward), (c) the 3x3 weight-gradient entry rpn_conv3x3_wgrad on the
@@ -14,6 +15,11 @@ With --train-backbone-from LAYER (VGG16 only): (a) and (b) for the trainer that 
 against the float32-MFMA peak, and per trained conv the single-layer entries rpn_conv3x3_dgrad (with its mask) and
 rpn_conv3x3_wgrad_wide on that layer's shape, timed with HIP events.  A rocprofv3 --kernel-trace --stats run of the same command
 gives the per-kernel totals.
+
+With --train-backbone: compile(train_backbone=True), every layer of the backbone trains.  VGG16: the block1_conv1 report.  MobileNetV2:
+(a) and (b) for the whole-model trainer, the device memory the trainer allocated at its first step, and the three stride-2 kernels'
+single-layer entries on their largest layers (block_1_depthwise: 250 x 250 x 96 in, 125 x 125 out; Conv1: 500 x 500 x 3 in, 250 x
+250 x 32 out) with the bytes each must move and its rate.
 """
 import argparse
 import json
@@ -214,6 +220,45 @@ def bench_mobilenet_span(train_from, precision, B, steps, warmup):
             "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "block_12_shape": [P, Cs, C], "kernels": kernels}
 
 
+def bench_mobilenet_full(precision, B, steps, warmup):
+    hp = train_utils.get_hyper_params("mobilenet_v2")
+    model, _ = rpn_mobilenet_v2.get_model(hp, precision=precision, max_batch=B)
+    imgs, deltas, lab = step_inputs(model, hp, B)
+    model.compile(learning_rate=1e-5, train_backbone=True)
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
+    trainer_bytes = free0 - torch.cuda.mem_get_info()[0]               # the trainer allocates at its first step
+    lib = L.lib()
+    s = L.stream_ptr
+    img = hp["img_size"]
+    H1 = (img + img % 2 + 1 - 3) // 2 + 1                               # Conv1's output side = block_1_depthwise's input side
+    H2 = (H1 + H1 % 2 + 1 - 3) // 2 + 1
+    C = 96
+    x, dy = torch.randn((B, H1, H1, C), device="cuda"), torch.randn((B, H2, H2, C), device="cuda")
+    dx, wd, dwd = torch.empty_like(x), torch.randn((3, 3, C), device="cuda"), torch.empty((3, 3, C), device="cuda")
+    xi, dys, dws = imgs, torch.randn((B, H1, H1, 32), device="cuda"), torch.empty((3, 3, 3, 32), device="cuda")
+    nd = lib.rpn_dwconv3x3_s2_wgrad_workspace_bytes(B, H1, H1, C)
+    ns = lib.rpn_conv3x3_s2_cin3_wgrad_workspace_bytes(B, img, img, 32)
+    ws = torch.empty(max(nd, ns), dtype=torch.uint8, device="cuda")
+    calls = {
+        "dwconv3x3_s2_dgrad": (lambda: lib.rpn_dwconv3x3_s2_dgrad(L.ptr(dy), L.ptr(wd), B, H1, H1, C, L.ptr(dx), s()),
+                               4.0 * (dy.numel() + dx.numel())),            # dy read, dx written
+        "dwconv3x3_s2_wgrad": (lambda: lib.rpn_dwconv3x3_s2_wgrad(L.ptr(x), L.ptr(dy), B, H1, H1, C, L.ptr(dwd), L.ptr(ws), nd, s()),
+                               4.0 * (x.numel() + dy.numel())),             # x, dy read
+        "conv3x3_s2_cin3_wgrad": (lambda: lib.rpn_conv3x3_s2_cin3_wgrad(L.ptr(xi), L.ptr(dys), B, img, img, 32, L.ptr(dws), L.ptr(ws), ns, s()),
+                                  4.0 * (xi.numel() + dys.numel())),        # the images, dy read
+    }
+    kernels = {}
+    for name, (fn, nbytes) in calls.items():
+        def run(fn=fn, name=name):
+            L.check(fn(), name)
+        ms = timed(run, steps, warmup)
+        kernels[name] = {"ms": round(ms, 4), "mbytes": round(nbytes / 1e6, 1), "tb_per_s": round(nbytes / ms / 1e9, 3)}
+    return {"backbone": "mobilenet_v2", "train_backbone": True, "precision": precision, "batch": B, "ms_train_step": round(ms_train, 3),
+            "ms_eval_step": round(ms_eval, 3), "trainer_device_gb": round(trainer_bytes / 1e9, 3), "kernels": kernels}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -225,8 +270,18 @@ def main():
                          "and the layers above")
     ap.add_argument("--backbone", default=None, choices=("vgg16", "mobilenet_v2"),
                     help="with --train-backbone-from: the backbone (default vgg16); without: time that backbone's head-only step alone")
+    ap.add_argument("--train-backbone", action="store_true",
+                    help="time the trainer of compile(train_backbone=True): every layer of --backbone (default vgg16) trains")
     args = ap.parse_args()
     L.require_gpu()
+    if args.train_backbone:
+        if args.train_backbone_from:
+            ap.error("--train-backbone trains every layer: it cannot be combined with --train-backbone-from")
+        if args.backbone == "mobilenet_v2":
+            print(json.dumps(bench_mobilenet_full(args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        else:
+            print(json.dumps(bench_backbone("block1_conv1", args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        return
     if args.train_backbone_from and args.backbone == "mobilenet_v2":
         print(json.dumps(bench_mobilenet_span(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup)), flush=True)
         return

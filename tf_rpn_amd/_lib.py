@@ -96,6 +96,12 @@ _SIGNATURES = {
     "rpn_dwconv3x3_dgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_dwconv3x3_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "rpn_dwconv3x3_wgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, ctypes.c_size_t, vp]),
+    "rpn_model_trainer_create_full": (ctypes.c_int, [vp, ctypes.POINTER(vp)]),
+    "rpn_dwconv3x3_s2_dgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
+    "rpn_dwconv3x3_s2_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "rpn_dwconv3x3_s2_wgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, ctypes.c_size_t, vp]),
+    "rpn_conv3x3_s2_cin3_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "rpn_conv3x3_s2_cin3_wgrad": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, ctypes.c_size_t, vp]),
     "rpn_conv3x3_dgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
     "rpn_conv3x3_dgrad_tile_n": (ctypes.c_int, [ctypes.c_int] * 4),
     "rpn_conv3x3_dgrad": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, ctypes.c_size_t, vp]),

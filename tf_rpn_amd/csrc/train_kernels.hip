@@ -491,6 +491,7 @@ extern "C" int rpn_conv3x3_wgrad(const float *d_x, const float *d_dy, int B, int
 }
 
 // ---- C ABI: the head trainer -------------------------------------------------------------------------------------------------
+constexpr int kMnMax = 40;                      // MobileNetV2's convs up to block_13_expand (mn_table())
 struct rpn_head_trainer {
     rpn_model *m = nullptr;
     int cin = 0, F = 0, K = 0, max_batch = 0, nc = 0;
@@ -518,19 +519,21 @@ struct rpn_head_trainer {
     PackedShape ps_bb[13]{};
     float *d_frozen = nullptr, *d_pack = nullptr, *d_wt = nullptr, *d_wpart = nullptr, *d_img4 = nullptr;
     float *d_act[13] = {}, *d_pool[13] = {}, *d_ping[2] = {}, *d_grad[2] = {};
-    // ---- MobileNetV2's stride-16 span (rpn_model_trainer_create on a MobileNetV2 handle; mn_*) ----
-    // mn_from: the first trained layer (index into mn_table(), an expand conv), -1: none.  A trained layer's kernel, gamma and beta
-    // follow the head in the flat buffers (off_mk / off_mg / off_mb); its moving mean | variance are state outside Adam's buffer
-    // (host_bn / d_bn at off_ms); d_bstat holds the statistics a step normalised with (mean | var | rstd at off_bs).
+    // ---- MobileNetV2 (rpn_model_trainer_create / _create_full on a MobileNetV2 handle; mn_*) ----
+    // mn_from: the first trained layer (index into mn_table(): an expand conv of the stride-16 span, or 0 = Conv1: the whole model),
+    // -1: none.  A trained layer's kernel, gamma and beta follow the head in the flat buffers (off_mk / off_mg / off_mb); its moving
+    // mean | variance are state outside Adam's buffer (host_bn / d_bn at off_ms); d_bstat holds the statistics a step normalised with
+    // (mean | var | rstd at off_bs).  mn_hin / mn_hout: the spatial side of each layer's input and output.
     int mn_from = -1;
-    std::string mn_x0;                           // the handle's tensor below the span: the frozen prefix ends there
-    size_t off_mk[19] = {}, off_mg[19] = {}, off_mb[19] = {}, off_ms[19] = {}, off_bs[19] = {};
-    bool mn_loaded[19] = {}, mn_bn_loaded[19] = {};
+    std::string mn_x0;                           // the handle's tensor below the span: the frozen prefix ends there (none from Conv1)
+    int mn_hin[kMnMax] = {}, mn_hout[kMnMax] = {};
+    size_t off_mk[kMnMax] = {}, off_mg[kMnMax] = {}, off_mb[kMnMax] = {}, off_ms[kMnMax] = {}, off_bs[kMnMax] = {};
+    bool mn_loaded[kMnMax] = {}, mn_bn_loaded[kMnMax] = {};
     std::vector<float> host_bn;
-    PackedShape ps_mn[19]{};
+    PackedShape ps_mn[kMnMax]{};
     float *d_bn = nullptr, *d_bstat = nullptr, *d_x0 = nullptr, *d_mpack = nullptr, *d_mwpart = nullptr;
     double *d_mpart = nullptr;
-    float *d_mz[19] = {}, *d_my[19] = {}, *d_mgr[2] = {}, *d_mt[3] = {};
+    float *d_mz[kMnMax] = {}, *d_my[kMnMax] = {}, *d_mgr[2] = {}, *d_mt[3] = {};
 };
 
 namespace {
@@ -611,75 +614,103 @@ int backbone_device(rpn_head_trainer *t)
     return RPN_OK;
 }
 
-// ---- MobileNetV2: the inverted-residual blocks at the feature map's own resolution ------------------------------------------------
-// kind 0: 1x1 expand + BatchNorm + ReLU6, 1: depthwise 3x3 stride 1 'same' + BatchNorm + ReLU6, 2: 1x1 project + BatchNorm (linear)
-// (+ the block's input when res).  No conv has a bias.  Keras names; the BatchNorm layer of conv X is "X_BN".
-constexpr int kMnLayers = 19;
+// ---- MobileNetV2: the stem and the inverted-residual blocks, each layer at its own resolution ---------------------------------------
+// kind 0: 1x1 expand + BatchNorm + ReLU6, 1: depthwise 3x3 + BatchNorm + ReLU6 (stride 1 'same', or stride 2 behind Keras'
+// correct_pad: mn_s2_geom), 2: 1x1 project + BatchNorm (linear) (+ the block's input when res), 3: the stem Conv1, a 3x3 stride-2
+// conv from the 3-channel image + BatchNorm + ReLU6 (same padding rule).  No conv has a bias.  Keras names; the BatchNorm layer of
+// conv X is "X_BN", Conv1's is "bn_Conv1".  expanded_conv has no expand conv.
+constexpr int kMnLayers = kMnMax;
+constexpr int kMnSpan = 21;                     // block_7_expand: the first layer at the feature map's own resolution (stride 16)
 constexpr float kMnBnEps = 1e-3f, kMnBnMomentum = 0.999f;      // keras.applications.MobileNetV2
 struct MnConv {
-    std::string name;
-    int kind, cin, cout;
+    std::string name, bn;
+    int kind, cin, cout, stride;
     bool res;
 };
 const std::vector<MnConv> &mn_table()
 {
     static const std::vector<MnConv> tab = [] {
         std::vector<MnConv> v;
-        const int cin[6] = {64, 64, 64, 64, 96, 96}, cout[6] = {64, 64, 64, 96, 96, 96};
-        for (int b = 0; b < 6; ++b) {
-            const std::string pre = "block_" + std::to_string(b + 7) + "_";
-            v.push_back({pre + "expand", 0, cin[b], 6 * cin[b], false});
-            v.push_back({pre + "depthwise", 1, 6 * cin[b], 6 * cin[b], false});
-            v.push_back({pre + "project", 2, 6 * cin[b], cout[b], cin[b] == cout[b]});
+        // (cin, cout, stride) of block_1 .. block_12 (keras.applications.MobileNetV2, alpha 1; expansion 6)
+        const int blk[12][3] = {{16, 24, 2}, {24, 24, 1}, {24, 32, 2}, {32, 32, 1}, {32, 32, 1}, {32, 64, 2},
+                                {64, 64, 1}, {64, 64, 1}, {64, 64, 1}, {64, 96, 1}, {96, 96, 1}, {96, 96, 1}};
+        v.push_back({"Conv1", "bn_Conv1", 3, 3, 32, 2, false});
+        v.push_back({"expanded_conv_depthwise", "expanded_conv_depthwise_BN", 1, 32, 32, 1, false});
+        v.push_back({"expanded_conv_project", "expanded_conv_project_BN", 2, 32, 16, 1, false});
+        for (int b = 0; b < 12; ++b) {
+            const std::string pre = "block_" + std::to_string(b + 1) + "_";
+            const int cin = blk[b][0], cout = blk[b][1], stride = blk[b][2];
+            v.push_back({pre + "expand", pre + "expand_BN", 0, cin, 6 * cin, 1, false});
+            v.push_back({pre + "depthwise", pre + "depthwise_BN", 1, 6 * cin, 6 * cin, stride, false});
+            v.push_back({pre + "project", pre + "project_BN", 2, 6 * cin, cout, 1, cin == cout && stride == 1});
         }
-        v.push_back({"block_13_expand", 0, 96, 576, false});
+        v.push_back({"block_13_expand", "block_13_expand_BN", 0, 96, 576, 1, false});
         return v;
     }();
     return tab;
 }
 
-// index of conv `name`, or of the conv whose BatchNorm layer is `name` (with_bn)
+// index of conv `name`, or of the conv whose BatchNorm layer is `name` (with_bn: "<conv>_BN" or the layer's Keras name)
 int mn_index(const char *name, bool with_bn = false)
 {
     const std::vector<MnConv> &tab = mn_table();
     for (int i = 0; i < kMnLayers; ++i)
-        if (tab[i].name == name || (with_bn && tab[i].name + "_BN" == name)) return i;
+        if (tab[i].name == name || (with_bn && (tab[i].name + "_BN" == name || tab[i].bn == name))) return i;
     return -1;
 }
 
 size_t mn_kernel_floats(int i)
 {
     const MnConv &l = mn_table()[i];
-    return l.kind == 1 ? (size_t)9 * l.cout : (size_t)l.cin * l.cout;
+    return l.kind == 1 ? (size_t)9 * l.cout : (l.kind == 3 ? (size_t)27 * l.cout : (size_t)l.cin * l.cout);
 }
+
+// pixels per image of layer i's input / output
+size_t mn_pin(const rpn_head_trainer *t, int i) { return (size_t)t->mn_hin[i] * t->mn_hin[i]; }
+size_t mn_pout(const rpn_head_trainer *t, int i) { return (size_t)t->mn_hout[i] * t->mn_hout[i]; }
 
 // the span's buffers, sized by max_batch and the trained layers: per trained conv its output z (kept for the BatchNorm backward)
 // and the normalised, activated tensor y (the next layer's input; the last one is d_feat)
+// Every per-layer buffer is sized by that layer's own pixel count; the gradient buffers by the largest tensor they carry (mn_backward):
+// d_mgr the block inputs, d_mt[0] the project outputs, d_mt[1 / 2] the expanded tensors (block_1_expand's 250 x 250 x 96 per image at
+// 500 x 500) -- never less than the stride-16 span needs (F x F x 96 / 576: rpn_conv's input gradient lands in d_mt[1]).
 int mn_device(rpn_head_trainer *t)
 {
     const std::vector<MnConv> &tab = mn_table();
-    const size_t P = (size_t)t->max_batch * t->F * t->F;
-    size_t pack = 0, wpart = 0, bstat = 0;
+    const size_t B = (size_t)t->max_batch, PF = B * t->F * t->F;
+    size_t pack = 0, wpart = 0, bstat = 0, part = bn_part_doubles((long long)PF, 576), gr = PF * 96, t0 = PF * 96, t12 = PF * 576;
     for (int i = t->mn_from; i < kMnLayers; ++i) {
         const MnConv &l = tab[i];
-        if (l.kind != 1) pack = std::max(pack, t->ps_mn[i].floats());
-        wpart = std::max(wpart, l.kind == 1 ? dwconv3x3_wgrad_ws_floats((long long)P, l.cout) : conv1x1_wgrad_ws_floats((long long)P, l.cin, l.cout));
+        const size_t Pi = B * mn_pin(t, i), Po = B * mn_pout(t, i);
+        if (l.kind == 0 || l.kind == 2) pack = std::max(pack, t->ps_mn[i].floats());
+        if (l.kind == 1)
+            wpart = std::max(wpart, l.stride == 2 ? dwconv3x3_s2_wgrad_ws_floats((int)B, t->mn_hin[i], t->mn_hin[i], l.cout)
+                                                  : dwconv3x3_wgrad_ws_floats((long long)Po, l.cout));
+        else if (l.kind == 3)
+            wpart = std::max(wpart, conv3x3_s2_cin3_wgrad_ws_floats((int)B, t->mn_hin[i], t->mn_hin[i], l.cout));
+        else
+            wpart = std::max(wpart, conv1x1_wgrad_ws_floats((long long)Po, l.cin, l.cout));
+        part = std::max(part, bn_part_doubles((long long)Po, l.cout));
+        if (l.kind == 0) gr = std::max(gr, Pi * l.cin);
+        if (l.kind == 2) t0 = std::max(t0, Po * l.cout);
+        if (l.kind != 3) t12 = std::max(t12, std::max(Pi * l.cin, l.kind == 2 ? (size_t)0 : Po * l.cout));
+        else t12 = std::max(t12, Po * l.cout);
         bstat = t->off_bs[i] + (size_t)3 * l.cout;
-        RPN_HIP_CHECK(hipMalloc(&t->d_mz[i], P * l.cout * sizeof(float)));
-        if (i < kMnLayers - 1) RPN_HIP_CHECK(hipMalloc(&t->d_my[i], P * l.cout * sizeof(float)));
+        RPN_HIP_CHECK(hipMalloc(&t->d_mz[i], Po * l.cout * sizeof(float)));
+        if (i < kMnLayers - 1) RPN_HIP_CHECK(hipMalloc(&t->d_my[i], Po * l.cout * sizeof(float)));
     }
-    RPN_HIP_CHECK(hipMalloc(&t->d_x0, P * tab[t->mn_from].cin * sizeof(float)));
+    if (t->mn_from > 0) RPN_HIP_CHECK(hipMalloc(&t->d_x0, PF * tab[t->mn_from].cin * sizeof(float)));
     RPN_HIP_CHECK(hipMalloc(&t->d_mpack, std::max<size_t>(1, pack) * sizeof(float)));
     RPN_HIP_CHECK(hipMalloc(&t->d_mwpart, std::max<size_t>(1, wpart) * sizeof(float)));
-    RPN_HIP_CHECK(hipMalloc(&t->d_mpart, bn_part_doubles((long long)P, 576) * sizeof(double)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mpart, part * sizeof(double)));
     RPN_HIP_CHECK(hipMalloc(&t->d_bstat, bstat * sizeof(float)));
     RPN_HIP_CHECK(hipMalloc(&t->d_bn, t->host_bn.size() * sizeof(float)));
     RPN_HIP_CHECK(hipMemcpy(t->d_bn, t->host_bn.data(), t->host_bn.size() * sizeof(float), hipMemcpyHostToDevice));
     RPN_HIP_CHECK(hipMalloc(&t->d_wt, (size_t)9 * 512 * 576 * sizeof(float)));
-    for (int u = 0; u < 2; ++u) RPN_HIP_CHECK(hipMalloc(&t->d_mgr[u], P * 96 * sizeof(float)));
-    RPN_HIP_CHECK(hipMalloc(&t->d_mt[0], P * 96 * sizeof(float)));
-    RPN_HIP_CHECK(hipMalloc(&t->d_mt[1], P * 576 * sizeof(float)));
-    RPN_HIP_CHECK(hipMalloc(&t->d_mt[2], P * 576 * sizeof(float)));
+    for (int u = 0; u < 2; ++u) RPN_HIP_CHECK(hipMalloc(&t->d_mgr[u], gr * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mt[0], t0 * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mt[1], t12 * sizeof(float)));
+    RPN_HIP_CHECK(hipMalloc(&t->d_mt[2], t12 * sizeof(float)));
     return RPN_OK;
 }
 
@@ -690,9 +721,9 @@ void trainer_free(rpn_head_trainer *t)
     for (float *p : mn)
         if (p) (void)hipFree(p);
     if (t->d_mpart) (void)hipFree(t->d_mpart);
-    for (int i = 0; i < 19; ++i) {
+    for (int i = 0; i < kMnLayers; ++i) {
         if (t->d_mz[i]) (void)hipFree(t->d_mz[i]);
-        if (t->d_my[i] && i < 18) (void)hipFree(t->d_my[i]);           // (the last one is d_feat)
+        if (t->d_my[i] && i < kMnLayers - 1) (void)hipFree(t->d_my[i]);           // (the last one is d_feat)
         t->d_mz[i] = t->d_my[i] = nullptr;
     }
     t->d_bn = t->d_bstat = t->d_x0 = t->d_mpack = t->d_mwpart = t->d_mgr[0] = t->d_mgr[1] = t->d_mt[0] = t->d_mt[1] = t->d_mt[2] = nullptr;
@@ -821,23 +852,29 @@ hipError_t backbone_backward(rpn_head_trainer *t, int B, hipStream_t s)
 }
 
 // The span's forward in exact float32 from the trainer's unfolded parameters, on top of the frozen prefix (the handle's ops up to
-// mn_x0).  train: BatchNorm normalises with the batch statistics and updates the moving ones; else with the moving statistics
-// (inference mode, nothing updated).  Every conv output z and every layer output y is kept.  -> the block_13_expand output in d_feat.
+// mn_x0; from Conv1 there is none: the span's input is the image batch).  train: BatchNorm normalises with the batch statistics and
+// updates the moving ones; else with the moving statistics (inference mode, nothing updated).  Every conv output z and every layer
+// output y is kept.  -> the block_13_expand output in d_feat.
 int mn_forward(rpn_head_trainer *t, const float *d_imgs, int B, bool train, hipStream_t s)
 {
     const std::vector<MnConv> &tab = mn_table();
-    const int F = t->F;
-    const long long P = (long long)B * F * F;
-    const int e0 = model_features_at(t->m, t->mn_x0.c_str(), d_imgs, B, t->d_x0, s);
-    if (e0 != RPN_OK) return e0;
+    if (t->mn_from > 0) {
+        const int e0 = model_features_at(t->m, t->mn_x0.c_str(), d_imgs, B, t->d_x0, s);
+        if (e0 != RPN_OK) return e0;
+    }
     t->d_my[kMnLayers - 1] = t->d_feat;
     for (int i = t->mn_from; i < kMnLayers; ++i) {
         const MnConv &l = tab[i];
-        const float *in = i == t->mn_from ? t->d_x0 : t->d_my[i - 1];
+        const int H = t->mn_hin[i], F = t->mn_hout[i];
+        const long long P = (long long)B * F * F;
+        const float *in = i == t->mn_from ? (i == 0 ? d_imgs : t->d_x0) : t->d_my[i - 1];
         const float *w = t->d_w + t->off_mk[i];
         hipError_t e;
         if (l.kind == 1) {
-            e = launch_dwconv3x3(in, B, F, F, l.cout, w, nullptr, 1, 1, 1, F, F, ACT_LINEAR, t->d_mz[i], s);
+            const int pad = l.stride == 2 ? H % 2 : 1;
+            e = launch_dwconv3x3(in, B, H, H, l.cout, w, nullptr, l.stride, pad, pad, F, F, ACT_LINEAR, t->d_mz[i], s);
+        } else if (l.kind == 3) {
+            e = launch_conv_cin3(in, w, nullptr, t->d_mz[i], B, H, H, F, F, l.cout, 2, H % 2, H % 2, ACT_LINEAR, 0, false, s);
         } else {
             pack_weights_device(t->ps_mn[i], w, t->d_mpack, s);
             ConvArgs a{};
@@ -869,18 +906,18 @@ int mn_forward(rpn_head_trainer *t, const float *d_imgs, int B, bool train, hipS
 // From dS (rpn_conv's pre-activation gradient) down to the first trained layer.  g: the gradient of the current layer's output.  A
 // residual block's output gradient stays in d_mgr[a] until the block's expand dgrad adds it to what that conv sends to the block's
 // input (the dgrad's epilogue: no atomics, no extra pass).
-hipError_t mn_backward(rpn_head_trainer *t, int B, hipStream_t s)
+hipError_t mn_backward(rpn_head_trainer *t, const float *d_imgs, int B, hipStream_t s)
 {
     const std::vector<MnConv> &tab = mn_table();
-    const int F = t->F;
-    const long long P = (long long)B * F * F;
     float *g = t->d_mt[1];
     const float *gres = nullptr;
     int a = 1;
-    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, nullptr, B, F, F, t->cin, 512, t->d_wt, g, s);
+    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, nullptr, B, t->F, t->F, t->cin, 512, t->d_wt, g, s);
     for (int i = kMnLayers - 1; i >= t->mn_from && e == hipSuccess; --i) {
         const MnConv &l = tab[i];
-        const float *in = i == t->mn_from ? t->d_x0 : t->d_my[i - 1];
+        const int H = t->mn_hin[i], F = t->mn_hout[i];
+        const long long P = (long long)B * F * F;
+        const float *in = i == t->mn_from ? (i == 0 ? d_imgs : t->d_x0) : t->d_my[i - 1];
         const float *w = t->d_w + t->off_mk[i];
         const float *mean = t->d_bstat + t->off_bs[i], *rstd = mean + 2 * l.cout;
         float *dz = g;
@@ -891,10 +928,19 @@ hipError_t mn_backward(rpn_head_trainer *t, int B, hipStream_t s)
         e = launch_bn_backward(t->d_mz[i], g, P, l.cout, mean, rstd, t->d_w + t->off_mg[i], t->d_w + t->off_mb[i], l.kind != 2, t->d_mpart,
                                t->d_g + t->off_mg[i], t->d_g + t->off_mb[i], dz, s);
         if (e != hipSuccess) break;
+        if (l.kind == 3) {                      // the stem: its input is the image, so there is no data gradient
+            e = launch_conv3x3_s2_cin3_wgrad(in, dz, B, H, H, l.cout, t->d_mwpart, t->d_g + t->off_mk[i], s);
+            break;
+        }
         if (l.kind == 1) {
-            e = launch_dwconv3x3_wgrad(in, dz, B, F, F, l.cout, t->d_mwpart, t->d_g + t->off_mk[i], s);
             float *dx = dz == t->d_mt[1] ? t->d_mt[2] : t->d_mt[1];
-            if (e == hipSuccess) e = launch_dwconv3x3_dgrad(dz, w, B, F, F, l.cout, dx, s);
+            if (l.stride == 2) {
+                e = launch_dwconv3x3_s2_wgrad(in, dz, B, H, H, l.cout, t->d_mwpart, t->d_g + t->off_mk[i], s);
+                if (e == hipSuccess) e = launch_dwconv3x3_s2_dgrad(dz, w, B, H, H, l.cout, dx, s);
+            } else {
+                e = launch_dwconv3x3_wgrad(in, dz, B, F, F, l.cout, t->d_mwpart, t->d_g + t->off_mk[i], s);
+                if (e == hipSuccess) e = launch_dwconv3x3_dgrad(dz, w, B, F, F, l.cout, dx, s);
+            }
             g = dx;
             continue;
         }
@@ -936,6 +982,63 @@ extern "C" int rpn_head_trainer_create(rpn_model *m, rpn_head_trainer **out)
     return RPN_OK;
 }
 
+// the MobileNetV2 trainer from layer `from` of mn_table() up: an expand conv of the stride-16 span, or 0 (Conv1: the whole model)
+static int mn_trainer_create(rpn_model *m, int from, int img, const char *what, rpn_head_trainer **out)
+{
+    const std::vector<MnConv> &tab = mn_table();
+    rpn_head_trainer *t = nullptr;
+    const int st = rpn_head_trainer_create(m, &t);
+    if (st != RPN_OK) return st;
+    for (int i = 0, h = img; i < kMnLayers; ++i) {          // each layer's own resolution, from the image down
+        t->mn_hin[i] = h;
+        if (tab[i].stride == 2) {
+            int pad;
+            mn_s2_geom(h, &pad, &h);
+        }
+        t->mn_hout[i] = h;
+    }
+    bool ok = t->cin == 576 && t->mn_hout[kMnLayers - 1] == t->F && t->F >= 1;
+    if (from > 0) {
+        t->mn_x0 = tab[from - 1].name;
+        int h = 0, w = 0, c = 0;
+        ok = ok && model_tensor_shape(m, t->mn_x0.c_str(), &h, &w, &c) == RPN_OK && h == t->F && w == t->F && c == tab[from].cin;
+    } else {
+        ok = ok && (long long)t->max_batch * t->mn_hout[0] * t->mn_hout[0] <= (1ll << 21);       // the 1x1 GEMMs' row count (gemm_ok)
+    }
+    if (!ok) {
+        rpn_head_trainer_destroy(t);
+        return fail(RPN_ERR_UNSUPPORTED, "%s: unexpected MobileNetV2 graph below '%s'", what, tab[from].name.c_str());
+    }
+    t->img = img;
+    t->mn_from = from;
+    size_t state = 0, bstat = 0;
+    for (int i = from; i < kMnLayers; ++i) {
+        t->off_mk[i] = (t->n + 3) & ~(size_t)3;     // the kernels read these slices as float4 (every slice's length is a multiple of 4)
+        t->off_mg[i] = t->off_mk[i] + mn_kernel_floats(i);
+        t->off_mb[i] = t->off_mg[i] + tab[i].cout;
+        t->n = t->off_mb[i] + tab[i].cout;
+        t->off_ms[i] = state;
+        state += (size_t)2 * tab[i].cout;
+        t->off_bs[i] = bstat;
+        bstat += (size_t)3 * tab[i].cout;
+        if (tab[i].kind == 0 || tab[i].kind == 2) t->ps_mn[i] = packed_shape(1, 1, tab[i].cin, tab[i].cout);
+    }
+    t->host_w.assign(t->n, 0.0f);
+    t->host_bn.assign(state, 0.0f);
+    *out = t;
+    return RPN_OK;
+}
+
+extern "C" int rpn_model_trainer_create_full(rpn_model *m, rpn_head_trainer **out)
+{
+    RPN_REQUIRE(m && out, "rpn_model_trainer_create_full: null argument");
+    int backbone, img;
+    model_train_backbone(m, &backbone, &img);
+    if (backbone == RPN_BACKBONE_MOBILENET_V2) return mn_trainer_create(m, 0, img, "rpn_model_trainer_create_full", out);
+    RPN_REQUIRE(backbone == RPN_BACKBONE_VGG16, "rpn_model_trainer_create_full: unknown backbone %d", backbone);
+    return rpn_model_trainer_create(m, kVgg[0].name, out);
+}
+
 extern "C" int rpn_model_trainer_create(rpn_model *m, const char *train_from, rpn_head_trainer **out)
 {
     RPN_REQUIRE(m && out, "rpn_model_trainer_create: null argument");
@@ -945,37 +1048,12 @@ extern "C" int rpn_model_trainer_create(rpn_model *m, const char *train_from, rp
     if (backbone == RPN_BACKBONE_MOBILENET_V2) {
         const std::vector<MnConv> &tab = mn_table();
         const int from = mn_index(train_from);
-        RPN_REQUIRE(from >= 0 && tab[from].kind == 0,
+        RPN_REQUIRE(from >= kMnSpan && tab[from].kind == 0,
                     "rpn_model_trainer_create: '%s' does not start a trainable span of MobileNetV2: accepted are block_7_expand .. "
                     "block_12_expand and block_13_expand (that layer and every layer above it train with the head); otherwise this "
                     "backbone trains its head only -- the layer is a VGG16 conv, is not the first layer of a block, or lies below "
-                    "block_7_expand", train_from);
-        rpn_head_trainer *t = nullptr;
-        const int st = rpn_head_trainer_create(m, &t);
-        if (st != RPN_OK) return st;
-        t->mn_x0 = from == 0 ? "block_6_project" : tab[from - 1].name;
-        int h = 0, w = 0, c = 0;
-        if (t->cin != 576 || model_tensor_shape(m, t->mn_x0.c_str(), &h, &w, &c) != RPN_OK || h != t->F || w != t->F || c != tab[from].cin) {
-            rpn_head_trainer_destroy(t);
-            return fail(RPN_ERR_UNSUPPORTED, "rpn_model_trainer_create: unexpected MobileNetV2 graph below '%s'", train_from);
-        }
-        t->mn_from = from;
-        size_t state = 0, bstat = 0;
-        for (int i = from; i < kMnLayers; ++i) {
-            t->off_mk[i] = (t->n + 3) & ~(size_t)3;     // the kernels read these slices as float4 (every slice's length is a multiple of 4)
-            t->off_mg[i] = t->off_mk[i] + mn_kernel_floats(i);
-            t->off_mb[i] = t->off_mg[i] + tab[i].cout;
-            t->n = t->off_mb[i] + tab[i].cout;
-            t->off_ms[i] = state;
-            state += (size_t)2 * tab[i].cout;
-            t->off_bs[i] = bstat;
-            bstat += (size_t)3 * tab[i].cout;
-            if (tab[i].kind != 1) t->ps_mn[i] = packed_shape(1, 1, tab[i].cin, tab[i].cout);
-        }
-        t->host_w.assign(t->n, 0.0f);
-        t->host_bn.assign(state, 0.0f);
-        *out = t;
-        return RPN_OK;
+                    "block_7_expand (rpn_model_trainer_create_full trains the whole model)", train_from);
+        return mn_trainer_create(m, from, img, "rpn_model_trainer_create", out);
     }
     RPN_REQUIRE(backbone == RPN_BACKBONE_VGG16, "rpn_model_trainer_create: unknown backbone %d", backbone);
     const int from = vgg_index(train_from);
@@ -1282,7 +1360,7 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
         if (e == hipSuccess) e = launch_wgrad(feat, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
         if (e == hipSuccess) e = launch_colsum(t->d_dS, P, 512, t->d_part, t->d_g + t->off_cb, s);
         if (e == hipSuccess && t->bb_from >= 0) e = backbone_backward(t, B, s);
-        if (e == hipSuccess && t->mn_from >= 0) e = mn_backward(t, B, s);
+        if (e == hipSuccess && t->mn_from >= 0) e = mn_backward(t, d_imgs, B, s);
         if (e == hipSuccess) {
             ++t->t;
             hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)t->n)), dim3(256), 0, s, t->d_w, t->d_g, t->d_m, t->d_v, (long long)t->n,

@@ -1,5 +1,6 @@
 // train_mnv2.h -- host-side interface of the MobileNetV2 backward kernels (train_mnv2_kernels.hip; internal to librpn_hip.so):
-// training-mode BatchNorm, the 1x1 conv backward on the float32 MFMA and the depthwise 3x3 stride-1 backward.  Every kernel is
+// training-mode BatchNorm, the 1x1 conv backward on the float32 MFMA, the depthwise 3x3 backward (stride 1 and stride 2) and the
+// stem's weight gradient.  Every kernel is
 // float32 (float64 partial sums inside the BatchNorm reductions), writes each output once and uses no floating-point atomics; every
 // reduction is a fixed number of leaves, chosen from the shape alone, added in a fixed tree.
 #pragma once
@@ -48,5 +49,28 @@ hipError_t launch_dwconv3x3_dgrad(const float *dy, const float *w, int B, int H,
 // dw[r][s][c] = sum_{b,y,x} x[b][y+r-1][x+s-1][c] dy[b][y][x][c]; part: dwconv3x3_wgrad_ws_floats(...) floats
 size_t dwconv3x3_wgrad_ws_floats(long long P, int C);
 hipError_t launch_dwconv3x3_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *part, float *dw, hipStream_t s);
+
+// ---- the stride-2 layers: Keras ZeroPadding2D(correct_pad(3)) + a 3x3 stride-2 'valid' conv ----------------------------------------
+// one spatial dim of n input pixels: pad before = n % 2 (even: 0, odd: 1), pad after = 1, out = (n + before + 1 - 3) / 2 + 1
+inline void mn_s2_geom(int n, int *pad_before, int *out)
+{
+    *pad_before = n % 2;
+    *out = (n + *pad_before + 1 - 3) / 2 + 1;
+}
+// depthwise, x (B, H, W, C), dy (B, OH, OW, C), w (3, 3, C), C % 4 == 0:
+// dx[b][y][x][c] = sum_{r,s} dy[b][(y+pt-r)/2][(x+pl-s)/2][c] w[r][s][c] over the taps where both quotients are exact and in range;
+// every dx element is written
+hipError_t launch_dwconv3x3_s2_dgrad(const float *dy, const float *w, int B, int H, int W, int C, float *dx, hipStream_t s);
+// dw[r][s][c] = sum_{b,oy,ox} x[b][2oy+r-pt][2ox+s-pl][c] dy[b][oy][ox][c]; mn_reduce_leaves(B OH OW) leaves;
+// part: dwconv3x3_s2_wgrad_ws_floats(...) floats
+size_t dwconv3x3_s2_wgrad_ws_floats(int B, int H, int W, int C);
+hipError_t launch_dwconv3x3_s2_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *part, float *dw, hipStream_t s);
+// the stem (Conv1), x (B, H, W, 3), dy (B, OH, OW, Cout), Cout % 4 == 0: dw (3, 3, 3, Cout)[r][s][ci][co] = sum_{b,oy,ox}
+// x[b][2oy+r-pt][2ox+s-pl][ci] dy[b][oy][ox][co] over stem_wgrad_leaves(B OH OW) leaves (a power of two <= 256 from the pixel count
+// alone) added in a fixed two-level tree; part: conv3x3_s2_cin3_wgrad_ws_floats(...) floats.  x is read element-wise (no alignment).
+int stem_wgrad_leaves(long long P);
+size_t conv3x3_s2_cin3_wgrad_ws_floats(int B, int H, int W, int Cout);
+hipError_t launch_conv3x3_s2_cin3_wgrad(const float *x, const float *dy, int B, int H, int W, int Cout, float *part, float *dw,
+                                        hipStream_t s);
 
 }  // namespace rpn

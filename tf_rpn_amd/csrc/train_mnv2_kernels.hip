@@ -1,6 +1,6 @@
-// train_mnv2_kernels.hip -- backward of MobileNetV2's stride-16 inverted-residual blocks (block_7 .. block_12, block_13_expand):
-// BatchNorm in training mode, the 1x1 convs on the float32 MFMA, the depthwise 3x3 stride-1 convs.  The trainer that strings them
-// together is in train_kernels.hip (mn_forward / mn_backward).
+// train_mnv2_kernels.hip -- backward of MobileNetV2 (Conv1, expanded_conv, block_1 .. block_12, block_13_expand): BatchNorm in
+// training mode, the 1x1 convs on the float32 MFMA, the depthwise 3x3 convs (stride 1 'same'; stride 2 behind Keras' correct_pad) and
+// the stem's weight gradient.  The trainer that strings them together is in train_kernels.hip (mn_forward / mn_backward).
 //
 // BatchNorm form (TF 2.0's fused BatchNorm, restated as recalled -- nothing here can run TF): over the N = B H W pixels of a channel,
 //   mean = sum x / N, var = sum (x - mean)^2 / N (biased), xhat = (x - mean) / sqrt(var + eps), y = gamma xhat + beta;
@@ -484,6 +484,242 @@ hipError_t launch_dwconv3x3_wgrad(const float *x, const float *dy, int B, int H,
     return hipGetLastError();
 }
 
+// ---- depthwise 3x3 stride-2 backward (block_1, block_3, block_6 and block_13's depthwise; Keras ZeroPadding2D(correct_pad) + 'valid') --
+// The forward reads x[2 oy + r - pt][2 ox + s - pl] for output (oy, ox), pt = H % 2, pl = W % 2 (mn_s2_geom).
+// dgrad: input pixel (y, x) is read by output ((y + pt - r) / 2, (x + pl - s) / 2) where both are exact and in range: at most 2 x 2 taps.
+// Every dx element is written once (pixels no output reads get zeros); a float4 of channels per lane.
+__global__ void __launch_bounds__(256) dwconv3x3_s2_dgrad_kernel(const float4 *__restrict__ dy, const float4 *__restrict__ w, int H, int W,
+                                                                int OH, int OW, int pt, int pl, int C4, long long total,
+                                                                float4 *__restrict__ dx)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % C4);
+        long long t = i / C4;
+        const int ix = (int)(t % W);
+        t /= W;
+        const int iy = (int)(t % H);
+        const long long b = t / H;
+        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int ny = iy + pt - r;
+            if (ny < 0 || (ny & 1) || (ny >> 1) >= OH) continue;
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const int nx = ix + pl - s;
+                if (nx < 0 || (nx & 1) || (nx >> 1) >= OW) continue;
+                const float4 v = dy[((b * OH + (ny >> 1)) * OW + (nx >> 1)) * C4 + c];
+                const float4 k = w[(r * 3 + s) * C4 + c];
+                acc.x = fmaf(v.x, k.x, acc.x);
+                acc.y = fmaf(v.y, k.y, acc.y);
+                acc.z = fmaf(v.z, k.z, acc.z);
+                acc.w = fmaf(v.w, k.w, acc.w);
+            }
+        }
+        dx[i] = acc;
+    }
+}
+
+// wgrad: part[leaf][9][C] = the nine per-channel sums over the leaf's OUTPUT pixels.  grid (ceil(C / 32), leaves); a workgroup is 8
+// channel quads x 32 row lanes (the stride-2 layers have 96 .. 576 channels and up to 125 000 output pixels: narrower channel tiles
+// give the grid three times the workgroups of the stride-1 kernel's 64-channel tile at the same leaf count).  The nine taps of a
+// lane's four channels stay in registers; a leaf is summed lane by lane in order.
+constexpr int kS2Quads = 8, kS2Lanes = 32;
+
+__global__ void __launch_bounds__(256) dwconv3x3_s2_wgrad_partial_kernel(const float4 *__restrict__ x, const float4 *__restrict__ dy, int B,
+                                                                        int H, int W, int OH, int OW, int pt, int pl, int C, int leaves,
+                                                                        float *__restrict__ part)
+{
+    __shared__ float red[kS2Lanes][9 * kS2Quads * 4];
+    const int q = threadIdx.x & (kS2Quads - 1), rl = threadIdx.x / kS2Quads;
+    const int C4 = C / 4, cq = blockIdx.x * kS2Quads + q, leaf = blockIdx.y;
+    const long long P = (long long)B * OH * OW, pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
+    float4 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (cq < C4) {
+        for (long long p = pbeg + rl; p < pend; p += kS2Lanes) {
+            const int ox = (int)(p % OW), oy = (int)((p / OW) % OH);
+            const long long b = p / ((long long)OW * OH);
+            const float4 d = dy[p * C4 + cq];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int iy = 2 * oy + r - pt;
+                if (iy < 0 || iy >= H) continue;
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    const int ix = 2 * ox + s - pl;
+                    if (ix < 0 || ix >= W) continue;
+                    const float4 v = x[((b * H + iy) * W + ix) * C4 + cq];
+                    float4 &a = acc[r * 3 + s];
+                    a.x = fmaf(v.x, d.x, a.x);
+                    a.y = fmaf(v.y, d.y, a.y);
+                    a.z = fmaf(v.z, d.z, a.z);
+                    a.w = fmaf(v.w, d.w, a.w);
+                }
+            }
+        }
+    }
+    // red[lane][tap][32 channels of the tile]
+    constexpr int TC = kS2Quads * 4;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        red[rl][t * TC + 4 * q + 0] = acc[t].x;
+        red[rl][t * TC + 4 * q + 1] = acc[t].y;
+        red[rl][t * TC + 4 * q + 2] = acc[t].z;
+        red[rl][t * TC + 4 * q + 3] = acc[t].w;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < 9 * TC; o += 256) {
+        const int t = o / TC, ch = blockIdx.x * TC + (o % TC);
+        float a = 0.0f;
+        for (int l = 0; l < kS2Lanes; ++l) a += red[l][o];
+        if (ch < C) part[((size_t)leaf * 9 + t) * C + ch] = a;
+    }
+}
+
+hipError_t launch_dwconv3x3_s2_dgrad(const float *dy, const float *w, int B, int H, int W, int C, float *dx, hipStream_t s)
+{
+    int pt, pl, OH, OW;
+    mn_s2_geom(H, &pt, &OH);
+    mn_s2_geom(W, &pl, &OW);
+    const long long total = (long long)B * H * W * (C / 4);
+    hipLaunchKernelGGL(dwconv3x3_s2_dgrad_kernel, dim3(grid_1dm(total)), dim3(256), 0, s, reinterpret_cast<const float4 *>(dy),
+                       reinterpret_cast<const float4 *>(w), H, W, OH, OW, pt, pl, C / 4, total, reinterpret_cast<float4 *>(dx));
+    return hipGetLastError();
+}
+
+size_t dwconv3x3_s2_wgrad_ws_floats(int B, int H, int W, int C)
+{
+    int pt, pl, OH, OW;
+    mn_s2_geom(H, &pt, &OH);
+    mn_s2_geom(W, &pl, &OW);
+    return (size_t)mn_reduce_leaves((long long)B * OH * OW) * 9 * C;
+}
+
+hipError_t launch_dwconv3x3_s2_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *part, float *dw, hipStream_t s)
+{
+    int pt, pl, OH, OW;
+    mn_s2_geom(H, &pt, &OH);
+    mn_s2_geom(W, &pl, &OW);
+    const int leaves = mn_reduce_leaves((long long)B * OH * OW);
+    hipLaunchKernelGGL(dwconv3x3_s2_wgrad_partial_kernel, dim3((C + kS2Quads * 4 - 1) / (kS2Quads * 4), leaves), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(x), reinterpret_cast<const float4 *>(dy), B, H, W, OH, OW, pt, pl, C, leaves, part);
+    hipLaunchKernelGGL(leaf_tree_kernel, dim3(grid_1dm(9LL * C)), dim3(256), 0, s, part, 9LL * C, leaves, dw);
+    return hipGetLastError();
+}
+
+// ---- the stem's weight gradient: 3x3 stride-2 conv from the 3-channel image (Conv1; same padding rule) -------------------------------
+// dw[r][s][ci][co] = sum over the B OH OW output pixels of x[b][2 oy + r - pt][2 ox + s - pl][ci] dy[b][oy][ox][co]: 27 Cout outputs,
+// each a sum over every pixel (500 000 at batch 8, 500 x 500), so the reduction tree is the kernel.  The pixels are cut into
+// stem_wgrad_leaves(P) leaves (a power of two <= 256 from P alone: 32 leaves would leave 7/8 of the device idle); a leaf is one
+// workgroup per 32 output channels, 8 channel quads x 32 pixel lanes, a lane keeping its 27 taps x 4 channels in registers (dy read
+// once as a float4, the 27 image values of the pixel's window shared by the 8 quads through the cache).  The lanes are summed in order
+// through LDS, one filter row at a time; the leaves in a fixed tree: tree_sum32 over each group of 32, then the (up to 8) groups
+// pairwise.
+constexpr int kStemMaxLeaves = 256;
+
+int stem_wgrad_leaves(long long P)
+{
+    int L = 1;
+    while (L < kStemMaxLeaves && P / (2 * L) >= 64) L *= 2;
+    return L;
+}
+
+__global__ void __launch_bounds__(256) conv3x3_s2_cin3_wgrad_partial_kernel(const float *__restrict__ x, const float4 *__restrict__ dy, int B,
+                                                                           int H, int W, int OH, int OW, int pt, int pl, int Cout,
+                                                                           int leaves, float *__restrict__ part)
+{
+    constexpr int TC = kS2Quads * 4;
+    __shared__ float red[kS2Lanes][9 * TC];
+    const int q = threadIdx.x & (kS2Quads - 1), rl = threadIdx.x / kS2Quads;
+    const int C4 = Cout / 4, cq = blockIdx.x * kS2Quads + q, leaf = blockIdx.y;
+    const long long P = (long long)B * OH * OW, pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
+    float4 acc[27];
+#pragma unroll
+    for (int t = 0; t < 27; ++t) acc[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (cq < C4) {
+        for (long long p = pbeg + rl; p < pend; p += kS2Lanes) {
+            const int ox = (int)(p % OW), oy = (int)((p / OW) % OH);
+            const long long b = p / ((long long)OW * OH);
+            const float4 d = dy[p * C4 + cq];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int iy = 2 * oy + r - pt;
+                if (iy < 0 || iy >= H) continue;
+#pragma unroll
+                for (int s = 0; s < 3; ++s) {
+                    const int ix = 2 * ox + s - pl;
+                    if (ix < 0 || ix >= W) continue;
+                    const float *xp = x + ((b * H + iy) * W + ix) * 3;
+#pragma unroll
+                    for (int ci = 0; ci < 3; ++ci) {
+                        const float v = xp[ci];
+                        float4 &a = acc[(r * 3 + s) * 3 + ci];
+                        a.x = fmaf(v, d.x, a.x);
+                        a.y = fmaf(v, d.y, a.y);
+                        a.z = fmaf(v, d.z, a.z);
+                        a.w = fmaf(v, d.w, a.w);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {                   // red[lane][(s, ci)][32 channels of the tile], one filter row per pass
+        if (r) __syncthreads();
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            red[rl][t * TC + 4 * q + 0] = acc[r * 9 + t].x;
+            red[rl][t * TC + 4 * q + 1] = acc[r * 9 + t].y;
+            red[rl][t * TC + 4 * q + 2] = acc[r * 9 + t].z;
+            red[rl][t * TC + 4 * q + 3] = acc[r * 9 + t].w;
+        }
+        __syncthreads();
+        for (int o = threadIdx.x; o < 9 * TC; o += 256) {
+            const int t = o / TC, ch = blockIdx.x * TC + (o % TC);
+            float a = 0.0f;
+            for (int l = 0; l < kS2Lanes; ++l) a += red[l][o];
+            if (ch < Cout) part[((size_t)leaf * 27 + r * 9 + t) * Cout + ch] = a;
+        }
+    }
+}
+
+// out[j] = the fixed two-level tree over the `leaves` (a power of two <= 256) slabs of len floats
+__global__ void __launch_bounds__(256) stem_tree_kernel(const float *__restrict__ part, long long len, int leaves, float *__restrict__ out)
+{
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256) {
+        float v[kStemMaxLeaves / kMaxLeaves];
+#pragma unroll
+        for (int g = 0; g < kStemMaxLeaves / kMaxLeaves; ++g) {     // (an absent group is a zero, which changes no bit)
+            const int n = leaves - g * kMaxLeaves;
+            v[g] = n > 0 ? tree_sum32<float>(part + (size_t)g * kMaxLeaves * len + j, (size_t)len, n < kMaxLeaves ? n : kMaxLeaves) : 0.0f;
+        }
+        out[j] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+    }
+}
+
+size_t conv3x3_s2_cin3_wgrad_ws_floats(int B, int H, int W, int Cout)
+{
+    int pt, pl, OH, OW;
+    mn_s2_geom(H, &pt, &OH);
+    mn_s2_geom(W, &pl, &OW);
+    return (size_t)stem_wgrad_leaves((long long)B * OH * OW) * 27 * Cout;
+}
+
+hipError_t launch_conv3x3_s2_cin3_wgrad(const float *x, const float *dy, int B, int H, int W, int Cout, float *part, float *dw,
+                                        hipStream_t s)
+{
+    int pt, pl, OH, OW;
+    mn_s2_geom(H, &pt, &OH);
+    mn_s2_geom(W, &pl, &OW);
+    const int leaves = stem_wgrad_leaves((long long)B * OH * OW);
+    hipLaunchKernelGGL(conv3x3_s2_cin3_wgrad_partial_kernel, dim3((Cout + kS2Quads * 4 - 1) / (kS2Quads * 4), leaves), dim3(256), 0, s, x,
+                       reinterpret_cast<const float4 *>(dy), B, H, W, OH, OW, pt, pl, Cout, leaves, part);
+    hipLaunchKernelGGL(stem_tree_kernel, dim3(grid_1dm(27LL * Cout)), dim3(256), 0, s, part, 27LL * Cout, leaves, dw);
+    return hipGetLastError();
+}
+
 }  // namespace rpn
 
 using namespace rpn;
@@ -604,4 +840,50 @@ extern "C" int rpn_dwconv3x3_wgrad(const float *d_x, const float *d_dy, int B, i
     RPN_REQUIRE_DEVICE();
     const hipError_t e = launch_dwconv3x3_wgrad(d_x, d_dy, B, H, W, C, reinterpret_cast<float *>(d_ws), d_dw, as_stream(stream));
     return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_dwconv3x3_wgrad: %s", hipGetErrorString(e));
+}
+
+extern "C" int rpn_dwconv3x3_s2_dgrad(const float *d_dy, const float *d_w, int B, int H, int W, int C, float *d_dx, void *stream)
+{
+    RPN_REQUIRE(d_dy && d_w && d_dx, "rpn_dwconv3x3_s2_dgrad: null pointer");
+    RPN_REQUIRE(dw_ok(B, H, W, C), "rpn_dwconv3x3_s2_dgrad: bad shape (C must be a multiple of 4)");
+    MN_ALIGNED("rpn_dwconv3x3_s2_dgrad", d_dy, d_w, d_dx);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_dwconv3x3_s2_dgrad(d_dy, d_w, B, H, W, C, d_dx, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_dwconv3x3_s2_dgrad: %s", hipGetErrorString(e));
+}
+
+extern "C" size_t rpn_dwconv3x3_s2_wgrad_workspace_bytes(int B, int H, int W, int C)
+{
+    return dw_ok(B, H, W, C) ? a256m(dwconv3x3_s2_wgrad_ws_floats(B, H, W, C) * sizeof(float)) : 0;
+}
+
+extern "C" int rpn_dwconv3x3_s2_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws,
+                                      size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_x && d_dy && d_dw, "rpn_dwconv3x3_s2_wgrad: null pointer");
+    RPN_REQUIRE(dw_ok(B, H, W, C), "rpn_dwconv3x3_s2_wgrad: bad shape (C must be a multiple of 4)");
+    MN_ALIGNED("rpn_dwconv3x3_s2_wgrad", d_x, d_dy, d_dw, (const char *)d_ws);
+    const size_t need = rpn_dwconv3x3_s2_wgrad_workspace_bytes(B, H, W, C);
+    if (!d_ws || ws_bytes < need) return fail(RPN_ERR_WORKSPACE, "rpn_dwconv3x3_s2_wgrad: %zu bytes of workspace needed", need);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_dwconv3x3_s2_wgrad(d_x, d_dy, B, H, W, C, reinterpret_cast<float *>(d_ws), d_dw, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_dwconv3x3_s2_wgrad: %s", hipGetErrorString(e));
+}
+
+extern "C" size_t rpn_conv3x3_s2_cin3_wgrad_workspace_bytes(int B, int H, int W, int Cout)
+{
+    return dw_ok(B, H, W, Cout) ? a256m(conv3x3_s2_cin3_wgrad_ws_floats(B, H, W, Cout) * sizeof(float)) : 0;
+}
+
+extern "C" int rpn_conv3x3_s2_cin3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int Cout, float *d_dw, void *d_ws,
+                                         size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_x && d_dy && d_dw, "rpn_conv3x3_s2_cin3_wgrad: null pointer");
+    RPN_REQUIRE(dw_ok(B, H, W, Cout), "rpn_conv3x3_s2_cin3_wgrad: bad shape (Cout must be a multiple of 4)");
+    MN_ALIGNED("rpn_conv3x3_s2_cin3_wgrad", d_x, d_dy, d_dw, (const char *)d_ws);
+    const size_t need = rpn_conv3x3_s2_cin3_wgrad_workspace_bytes(B, H, W, Cout);
+    if (!d_ws || ws_bytes < need) return fail(RPN_ERR_WORKSPACE, "rpn_conv3x3_s2_cin3_wgrad: %zu bytes of workspace needed", need);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_conv3x3_s2_cin3_wgrad(d_x, d_dy, B, H, W, Cout, reinterpret_cast<float *>(d_ws), d_dw, as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_conv3x3_s2_cin3_wgrad: %s", hipGetErrorString(e));
 }

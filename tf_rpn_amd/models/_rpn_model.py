@@ -8,7 +8,9 @@ head (``rpn_conv``, ``rpn_reg``, ``rpn_cls``) is trained on a frozen backbone; `
 trains the whole VGG16 model as the reference does (its Keras base model is trainable), a later conv name the convs from there up.
 On MobileNetV2 ``train_backbone_from`` names the first layer of a stride-16 inverted-residual block (``"block_7_expand"`` ..
 ``"block_12_expand"``) or ``"block_13_expand"``: that layer and everything above it train with the head, BatchNorm in training mode;
-the layers below (the stride-2 depthwise convs, the stem, the large low-level activations) stay frozen.
+the layers below stay frozen.  ``compile(train_backbone=True)`` trains every layer of either backbone, as the reference's trainer.py
+does: on MobileNetV2 all 40 convs (``MOBILENET_V2_CONVS``: the stem, ``expanded_conv``, ``block_1`` .. ``block_12``,
+``block_13_expand``), each with its BatchNorm, and the head.
 """
 import ctypes
 
@@ -44,6 +46,11 @@ VGG16_CONVS = ("block1_conv1", "block1_conv2", "block2_conv1", "block2_conv2", "
 MOBILENET_V2_SPAN = tuple("block_%d_%s" % (b, part) for b in range(7, 13) for part in ("expand", "depthwise", "project")) + ("block_13_expand",)
 # ... and the names it accepts: the first layer of a block, or block_13_expand alone
 MOBILENET_V2_TRAIN_FROM = tuple("block_%d_expand" % b for b in range(7, 14))
+# every conv of MobileNetV2 up to the feature map, in graph order: what compile(train_backbone=True) trains.  expanded_conv has no
+# expand conv; Conv1's BatchNorm layer is "bn_Conv1" (its Keras name), every other conv X's is "X_BN".
+MOBILENET_V2_CONVS = (("Conv1", "expanded_conv_depthwise", "expanded_conv_project")
+                      + tuple("block_%d_%s" % (b, part) for b in range(1, 13) for part in ("expand", "depthwise", "project"))
+                      + ("block_13_expand",))
 BN_KEYS = ("gamma", "beta", "mean", "var")
 
 
@@ -74,8 +81,9 @@ class RPNModel(object):
         self.tap_layer = "block5_conv3" if backbone == "vgg16" else "block_13_expand"
         self._head = {}                 # head weights last given to set_weights / load_weights: {name: (kernel, bias)}
         self._backbone = {}             # the same for the VGG16 convs (the handle keeps only packed / transformed copies)
-        self._mn = {}                   # MobileNetV2's stride-16 span, UNFOLDED (the handle folds BatchNorm at load):
+        self._mn = {}                   # MobileNetV2's convs, UNFOLDED (the handle folds BatchNorm at load):
                                         # {conv: {"kernel", "gamma", "beta", "mean", "var"}}
+        self._bn_of = {layer["name"]: layer["bn_name"] for layer in self.layers}
         self._t = L.vp(0)               # native trainer (compile)
         self._opt = None
         self._train_from = None         # first trained backbone layer, None: the head only
@@ -132,7 +140,7 @@ class RPNModel(object):
             else:
                 args += [None, None, None, None]
             L.check(lib.rpn_model_set_layer(self._h, name.encode(), *args), "rpn_model_set_layer(%s)" % name)
-            if self.backbone == "mobilenet_v2" and name in MOBILENET_V2_SPAN:
+            if self._is_mn(name):
                 self._mn[name] = dict({"kernel": kernel.copy()}, **{k: a.copy() for k, a in zip(BN_KEYS, keep[2:])})
                 if self._t and name in self.trained_layers():
                     self._trainer_set(name)
@@ -278,7 +286,8 @@ class RPNModel(object):
         return out if batch is None else out[:batch]
 
     # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
-    def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None):
+    def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None,
+                train_backbone=False):
         """``rpn_model.compile(optimizer=tf.optimizers.Adam(learning_rate), loss=[reg_loss, cls_loss])`` (trainer.py:54-56).
 
         ``train_backbone_from=None`` (default) trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone,
@@ -293,7 +302,13 @@ class RPNModel(object):
         trained layers run in exact float32 with BatchNorm in TRAINING mode -- batch mean and biased batch variance over (B, F, F),
         eps 1e-3, and the moving statistics updated in the same step with momentum 0.999 and Bessel's correction (TF 2.0's fused
         BatchNorm as recalled); ``test_on_batch`` normalises with the moving statistics and updates nothing (Keras ``evaluate``).
-        The stride-2 blocks, the stem and ``expanded_conv`` do not train yet; with any other name the backbone trains its head only.
+        With any other name the backbone trains its head only.
+
+        ``train_backbone=True`` trains every layer of the model, as the reference's trainer.py does (it cannot be combined with
+        ``train_backbone_from``).  On VGG16 it is ``train_backbone_from="block1_conv1"``.  On MobileNetV2 it trains all 40 convs of
+        ``MOBILENET_V2_CONVS`` -- the stem ``Conv1``, ``expanded_conv``, the stride-2 blocks included -- each with its BatchNorm, and
+        the head: there is no frozen prefix, every layer runs in exact float32 at its own resolution from the image batch up, with
+        BatchNorm as described above.  The kept activations take about 2 GB at batch 8, 500 x 500 (README, "Training the head").
 
         ``trainable`` names the head layers only and must be exactly the three of them.
 
@@ -304,13 +319,18 @@ class RPNModel(object):
         if isinstance(trainable, str) or set(trainable) != set(HEAD_LAYERS):
             raise ValueError("trainable=%r: trainable names the RPN head, which trains on a frozen backbone -- it must be exactly %s; "
                              "to train backbone convs too use train_backbone_from=<first trained conv>" % (trainable, HEAD_LAYERS))
+        if train_backbone and train_backbone_from is not None:
+            raise ValueError("train_backbone=True trains every layer: it cannot be combined with train_backbone_from=%r"
+                             % (train_backbone_from,))
+        if train_backbone and self.backbone == "vgg16":
+            train_backbone_from = VGG16_CONVS[0]
         if train_backbone_from is not None:
             if self.backbone != "vgg16":
                 if train_backbone_from not in MOBILENET_V2_TRAIN_FROM:
                     raise ValueError("train_backbone_from=%r: on %s the accepted names are %s (that layer and every layer above it "
                                      "train with the head); otherwise the backbone trains its head only -- the named layer is a VGG16 "
-                                     "conv, is not the first layer of a block, or lies below block_7_expand, where the stride-2 "
-                                     "depthwise convs and the stem have no backward yet"
+                                     "conv, is not the first layer of a block, or lies below block_7_expand (train_backbone=True "
+                                     "trains the whole model)"
                                      % (train_backbone_from, self.backbone, MOBILENET_V2_TRAIN_FROM))
             elif train_backbone_from not in VGG16_CONVS:
                 raise ValueError("train_backbone_from=%r is not a VGG16 conv (one of %s)" % (train_backbone_from, VGG16_CONVS))
@@ -319,14 +339,17 @@ class RPNModel(object):
             self._sync_head()       # layers the new trainer freezes run on the handle: they keep what the old one trained
             got = self.get_weights()
             for k, d in got.items():
-                if k in MOBILENET_V2_SPAN and self.backbone == "mobilenet_v2":
-                    self._mn[k] = dict({"kernel": d["kernel"]}, **got[k + "_BN"])
+                if self._is_mn(k):
+                    self._mn[k] = dict({"kernel": d["kernel"]}, **got[self._bn_of[k]])
                 elif "kernel" in d:
                     (self._head if k in HEAD_LAYERS else self._backbone)[k] = (d["kernel"], d["bias"])
             L.lib().rpn_head_trainer_destroy(self._t)
             self._t = L.vp(0)
         t = L.vp(0)
-        if train_backbone_from is None:
+        if train_backbone and train_backbone_from is None:      # MobileNetV2 from the stem up
+            L.check(L.lib().rpn_model_trainer_create_full(self._h, ctypes.byref(t)), "rpn_model_trainer_create_full")
+            train_backbone_from = MOBILENET_V2_CONVS[0]
+        elif train_backbone_from is None:
             L.check(L.lib().rpn_head_trainer_create(self._h, ctypes.byref(t)), "rpn_head_trainer_create")
         else:
             L.check(L.lib().rpn_model_trainer_create(self._h, train_backbone_from.encode(), ctypes.byref(t)),
@@ -343,15 +366,15 @@ class RPNModel(object):
                     self._trainer_set(name)
 
     def trained_layers(self):
-        """The layers a training step updates: the head, plus the backbone convs from ``train_backbone_from`` up (each
-        MobileNetV2 conv with its BatchNorm)."""
+        """The layers a training step updates: the head, plus the backbone convs from ``train_backbone_from`` up, or all of them
+        after ``compile(train_backbone=True)``, in graph order (each MobileNetV2 conv with its BatchNorm)."""
         if self._train_from is None:
             return HEAD_LAYERS
-        order = VGG16_CONVS if self.backbone == "vgg16" else MOBILENET_V2_SPAN
+        order = VGG16_CONVS if self.backbone == "vgg16" else MOBILENET_V2_CONVS
         return tuple(order[order.index(self._train_from):]) + HEAD_LAYERS
 
     def _is_mn(self, name):
-        return self.backbone == "mobilenet_v2" and name in MOBILENET_V2_SPAN
+        return self.backbone == "mobilenet_v2" and name in MOBILENET_V2_CONVS
 
     def _trainer_set(self, name):
         if self._is_mn(name):
@@ -450,7 +473,7 @@ class RPNModel(object):
             if "kernel" not in d:           # a BatchNorm entry: goes with its conv
                 continue
             if self._is_mn(name):           # refolded from kernel + gamma / beta / the updated moving statistics
-                bn = [got[name + "_BN"][k].ctypes.data_as(L.c_float_p) for k in BN_KEYS]
+                bn = [got[self._bn_of[name]][k].ctypes.data_as(L.c_float_p) for k in BN_KEYS]
                 L.check(lib.rpn_model_set_layer(self._h, name.encode(), d["kernel"].ctypes.data_as(L.c_float_p), None, *bn),
                         "rpn_model_set_layer(%s)" % name)
                 continue
