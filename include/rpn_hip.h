@@ -425,6 +425,35 @@ int rpn_maxpool2x2(const float *d_x, int B, int H, int W, int C, float *d_out, v
 int rpn_dwconv3x3(const float *d_x, int B, int H, int W, int C, const float *d_w, const float *d_bias,
                   int stride, int pad_t, int pad_l, int OH, int OW, int act, float *d_out, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * RoI pooling of a feature map under proposals (no reference counterpart: the operator between the RPN and a Faster R-CNN
+ * detection head, tf.image.crop_and_resize(feature_map, rois, box_indices, (ph, pw)), bilinear, extrapolation value 0).
+ *   d_x (B,H,W,C) NHWC float32, d_rois (B,R,4) normalised [y1,x1,y2,x2], d_out (B,R,ph,pw,C); RoI r of image b samples image b.
+ *   d_valid (B,) int32 or NULL: rows r >= valid[b] are written as zeros (what rpn_decode_nms / rpn_combined_nms return).
+ *   float32, every operation rounded on its own:
+ *     hs = (y2 - y1) * (H - 1) / (ph - 1), in_y(i) = y1 * (H - 1) + i * hs   (ph == 1: in_y = 0.5 * (y1 + y2) * (H - 1)), same in x;
+ *     in_y < 0, in_y > H - 1, in_x < 0, in_x > W - 1 or NaN: the sample is 0 in every channel; else t = floor(in_y), b = ceil(in_y),
+ *     ly = in_y - t, l = floor(in_x), r = ceil(in_x), lx = in_x - l, top = x[t,l] + (x[t,r] - x[t,l]) * lx, bot likewise on row b,
+ *     out = top + (bot - top) * ly.
+ *   A box side clipped to exactly 1.0 can round the LAST sample's coordinate just above H - 1 in float32; that sample is then 0
+ *   (TensorFlow evaluates the same expression).
+ * rpn_roi_pool_backward: d_dx (B,H,W,C) = the adjoint of rpn_roi_pool applied to d_dy (B,R,ph,pw,C): every sample adds dy times its
+ *   four corner weights; extrapolated samples and rows beyond valid add nothing.  Writes every element of d_dx.  A gather in
+ *   (r, i, j) order without floating-point atomics: bit-identical from run to run, and image b's dx depends on image b alone.
+ *   There is no gradient with respect to the boxes.
+ * rpn_model_roi_pool: rpn_roi_pool of the feature tap (block5_conv3 / block_13_expand) where the handle's last forward left it --
+ *   float32, or the hi / lo 16-bit split form under BF16X3 / F16X3, no float32 copy -- bit-identical to rpn_roi_pool applied to
+ *   rpn_model_get_activation of that tap.  Ordered on `stream` like a forward; fails before the first forward and for
+ *   B > max_batch.
+ * C % 4 == 0; pointers 16-byte aligned; B, R, ph, pw, H, W >= 1.
+ * ---------------------------------------------------------------------------------- */
+int rpn_roi_pool(const float *d_x, int B, int H, int W, int C, const float *d_rois, int R, int ph, int pw, const int *d_valid,
+                 float *d_out, void *stream);
+int rpn_roi_pool_backward(const float *d_dy, const float *d_rois, const int *d_valid, int B, int H, int W, int C, int R, int ph,
+                          int pw, float *d_dx, void *stream);
+int rpn_model_roi_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, const int *d_valid, float *d_out,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

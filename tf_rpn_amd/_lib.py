@@ -111,6 +111,9 @@ _SIGNATURES = {
     "rpn_conv2d": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 10 + [vp, vp]),
     "rpn_maxpool2x2": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_dwconv3x3": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),
+    "rpn_roi_pool": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp] + [ctypes.c_int] * 3 + [vp, vp, vp]),
+    "rpn_roi_pool_backward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 7 + [vp, vp]),
+    "rpn_model_roi_pool": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "conv_kernels.h"
+#include "roi_kernels.h"
 #include "rpn_common.h"
 
 namespace rpn {
@@ -101,6 +102,7 @@ struct rpn_model {
     // all such layers of the handle, under the same one-stream-at-a-time rule
     void *d_wino_ws = nullptr;
     const float *last_input = nullptr;
+    bool feat_written = false;             // some forward has written feat_tensor (rpn_model_roi_pool reads it from the arena)
     double flops = 0.0;
     // optional per-op timing: one hipEvent before the first op and one after every op
     int profiling = 0;                 // number of forwards whose events are kept (ring)
@@ -1072,6 +1074,7 @@ static int run_ops(rpn_model *m, const float *d_imgs, int B, float *d_reg, float
                         hipGetErrorString(e));
         ++op_index;
         if (evs && want_event((size_t)op_index)) RPN_HIP_CHECK(hipEventRecord(evs[op_index], s));
+        if (op.out == m->feat_tensor) m->feat_written = true;
     }
     return RPN_OK;
 }
@@ -1385,6 +1388,21 @@ extern "C" int rpn_model_get_activation(rpn_model *m, const char *name, float *d
     RPN_HIP_CHECK(hipMemcpyAsync(d_out, m->d_arena + t.offset * (size_t)m->max_batch, bytes,
                                  hipMemcpyDeviceToDevice, as_stream(stream)));
     return RPN_OK;
+}
+
+// RoI pooling of the feature tap, read where the last forward left it: float32 NHWC, or the split form of the bf16x3 / f16x3 graphs
+// (roi_kernels.hip joins hi + lo per corner exactly as split_to_f32_kernel does, so the result equals pooling the float32 copy)
+extern "C" int rpn_model_roi_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, const int *d_valid, float *d_out,
+                                  void *stream)
+{
+    RPN_REQUIRE(m && d_rois && d_out, "rpn_model_roi_pool: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_roi_pool: batch %d outside [1, %d]", B, m->max_batch);
+    RPN_REQUIRE(R >= 1 && ph >= 1 && pw >= 1, "rpn_model_roi_pool: R and the pooling size must be >= 1 (got %d, %d x %d)", R, ph, pw);
+    RPN_REQUIRE(m->d_arena && m->feat_written, "rpn_model_roi_pool: no forward pass has run");
+    const Tensor &t = m->tensors[m->feat_tensor];
+    const int src = !t.split_fmt ? ROI_SRC_F32 : (m->f16 ? ROI_SRC_SPLIT_F16 : ROI_SRC_SPLIT_BF16);
+    return roi_pool_forward("rpn_model_roi_pool", m->d_arena + t.offset * (size_t)m->max_batch, src, B, t.H, t.W, t.C, d_rois, R, ph,
+                            pw, d_valid, d_out, as_stream(stream));
 }
 
 // ---- single-layer entry points (kernel-level parity tests, micro-benchmarks) -----------------

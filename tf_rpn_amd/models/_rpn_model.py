@@ -35,6 +35,15 @@ class FeatureExtractor(object):
     def output(self):
         return self._model.get_activation(self.name)
 
+    def roi_pool(self, rois, pooling_size=(7, 7), valid=None, out=None):
+        """RoI pooling of this layer's output as the model's last forward left it, under ``rois`` (B, R, [y1, x1, y2, x2])
+        normalised -> (B, R, ph, pw, C) float32 (``utils/roi_utils.py`` states the operator; ``valid`` (B,) int32: rows beyond it
+        are zeros).  Read straight from the handle's arena on the current stream -- under "f16x3" / "bf16x3" in the split form the
+        tap is kept in, without a float32 copy -- and bit-identical to ``roi_utils.roi_pooling(self.output()[:B], ...)``."""
+        if self.name != self._model.tap_layer:
+            raise ValueError("roi_pool reads the model's feature tap %r, not %r" % (self._model.tap_layer, self.name))
+        return self._model.roi_pool(rois, pooling_size, valid, out)
+
 
 # the layers a training step updates (models/rpn_vgg16.py:18-20, models/rpn_mobilenet_v2.py:18-20)
 HEAD_LAYERS = ("rpn_conv", "rpn_cls", "rpn_reg")
@@ -284,6 +293,29 @@ class RPNModel(object):
         L.check(L.lib().rpn_model_get_activation(self._h, name.encode(), L.ptr(out), out.numel() * 4, None,
                                                  L.stream_ptr()), "rpn_model_get_activation")
         return out if batch is None else out[:batch]
+
+    def roi_pool(self, rois, pooling_size=(7, 7), valid=None, out=None):
+        """``FeatureExtractor.roi_pool``: rpn_model_roi_pool of the tap layer after a forward.  ``out``: a preallocated contiguous
+        CUDA float32 (B, R, ph, pw, C) tensor to fill (no allocation, as ``forward_into``)."""
+        ph, pw = (int(v) for v in pooling_size)
+        C = self.activation_shape(self.tap_layer)[3]
+        for t, dtype, what in ((rois, torch.float32, "rois"), (valid, torch.int32, "valid")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+                raise ValueError("%s must be a contiguous CUDA %s tensor" % (what, dtype))
+        if rois.dim() != 3 or int(rois.shape[2]) != 4 or not 1 <= int(rois.shape[0]) <= self.max_batch:
+            raise ValueError("rois must be (B<=%d, R, 4), got %s" % (self.max_batch, tuple(rois.shape)))
+        B, R = int(rois.shape[0]), int(rois.shape[1])
+        if valid is not None and tuple(valid.shape) != (B,):
+            raise ValueError("valid must be (%d,), got %s" % (B, tuple(valid.shape)))
+        shape = (B, R, ph, pw, C)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device="cuda")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and tuple(out.shape) == shape):
+            raise ValueError("out must be a contiguous CUDA float32 tensor of shape %s" % (shape,))
+        L.check(L.lib().rpn_model_roi_pool(self._h, L.ptr(rois), B, R, ph, pw, L.ptr(valid), L.ptr(out), L.stream_ptr()),
+                "rpn_model_roi_pool")
+        return out
 
     # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
     def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None,

@@ -194,6 +194,24 @@ class Proposer(object):
         # before trusting the proposals of weights that may leave the float16 range)
         return ob, osc, ov, oi
 
+    def propose_features(self, imgs, pooling_size=(7, 7)):
+        """imgs -> (boxes (B,300,4), scores (B,300), valid (B,) int32, pooled (B,300,ph,pw,C)): the proposals of ``propose`` and the
+        feature tap pooled under them (``FeatureExtractor.roi_pool``; rows beyond ``valid`` are zeros) -- what a Faster R-CNN
+        detection head consumes.  Forward, decode + NMS and the pool run in that order on the current stream, without a host
+        synchronisation.  Always the non-overlapped sequence, also with ``overlap_nms=True`` (the pipelined ``propose_async`` is
+        not involved).  ``pooled`` is a buffer of this object, overwritten by the next call with the same pooling size."""
+        B = self._check_imgs(imgs)
+        ph, pw = (int(v) for v in pooling_size)
+        deltas, scores = self.forward(imgs)
+        ob, osc, oi, ov = self._boxes[:B], self._scores[:B], self._idx[:B], self._valid[:B]
+        self.decode_nms(deltas, scores, B, ob, osc, oi, ov)
+        bufs = self.__dict__.setdefault("_pooled", {})
+        if (ph, pw) not in bufs:
+            C = self.feature_extractor.output_shape[3]
+            bufs[(ph, pw)] = torch.empty((self.max_batch, self.topn, ph, pw, C), dtype=torch.float32, device="cuda")
+        pooled = self.feature_extractor.roi_pool(ob, (ph, pw), valid=ov, out=bufs[(ph, pw)][:B])
+        return ob, osc, ov, pooled
+
     def propose_async(self, imgs):
         """Pipelined form (needs ``overlap_nms=True``): enqueues the conv stack on the current stream and decode+NMS
         on the side stream and returns the output tensors WITHOUT ordering the current stream behind the NMS, so that
