@@ -306,6 +306,32 @@ int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const
                           float *d_losses, void *stream);
 long long rpn_head_trainer_steps(const rpn_head_trainer *t);
 int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, int B, void *stream);
+/* A step in two halves, for a caller that trains a second stage on the feature tap (joint Faster R-CNN training: the backbone gets the
+ * RPN's gradient plus the second stage's).  rpn_head_trainer_step(update) IS rpn_head_trainer_forward(train = update) followed, when
+ * update = 1, by rpn_head_trainer_backward(d_feature_grad = NULL): the same launches in the same order on the same buffers, the same
+ * bits.
+ *   forward: the forward pass and the losses, d_losses <- [reg + cls, reg, cls]; train = 1 also keeps the loss gradients and, on
+ *     MobileNetV2, runs BatchNorm with the batch statistics and updates the moving statistics HERE (as the first half of an update step
+ *     does); train = 0 is an evaluation (moving statistics, nothing kept).  train = 1 leaves the forward PENDING on the trainer; train = 0
+ *     leaves nothing pending.  A new forward replaces a pending one (on MobileNetV2 the moving statistics have then been updated twice);
+ *     set_layer / set_bn drop it.  rpn_head_trainer_outputs works after either kind of forward.
+ *   feature: the float32 feature tap (B,F,F,Cin) of the last forward of either kind -- block5_conv3 after its ReLU / block_13_expand
+ *     after its ReLU6 -- copied to d_out.  On a trainer with a trained backbone span this is the trainer's own exact-float32 tensor from
+ *     the master weights (BatchNorm in batch-statistics mode after train = 1), not the inference handle's; on a frozen-backbone trainer
+ *     it is the handle's features as the head trainer reads them.
+ *   backward: the second half -- head backward, backbone backward, ONE Adam launch (t += 1 here, and only here).  d_feature_grad
+ *     (B,F,F,Cin) or NULL: dL2/dfeat of a loss the caller computed from `feature`'s tensor; it is read in place (no copy, no extra
+ *     pass, no atomics) by the epilogue of the first 3x3 dgrad, where it is added to the RPN's gradient at the tap BEFORE the tap's
+ *     activation mask: VGG16 (dgrad + g2) [feat > 0]; MobileNetV2: the BatchNorm backward that follows masks the sum with ReLU6's
+ *     [0 < y < 6].  The gradients of rpn_conv, rpn_reg and rpn_cls do not depend on it.  It must stay valid until the stream has run
+ *     the call.  Requires a pending forward (train = 1) on this trainer with the same d_imgs pointer and the same B, else
+ *     RPN_ERR_INVALID; the pending forward is consumed.  On a frozen-backbone trainer (rpn_head_trainer_create, train_from = NULL) a
+ *     non-NULL d_feature_grad is RPN_ERR_INVALID -- nothing below the tap trains -- rather than being dropped. */
+int rpn_head_trainer_forward(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
+                             const float *d_bbox_labels, int train, float *d_losses, void *stream);
+int rpn_head_trainer_feature(rpn_head_trainer *t, float *d_out, int B, void *stream);
+int rpn_head_trainer_backward(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_feature_grad,
+                              float lr, float beta_1, float beta_2, float epsilon, void *stream);
 /* the same trainer with the VGG16 backbone trained from `train_from` ("block1_conv1" .. "block5_conv3") upward: the reference's
  * trainable Keras base model (models/rpn_vgg16.py:16-21) when train_from = "block1_conv1".  NULL: rpn_head_trainer_create.
  * set_layer takes every VGG16 conv as well (all 13 must be set before a step): convs below train_from are frozen constants, outside
@@ -392,6 +418,10 @@ int rpn_conv3x3_s2_cin3_wgrad(const float *d_x, const float *d_dy, int B, int H,
  *   i.e. dx[b][y][x][ci] = sum_{r,s,co} dy[b][y+1-r][x+1-s][co] w[r][s][ci][co] (zero outside); with d_mask (B,H,W,Cin) non-NULL
  *   only the entries where mask > 0 are kept (the ReLU of the layer's input), the others are 0.  Cin % 4 == 0, Cout % 16 == 0.
  *   d_ws: rpn_conv3x3_dgrad_workspace_bytes(Cin, Cout) bytes.
+ * rpn_conv3x3_dgrad_add: the same with an addend d_add (B,H,W,Cin), non-NULL and 4-byte aligned, in the epilogue: d_dx = mask > 0 ?
+ *   fl32(dgrad + add) : 0 (without mask: fl32(dgrad + add)) -- the gradient that reaches the same tensor by another path, added before
+ *   the mask, in the same pass, each output written once.  Same validation, workspace and tile choice (rpn_conv3x3_dgrad_tile_n).
+ *   d_add == d_dx is allowed: each element is read and then written by the same lane.
  * rpn_maxpool2x2_backward: MaxPooling2D(2, 2) 'valid' backward fused with the ReLU mask of the pooled tensor: d_y (B,H,W,C) the
  *   pool's input, d_dpool (B,H/2,W/2,C) -> d_dy_out (B,H,W,C): each window's gradient at its first maximum (row-major, replaced only
  *   by a strictly greater value) when that maximum is > 0; every other entry, the rows / columns no window covers included, is 0.
@@ -406,6 +436,8 @@ size_t rpn_conv3x3_dgrad_workspace_bytes(int Cin, int Cout);
 int rpn_conv3x3_dgrad_tile_n(int B, int H, int W, int Cin);
 int rpn_conv3x3_dgrad(const float *d_dy, const float *d_w, const float *d_mask, int B, int H, int W, int Cin, int Cout, float *d_dx,
                       void *d_ws, size_t ws_bytes, void *stream);
+int rpn_conv3x3_dgrad_add(const float *d_dy, const float *d_w, const float *d_mask, const float *d_add, int B, int H, int W, int Cin,
+                          int Cout, float *d_dx, void *d_ws, size_t ws_bytes, void *stream);
 int rpn_maxpool2x2_backward(const float *d_y, const float *d_dpool, int B, int H, int W, int C, float *d_dy_out, void *stream);
 size_t rpn_conv3x3_wgrad_wide_workspace_bytes(int B, int H, int W, int Cin, int Cout);
 int rpn_conv3x3_wgrad_wide(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw, float *d_db,

@@ -4,6 +4,7 @@
     python scripts/train_step_bench.py --train-backbone-from block1_conv1 [--batch 8] [--steps 20] [--warmup 3]
     python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone-from block_7_expand [--batch 8] ...
     python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone [--batch 8] ...     (the whole model; also vgg16)
+    python scripts/train_step_bench.py --train-backbone --feature-grad ...       (any backbone-training leg: + the joint step)
 
 Times on the device with HIP events around (a) a whole training step (backbone at the handle's precision + float32 head forward,
 losses, backward, Adam), (b) an evaluation step (no backward), (c) the 3x3 weight-gradient entry rpn_conv3x3_wgrad on the
@@ -20,6 +21,12 @@ With --train-backbone: compile(train_backbone=True), every layer of the backbone
 (a) and (b) for the whole-model trainer, the device memory the trainer allocated at its first step, and the three stride-2 kernels'
 single-layer entries on their largest layers (block_1_depthwise: 250 x 250 x 96 in, 125 x 125 out; Conv1: 500 x 500 x 3 in, 250 x
 250 x 32 out) with the bytes each must move and its rate.
+
+With --feature-grad (a backbone-training leg): after the plain step, in the same process and with the same HIP-event method, the step
+in two halves with a fixed random second-stage gradient G (B,F,F,C) at the feature tap -- "ms_feature_grad_step":
+RPNModel.forward_for_training + apply_gradients(G) (the Python surface: it also copies the tap and the head outputs to fresh tensors);
+"ms_split_step" / "ms_split_step_feature_grad": rpn_head_trainer_forward + rpn_head_trainer_backward with NULL / with G, nothing
+else, whose difference is what the addend costs in the first dgrad's epilogue; "feature_grad_mbytes": the B F F C 4 bytes it reads.
 """
 import argparse
 import json
@@ -116,16 +123,42 @@ def step_times(model, imgs, deltas, lab, B, steps, warmup):
     return timed(lambda: step(1), steps, warmup), timed(lambda: step(0), steps, warmup)
 
 
+def feature_grad_times(model, imgs, deltas, lab, B, steps, warmup):
+    """The joint step's legs (module docstring, --feature-grad), after the plain step in the same process."""
+    lib = L.lib()
+    F = model.feature_map_shape
+    C = model.activation_shape(model.tap_layer)[3]
+    G = torch.from_numpy((np.random.RandomState(1).standard_normal((B, F, F, C)) * 1e-4).astype(np.float32)).cuda()
+    losses = torch.empty(3, device="cuda")
+
+    def python_step():
+        model.forward_for_training(imgs, (deltas, lab))
+        model.apply_gradients(G)
+
+    def abi_step(g):
+        L.check(lib.rpn_head_trainer_forward(model._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(lab), 1, L.ptr(losses), L.stream_ptr()),
+                "rpn_head_trainer_forward")
+        L.check(lib.rpn_head_trainer_backward(model._t, L.ptr(imgs), B, L.ptr(g), *(model._opt + (L.stream_ptr(),))),
+                "rpn_head_trainer_backward")
+
+    ms_null = timed(lambda: abi_step(None), steps, warmup)
+    ms_g = timed(lambda: abi_step(G), steps, warmup)
+    ms_py = timed(python_step, steps, warmup)
+    return {"ms_split_step": round(ms_null, 4), "ms_split_step_feature_grad": round(ms_g, 4), "ms_feature_grad_step": round(ms_py, 4),
+            "feature_grad_mbytes": round(G.numel() * 4 / 1e6, 1)}
+
+
 def frac(flop, ms):
     return round(flop / (ms * 1e-3) / PEAK_F32_MFMA, 3)
 
 
-def bench_backbone(train_from, precision, B, steps, warmup):
+def bench_backbone(train_from, precision, B, steps, warmup, feature_grad=False):
     hp = train_utils.get_hyper_params("vgg16")
     model, _ = rpn_vgg16.get_model(hp, precision=precision, max_batch=B)
     imgs, deltas, lab = step_inputs(model, hp, B)
     model.compile(learning_rate=1e-5, train_backbone_from=train_from)
     ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
+    joint = feature_grad_times(model, imgs, deltas, lab, B, steps, warmup) if feature_grad else {}
     lib = L.lib()
     F, K = model.feature_map_shape, model.anchor_count
     first = [v[0] for v in VGG16].index(train_from)
@@ -164,13 +197,13 @@ def bench_backbone(train_from, precision, B, steps, warmup):
         if pool:
             H //= 2
     total = fwd + bwd
-    return {"backbone": "vgg16", "train_backbone_from": train_from, "precision": precision, "batch": B,
-            "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "step_tflop": round(total / 1e12, 3),
-            "step_tflops": round(total / (ms_train * 1e-3) / 1e12, 2), "step_frac_of_f32_mfma_peak": frac(total, ms_train),
-            "layers": layers}
+    return dict({"backbone": "vgg16", "train_backbone_from": train_from, "precision": precision, "batch": B,
+                 "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "step_tflop": round(total / 1e12, 3),
+                 "step_tflops": round(total / (ms_train * 1e-3) / 1e12, 2), "step_frac_of_f32_mfma_peak": frac(total, ms_train),
+                 "layers": layers}, **joint)
 
 
-def bench_mobilenet_span(train_from, precision, B, steps, warmup):
+def bench_mobilenet_span(train_from, precision, B, steps, warmup, feature_grad=False):
     """MobileNetV2 from `train_from` (block_7_expand .. block_13_expand): ms per training / evaluation step, and each new kernel family's
     single-layer entry on the block_12 shape (96 -> 576 -> 96 at F x F) with its fraction of its own floor: bytes / 8 TB/s for the
     BatchNorm and depthwise kernels, the float32-MFMA peak for the two GEMMs."""
@@ -179,6 +212,7 @@ def bench_mobilenet_span(train_from, precision, B, steps, warmup):
     imgs, deltas, lab = step_inputs(model, hp, B)
     model.compile(learning_rate=1e-5, train_backbone_from=train_from)
     ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
+    joint = feature_grad_times(model, imgs, deltas, lab, B, steps, warmup) if feature_grad else {}
     lib = L.lib()
     F = model.feature_map_shape
     P, C, Cs = B * F * F, 576, 96
@@ -216,11 +250,12 @@ def bench_mobilenet_span(train_from, precision, B, steps, warmup):
         ms = timed(run, steps, warmup)
         floor_ms = amount / (8e12 if kind == "bytes" else PEAK_F32_MFMA) * 1e3
         kernels[name] = {"ms": round(ms, 4), "floor_ms": round(floor_ms, 5), "frac_of_floor": round(floor_ms / ms, 3)}
-    return {"backbone": "mobilenet_v2", "train_backbone_from": train_from, "precision": precision, "batch": B,
-            "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "block_12_shape": [P, Cs, C], "kernels": kernels}
+    return dict({"backbone": "mobilenet_v2", "train_backbone_from": train_from, "precision": precision, "batch": B,
+                 "ms_train_step": round(ms_train, 3), "ms_eval_step": round(ms_eval, 3), "block_12_shape": [P, Cs, C], "kernels": kernels},
+                **joint)
 
 
-def bench_mobilenet_full(precision, B, steps, warmup):
+def bench_mobilenet_full(precision, B, steps, warmup, feature_grad=False):
     hp = train_utils.get_hyper_params("mobilenet_v2")
     model, _ = rpn_mobilenet_v2.get_model(hp, precision=precision, max_batch=B)
     imgs, deltas, lab = step_inputs(model, hp, B)
@@ -229,6 +264,7 @@ def bench_mobilenet_full(precision, B, steps, warmup):
     free0 = torch.cuda.mem_get_info()[0]
     ms_train, ms_eval = step_times(model, imgs, deltas, lab, B, steps, warmup)
     trainer_bytes = free0 - torch.cuda.mem_get_info()[0]               # the trainer allocates at its first step
+    joint = feature_grad_times(model, imgs, deltas, lab, B, steps, warmup) if feature_grad else {}
     lib = L.lib()
     s = L.stream_ptr
     img = hp["img_size"]
@@ -255,8 +291,8 @@ def bench_mobilenet_full(precision, B, steps, warmup):
             L.check(fn(), name)
         ms = timed(run, steps, warmup)
         kernels[name] = {"ms": round(ms, 4), "mbytes": round(nbytes / 1e6, 1), "tb_per_s": round(nbytes / ms / 1e9, 3)}
-    return {"backbone": "mobilenet_v2", "train_backbone": True, "precision": precision, "batch": B, "ms_train_step": round(ms_train, 3),
-            "ms_eval_step": round(ms_eval, 3), "trainer_device_gb": round(trainer_bytes / 1e9, 3), "kernels": kernels}
+    return dict({"backbone": "mobilenet_v2", "train_backbone": True, "precision": precision, "batch": B, "ms_train_step": round(ms_train, 3),
+                 "ms_eval_step": round(ms_eval, 3), "trainer_device_gb": round(trainer_bytes / 1e9, 3), "kernels": kernels}, **joint)
 
 
 def main():
@@ -272,24 +308,30 @@ def main():
                     help="with --train-backbone-from: the backbone (default vgg16); without: time that backbone's head-only step alone")
     ap.add_argument("--train-backbone", action="store_true",
                     help="time the trainer of compile(train_backbone=True): every layer of --backbone (default vgg16) trains")
+    ap.add_argument("--feature-grad", action="store_true",
+                    help="with --train-backbone / --train-backbone-from: also time the step in two halves with a second-stage gradient at "
+                         "the feature tap (forward_for_training + apply_gradients(G))")
     args = ap.parse_args()
+    if args.feature_grad and not (args.train_backbone or args.train_backbone_from):
+        ap.error("--feature-grad needs a trained backbone span: --train-backbone or --train-backbone-from")
     L.require_gpu()
+    fg = args.feature_grad
     if args.train_backbone:
         if args.train_backbone_from:
             ap.error("--train-backbone trains every layer: it cannot be combined with --train-backbone-from")
         if args.backbone == "mobilenet_v2":
-            print(json.dumps(bench_mobilenet_full(args.precision, args.batch, args.steps, args.warmup)), flush=True)
+            print(json.dumps(bench_mobilenet_full(args.precision, args.batch, args.steps, args.warmup, fg)), flush=True)
         else:
-            print(json.dumps(bench_backbone("block1_conv1", args.precision, args.batch, args.steps, args.warmup)), flush=True)
+            print(json.dumps(bench_backbone("block1_conv1", args.precision, args.batch, args.steps, args.warmup, fg)), flush=True)
         return
     if args.train_backbone_from and args.backbone == "mobilenet_v2":
-        print(json.dumps(bench_mobilenet_span(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        print(json.dumps(bench_mobilenet_span(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup, fg)), flush=True)
         return
     if args.backbone and not args.train_backbone_from:
         print(json.dumps(bench(args.backbone, args.precision, args.batch, args.steps, args.warmup)), flush=True)
         return
     if args.train_backbone_from:
-        print(json.dumps(bench_backbone(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        print(json.dumps(bench_backbone(args.train_backbone_from, args.precision, args.batch, args.steps, args.warmup, fg)), flush=True)
         return
     for backbone in ("vgg16", "mobilenet_v2"):
         print(json.dumps(bench(backbone, args.precision, args.batch, args.steps, args.warmup)), flush=True)

@@ -81,6 +81,9 @@ _SIGNATURES = {
     "rpn_head_trainer_step": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int] + [ctypes.c_float] * 4 + [vp, vp]),
     "rpn_head_trainer_steps": (ctypes.c_longlong, [vp]),
     "rpn_head_trainer_outputs": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, vp]),
+    "rpn_head_trainer_forward": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]),
+    "rpn_head_trainer_feature": (ctypes.c_int, [vp, vp, ctypes.c_int, vp]),
+    "rpn_head_trainer_backward": (ctypes.c_int, [vp, vp, ctypes.c_int, vp] + [ctypes.c_float] * 4 + [vp]),
     "rpn_model_trainer_create": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.POINTER(vp)]),
     "rpn_head_trainer_set_bn": (ctypes.c_int, [vp, ctypes.c_char_p] + [c_float_p] * 4),
     "rpn_head_trainer_get_bn": (ctypes.c_int, [vp, ctypes.c_char_p] + [c_float_p] * 4 + [vp]),
@@ -105,6 +108,7 @@ _SIGNATURES = {
     "rpn_conv3x3_dgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
     "rpn_conv3x3_dgrad_tile_n": (ctypes.c_int, [ctypes.c_int] * 4),
     "rpn_conv3x3_dgrad": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, ctypes.c_size_t, vp]),
+    "rpn_conv3x3_dgrad_add": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, ctypes.c_size_t, vp]),
     "rpn_maxpool2x2_backward": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_conv3x3_wgrad_wide_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "rpn_conv3x3_wgrad_wide": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]),

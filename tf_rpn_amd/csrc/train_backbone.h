@@ -7,11 +7,11 @@
 
 namespace rpn {
 
-// dgrad of a 3x3 stride-1 'same' conv: dx (B,H,W,Cin) = conv_transpose(dy (B,H,W,Cout), w HWIO), then dx *= [mask > 0] when mask is
-// given.  wt: 9 Cout Cin floats of device scratch that receive the flipped, transposed weights W'[r][s][co][ci] = W[2-r][2-s][ci][co].
-// Cin % 4 == 0, Cout % 16 == 0.
-hipError_t launch_conv3x3_dgrad(const float *dy, const float *w_hwio, const float *mask, int B, int H, int W, int Cin, int Cout, float *wt,
-                                float *dx, hipStream_t s);
+// dgrad of a 3x3 stride-1 'same' conv: dx (B,H,W,Cin) = conv_transpose(dy (B,H,W,Cout), w HWIO), then dx += add when add is given
+// (same shape as dx; it may be dx), then dx *= [mask > 0] when mask is given.  wt: 9 Cout Cin floats of device scratch that receive
+// the flipped, transposed weights W'[r][s][co][ci] = W[2-r][2-s][ci][co].  Cin % 4 == 0, Cout % 16 == 0.
+hipError_t launch_conv3x3_dgrad(const float *dy, const float *w_hwio, const float *mask, const float *add, int B, int H, int W, int Cin,
+                                int Cout, float *wt, float *dx, hipStream_t s);
 // whether the dgrad runs on the 128 x 128 tile (else 128 x 64): chosen from the shape alone, the bits are the same either way
 bool conv3x3_dgrad_wide_tile(int B, int H, int W, int Cin);
 

@@ -26,13 +26,19 @@ using f32x16b = __attribute__((ext_vector_type(16))) float;
 // W[8 - tap][ci][co] (dgrad_weights_kernel).  Workgroup: 128 pixels x 64 WN input channels, four waves of 64 x 32 WN; K slices of 16
 // (one tap, 16 output channels: Cout % 16 == 0) staged global -> registers -> LDS, double-buffered with one barrier per slice, as
 // conv3x3_wgrad_f32_kernel stages its operands.  The K order of every output is the same at every tile width: the same bits.
-// Epilogue: the ReLU mask of the layer's input (mask > 0), when given.
+// Epilogue: + add[o] when given (a gradient that reaches the same tensor by another path, read in place: same lane, same address as
+// the store, read before it, and dX carries no __restrict__ there, so add may be dX itself), then the ReLU mask of the layer's input (mask > 0), when given.
+// The add is chosen at compile time (ADD): conv3x3_dgrad_f32_kernel is the body without it, conv3x3_dgrad_add_f32_kernel with it.
 constexpr int kDgBM = 128, kDgBK = 16, kDgLdA = 160;   // A rows of 160 floats: the two half-waves of a fragment read hit disjoint banks
 
-template <int WN>
-__global__ void __launch_bounds__(256) conv3x3_dgrad_f32_kernel(const float *__restrict__ dY, const float *__restrict__ Wt,
-                                                              const float *__restrict__ mask, int B, int H, int W, int Cin, int Cout,
-                                                              float *__restrict__ dX)
+// dX is __restrict__ in the plain kernel only: with ADD the addend may BE dX (in place), so neither pointer may promise the other away
+template <bool ADD> struct DgradOut { using type = float *__restrict__; };
+template <> struct DgradOut<true> { using type = float *; };
+
+template <int WN, bool ADD>
+__device__ __forceinline__ void conv3x3_dgrad_f32_body(const float *__restrict__ dY, const float *__restrict__ Wt,
+                                                       const float *__restrict__ mask, const float *add, int B, int H, int W, int Cin,
+                                                       int Cout, typename DgradOut<ADD>::type dX)
 {
     constexpr int BN = 64 * WN, LDB = WN == 2 ? 160 : 96, QPR = BN / 4, RPP = 256 / QPR;   // quads per B row, B rows per pass
     __shared__ float As[2][kDgBK][kDgLdA];
@@ -126,10 +132,28 @@ __global__ void __launch_bounds__(256) conv3x3_dgrad_f32_kernel(const float *__r
                 if (p >= P) continue;
                 const size_t o = (size_t)p * Cin + col;
                 float v = acc[i][j][e];
+                if (ADD) v += add[o];
                 if (mask && !(mask[o] > 0.0f)) v = 0.0f;
                 dX[o] = v;
             }
         }
+}
+
+template <int WN>
+__global__ void __launch_bounds__(256) conv3x3_dgrad_f32_kernel(const float *__restrict__ dY, const float *__restrict__ Wt,
+                                                              const float *__restrict__ mask, int B, int H, int W, int Cin, int Cout,
+                                                              float *__restrict__ dX)
+{
+    conv3x3_dgrad_f32_body<WN, false>(dY, Wt, mask, nullptr, B, H, W, Cin, Cout, dX);
+}
+
+// the same tile with the addend in the epilogue: a kernel of its own, so that the plain one keeps its code and its registers
+template <int WN>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) conv3x3_dgrad_add_f32_kernel(const float *__restrict__ dY, const float *__restrict__ Wt,
+                                                                  const float *__restrict__ mask, const float *add, int B, int H, int W,
+                                                                  int Cin, int Cout, float *dX)
+{
+    conv3x3_dgrad_f32_body<WN, true>(dY, Wt, mask, add, B, H, W, Cin, Cout, dX);
 }
 
 // Wt[tap Cout + co][ci] = W[8 - tap][ci][co]
@@ -150,15 +174,21 @@ bool conv3x3_dgrad_wide_tile(int B, int H, int W, int Cin)
     return Cin >= 128 && mt * ((Cin + 127) / 128) >= 512;      // 128 x 128 tiles only when they still give two per CU of 256
 }
 
-hipError_t launch_conv3x3_dgrad(const float *dy, const float *w_hwio, const float *mask, int B, int H, int W, int Cin, int Cout, float *wt,
-                                float *dx, hipStream_t s)
+hipError_t launch_conv3x3_dgrad(const float *dy, const float *w_hwio, const float *mask, const float *add, int B, int H, int W, int Cin,
+                                int Cout, float *wt, float *dx, hipStream_t s)
 {
     hipLaunchKernelGGL(dgrad_weights_kernel, dim3(grid_1d(9LL * Cin * Cout)), dim3(256), 0, s, w_hwio, Cin, Cout, wt);
     const unsigned mt = (unsigned)(((long long)B * H * W + kDgBM - 1) / kDgBM);
-    if (conv3x3_dgrad_wide_tile(B, H, W, Cin))
-        hipLaunchKernelGGL(conv3x3_dgrad_f32_kernel<2>, dim3(mt, (Cin + 127) / 128), dim3(256), 0, s, dy, wt, mask, B, H, W, Cin, Cout, dx);
+    const bool wide = conv3x3_dgrad_wide_tile(B, H, W, Cin);
+    const dim3 grid(mt, wide ? (Cin + 127) / 128 : (Cin + 63) / 64);
+    if (wide && add)
+        hipLaunchKernelGGL(conv3x3_dgrad_add_f32_kernel<2>, grid, dim3(256), 0, s, dy, wt, mask, add, B, H, W, Cin, Cout, dx);
+    else if (wide)
+        hipLaunchKernelGGL(conv3x3_dgrad_f32_kernel<2>, grid, dim3(256), 0, s, dy, wt, mask, B, H, W, Cin, Cout, dx);
+    else if (add)
+        hipLaunchKernelGGL(conv3x3_dgrad_add_f32_kernel<1>, grid, dim3(256), 0, s, dy, wt, mask, add, B, H, W, Cin, Cout, dx);
     else
-        hipLaunchKernelGGL(conv3x3_dgrad_f32_kernel<1>, dim3(mt, (Cin + 63) / 64), dim3(256), 0, s, dy, wt, mask, B, H, W, Cin, Cout, dx);
+        hipLaunchKernelGGL(conv3x3_dgrad_f32_kernel<1>, grid, dim3(256), 0, s, dy, wt, mask, B, H, W, Cin, Cout, dx);
     return hipGetLastError();
 }
 
@@ -415,8 +445,26 @@ extern "C" int rpn_conv3x3_dgrad(const float *d_dy, const float *d_w, const floa
     const size_t need = rpn_conv3x3_dgrad_workspace_bytes(Cin, Cout);
     if (!d_ws || ws_bytes < need) return fail(RPN_ERR_WORKSPACE, "rpn_conv3x3_dgrad: %zu bytes of workspace needed", need);
     RPN_REQUIRE_DEVICE();
-    const hipError_t e = launch_conv3x3_dgrad(d_dy, d_w, d_mask, B, H, W, Cin, Cout, reinterpret_cast<float *>(d_ws), d_dx, as_stream(stream));
+    const hipError_t e = launch_conv3x3_dgrad(d_dy, d_w, d_mask, nullptr, B, H, W, Cin, Cout, reinterpret_cast<float *>(d_ws), d_dx,
+                                              as_stream(stream));
     return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_conv3x3_dgrad: %s", hipGetErrorString(e));
+}
+
+extern "C" int rpn_conv3x3_dgrad_add(const float *d_dy, const float *d_w, const float *d_mask, const float *d_add, int B, int H, int W,
+                                     int Cin, int Cout, float *d_dx, void *d_ws, size_t ws_bytes, void *stream)
+{
+    RPN_REQUIRE(d_dy && d_w && d_add && d_dx, "rpn_conv3x3_dgrad_add: null pointer");
+    RPN_REQUIRE(((uintptr_t)d_add & 3) == 0, "rpn_conv3x3_dgrad_add: d_add must be 4-byte aligned");
+    RPN_REQUIRE(B >= 1 && H >= 1 && W >= 1 && Cin >= 4 && Cout >= 16, "rpn_conv3x3_dgrad_add: bad shape");
+    RPN_REQUIRE(Cin % 4 == 0 && Cout % 16 == 0, "rpn_conv3x3_dgrad_add: Cin must be a multiple of 4 and Cout of 16");
+    RPN_REQUIRE((long long)9 * Cin * Cout <= (1ll << 30) && (long long)H * W <= (1 << 30) && (long long)B * H * W <= (1ll << 36),
+                "rpn_conv3x3_dgrad_add: layer too large");
+    const size_t need = rpn_conv3x3_dgrad_workspace_bytes(Cin, Cout);
+    if (!d_ws || ws_bytes < need) return fail(RPN_ERR_WORKSPACE, "rpn_conv3x3_dgrad_add: %zu bytes of workspace needed", need);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_conv3x3_dgrad(d_dy, d_w, d_mask, d_add, B, H, W, Cin, Cout, reinterpret_cast<float *>(d_ws), d_dx,
+                                              as_stream(stream));
+    return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_conv3x3_dgrad_add: %s", hipGetErrorString(e));
 }
 
 extern "C" int rpn_conv3x3_dgrad_tile_n(int B, int H, int W, int Cin)

@@ -502,6 +502,9 @@ struct rpn_head_trainer {
     bool loaded[3] = {false, false, false};     // rpn_conv, rpn_reg, rpn_cls
     long long t = 0;                            // applied Adam steps
     int last_B = 0;
+    int pending_B = 0;                          // the batch of a forward(train = 1) whose backward has not run yet; 0: none
+    const float *pending_imgs = nullptr;        // ... and its d_imgs
+    const float *d_tap = nullptr;               // the feature tap of the last forward (d_feat, or the VGG16 span's block5_conv3 output)
     float *d_w = nullptr, *d_g = nullptr, *d_m = nullptr, *d_v = nullptr;
     float *d_pconv = nullptr, *d_phead = nullptr;
     float *d_feat = nullptr, *d_S = nullptr, *d_reg = nullptr, *d_cls = nullptr, *d_graw = nullptr, *d_dz = nullptr, *d_dS = nullptr;
@@ -829,22 +832,24 @@ hipError_t backbone_forward(rpn_head_trainer *t, const float *d_imgs, int B, hip
 }
 
 // From dS (rpn_conv's pre-activation gradient) down to the first trained conv: dgrad (+ the ReLU mask of its input) or dgrad + the
-// max-pool backward (+ the mask of the pooled conv) between layers, the weight and bias gradient of each trained conv.
-hipError_t backbone_backward(rpn_head_trainer *t, int B, hipStream_t s)
+// max-pool backward (+ the mask of the pooled conv) between layers, the weight and bias gradient of each trained conv.  add (B,F,F,cin)
+// or NULL: a second stage's gradient with respect to the tap (the post-ReLU block5_conv3 output); it joins the RPN's gradient in the
+// first dgrad's epilogue, before block5_conv3's ReLU mask: (dgrad + add) [feat > 0].
+hipError_t backbone_backward(rpn_head_trainer *t, int B, const float *add, hipStream_t s)
 {
     float *g = t->d_grad[0], *h = t->d_grad[1];
     const int F = t->hs[12];
-    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, t->d_act[12], B, F, F, t->cin, 512, t->d_wt, g, s);
+    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, t->d_act[12], add, B, F, F, t->cin, 512, t->d_wt, g, s);
     for (int i = 12; i >= t->bb_from && e == hipSuccess; --i) {
         const int H = t->hs[i];
         const float *x = i == 0 ? t->d_img4 : (kVgg[i - 1].pool ? t->d_pool[i - 1] : t->d_act[i - 1]);
         e = launch_wgrad_wide(x, g, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wpart, t->d_g + t->off_bk[i], t->d_g + t->off_bb[i], s);
         if (e != hipSuccess || i == t->bb_from) break;
         if (kVgg[i - 1].pool) {
-            e = launch_conv3x3_dgrad(g, vgg_w(t, i), nullptr, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wt, h, s);
+            e = launch_conv3x3_dgrad(g, vgg_w(t, i), nullptr, nullptr, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wt, h, s);
             if (e == hipSuccess) e = launch_maxpool2x2_backward(t->d_act[i - 1], h, B, t->hs[i - 1], t->hs[i - 1], kVgg[i - 1].cout, g, s);
         } else {
-            e = launch_conv3x3_dgrad(g, vgg_w(t, i), t->d_act[i - 1], B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wt, h, s);
+            e = launch_conv3x3_dgrad(g, vgg_w(t, i), t->d_act[i - 1], nullptr, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d_wt, h, s);
             std::swap(g, h);
         }
     }
@@ -855,7 +860,7 @@ hipError_t backbone_backward(rpn_head_trainer *t, int B, hipStream_t s)
 // mn_x0; from Conv1 there is none: the span's input is the image batch).  train: BatchNorm normalises with the batch statistics and
 // updates the moving ones; else with the moving statistics (inference mode, nothing updated).  Every conv output z and every layer
 // output y is kept.  -> the block_13_expand output in d_feat.
-int mn_forward(rpn_head_trainer *t, const float *d_imgs, int B, bool train, hipStream_t s)
+int mn_forward(rpn_head_trainer *t, const char *what, const float *d_imgs, int B, bool train, hipStream_t s)
 {
     const std::vector<MnConv> &tab = mn_table();
     if (t->mn_from > 0) {
@@ -898,21 +903,23 @@ int mn_forward(rpn_head_trainer *t, const float *d_imgs, int B, bool train, hipS
         const float *res = (l.kind == 2 && l.res) ? (i - 2 == t->mn_from ? t->d_x0 : t->d_my[i - 3]) : nullptr;
         if (e == hipSuccess)
             e = launch_bn_apply(t->d_mz[i], P, l.cout, mean, rstd, t->d_w + t->off_mg[i], t->d_w + t->off_mb[i], l.kind != 2, res, t->d_my[i], s);
-        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: %s: %s", l.name.c_str(), hipGetErrorString(e));
+        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s: %s", what, l.name.c_str(), hipGetErrorString(e));
     }
     return RPN_OK;
 }
 
 // From dS (rpn_conv's pre-activation gradient) down to the first trained layer.  g: the gradient of the current layer's output.  A
 // residual block's output gradient stays in d_mgr[a] until the block's expand dgrad adds it to what that conv sends to the block's
-// input (the dgrad's epilogue: no atomics, no extra pass).
-hipError_t mn_backward(rpn_head_trainer *t, const float *d_imgs, int B, hipStream_t s)
+// input (the dgrad's epilogue: no atomics, no extra pass).  add (B,F,F,cin) or NULL: a second stage's gradient with respect to the
+// tap (block_13_expand after its ReLU6); it joins the RPN's gradient in the first dgrad's epilogue, and the BatchNorm backward that
+// follows applies the ReLU6 mask to the sum.
+hipError_t mn_backward(rpn_head_trainer *t, const float *d_imgs, int B, const float *add, hipStream_t s)
 {
     const std::vector<MnConv> &tab = mn_table();
     float *g = t->d_mt[1];
     const float *gres = nullptr;
     int a = 1;
-    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, nullptr, B, t->F, t->F, t->cin, 512, t->d_wt, g, s);
+    hipError_t e = launch_conv3x3_dgrad(t->d_dS, t->d_w + t->off_ck, nullptr, add, B, t->F, t->F, t->cin, 512, t->d_wt, g, s);
     for (int i = kMnLayers - 1; i >= t->mn_from && e == hipSuccess; --i) {
         const MnConv &l = tab[i];
         const int H = t->mn_hin[i], F = t->mn_hout[i];
@@ -1097,6 +1104,7 @@ extern "C" void rpn_head_trainer_destroy(rpn_head_trainer *t)
 extern "C" int rpn_head_trainer_set_layer(rpn_head_trainer *t, const char *name, const float *kernel, const float *bias)
 {
     RPN_REQUIRE(t && name && kernel, "rpn_head_trainer_set_layer: null argument");
+    t->pending_B = 0;                           // new parameters: a pending forward no longer matches them
     const int mi = t->mn_from >= 0 ? mn_index(name) : -1;
     if (mi >= 0) {
         // a MobileNetV2 conv of the span: the kernel alone (these convs have no bias; rpn_head_trainer_set_bn carries the BatchNorm)
@@ -1216,6 +1224,7 @@ extern "C" int rpn_head_trainer_set_bn(rpn_head_trainer *t, const char *name, co
                                        const float *var)
 {
     RPN_REQUIRE(t && name && gamma && beta && mean && var, "rpn_head_trainer_set_bn: null argument");
+    t->pending_B = 0;                           // new parameters: a pending forward no longer matches them
     const int mi = t->mn_from >= 0 ? mn_index(name, true) : -1;
     RPN_REQUIRE(mi >= 0, "rpn_head_trainer_set_bn: '%s' is not a BatchNorm this trainer trains", name);
     RPN_REQUIRE(mi >= t->mn_from, "rpn_head_trainer_set_bn: '%s' is frozen (training starts at %s): it runs on the model handle", name,
@@ -1278,22 +1287,44 @@ extern "C" int rpn_head_trainer_get_bn_gradient(rpn_head_trainer *t, const char 
     return trainer_read_bn(t, "rpn_head_trainer_get_bn_gradient", name, dgamma, dbeta, nullptr, nullptr, 1, stream);
 }
 
-extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
-                                     const float *d_bbox_labels, int update, float lr, float beta_1, float beta_2, float epsilon,
-                                     float *d_losses, void *stream)
+// ---- a step in two halves: forward + losses (+ the loss gradients), then head backward, backbone backward and Adam ------------------
+// `what` names the public entry in the messages.  rpn_head_trainer_step = both halves back to back: the same launches in the same
+// order on the same buffers as the closed call it was.
+static int trainer_check_forward(const rpn_head_trainer *t, const char *what, const float *d_imgs, int B, const float *d_bbox_deltas,
+                                 const float *d_bbox_labels, const float *d_losses)
 {
-    RPN_REQUIRE(t && d_imgs && d_bbox_deltas && d_bbox_labels && d_losses, "rpn_head_trainer_step: null argument");
-    RPN_REQUIRE(B >= 1 && B <= t->max_batch, "rpn_head_trainer_step: batch %d outside [1, %d]", B, t->max_batch);
-    RPN_REQUIRE(update == 0 || update == 1, "rpn_head_trainer_step: update must be 0 or 1");
-    RPN_REQUIRE(!update || (std::isfinite(lr) && lr >= 0.0f && beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f &&
-                            std::isfinite(epsilon) && epsilon >= 0.0f),
-                "rpn_head_trainer_step: bad Adam hyper-parameters");
-    for (int i = 0; i < 3; ++i) RPN_REQUIRE(t->loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kHeadLayers[i]);
+    RPN_REQUIRE(t && d_imgs && d_bbox_deltas && d_bbox_labels && d_losses, "%s: null argument", what);
+    RPN_REQUIRE(B >= 1 && B <= t->max_batch, "%s: batch %d outside [1, %d]", what, B, t->max_batch);
+    return RPN_OK;
+}
+
+static int trainer_check_adam(const char *what, float lr, float beta_1, float beta_2, float epsilon)
+{
+    RPN_REQUIRE(std::isfinite(lr) && lr >= 0.0f && beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f &&
+                    std::isfinite(epsilon) && epsilon >= 0.0f,
+                "%s: bad Adam hyper-parameters", what);
+    return RPN_OK;
+}
+
+static int trainer_check_loaded(const rpn_head_trainer *t, const char *what)
+{
+    for (int i = 0; i < 3; ++i) RPN_REQUIRE(t->loaded[i], "%s: layer '%s' was never set", what, kHeadLayers[i]);
     if (t->bb_from >= 0)
-        for (int i = 0; i < 13; ++i) RPN_REQUIRE(t->bb_loaded[i], "rpn_head_trainer_step: layer '%s' was never set", kVgg[i].name);
+        for (int i = 0; i < 13; ++i) RPN_REQUIRE(t->bb_loaded[i], "%s: layer '%s' was never set", what, kVgg[i].name);
     for (int i = std::max(t->mn_from, 0); t->mn_from >= 0 && i < kMnLayers; ++i)
-        RPN_REQUIRE(t->mn_loaded[i] && t->mn_bn_loaded[i], "rpn_head_trainer_step: layer '%s' or its BatchNorm was never set",
+        RPN_REQUIRE(t->mn_loaded[i] && t->mn_bn_loaded[i], "%s: layer '%s' or its BatchNorm was never set", what,
                     mn_table()[i].name.c_str());
+    return RPN_OK;
+}
+
+// the arguments are checked by the caller
+static int trainer_forward(rpn_head_trainer *t, const char *what, const float *d_imgs, int B, const float *d_bbox_deltas,
+                           const float *d_bbox_labels, int train, float *d_losses, void *stream)
+{
+    t->pending_B = 0;                           // whatever happens below, the buffers of an earlier forward are being overwritten:
+    t->pending_imgs = nullptr;                  // nothing is pending, and feature / outputs have nothing to return until this one is done
+    t->last_B = 0;
+    t->d_tap = nullptr;
     const int st = trainer_device(t);
     if (st != RPN_OK) return st;
     hipStream_t s = as_stream(stream);
@@ -1303,10 +1334,10 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
     if (t->bb_from >= 0) {
         // a trained backbone: the whole VGG16 in exact float32 from the trainer's weights
         const hipError_t eb = backbone_forward(t, d_imgs, B, s, &feat);
-        if (eb != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: backbone: %s", hipGetErrorString(eb));
+        if (eb != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: backbone: %s", what, hipGetErrorString(eb));
     } else if (t->mn_from >= 0) {
         // a trained MobileNetV2 span: BatchNorm in training mode on an update step, in inference mode on an evaluation
-        const int e0 = mn_forward(t, d_imgs, B, update != 0, s);
+        const int e0 = mn_forward(t, what, d_imgs, B, train != 0, s);
         if (e0 != RPN_OK) return e0;
     } else {
         const int e0 = model_features(t->m, d_imgs, B, t->d_feat, s);
@@ -1334,16 +1365,36 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
     float *graw_reg = t->d_graw, *graw_cls = t->d_graw + P * 4 * K;
     const long long n = P * K;                  // (B, A) with A = F F K
     if (e == hipSuccess)
-        e = launch_losses(d_bbox_deltas, t->d_reg, d_bbox_labels, t->d_cls, n, update ? graw_reg : nullptr,
-                          update ? graw_cls : nullptr, d_losses, 1, t->d_lws, s);
-    if (e == hipSuccess && update) {
-        hipLaunchKernelGGL(head_dz_kernel, dim3(grid_for(P * nc)), dim3(256), 0, s, graw_reg, graw_cls, t->d_cls, losses_scale(t->d_lws, n),
-                           P, K, t->d_dz);
-        const int chunks = (int)((P + kChunkRows - 1) / kChunkRows);
-        const int dgrid = (int)((P + 15) / 16);
-        // head_{w,d}grad are instantiated for the anchor counts of the reference's configurations (5 K = 45: 3 ratios x 3 scales)
-        // and the other small tables up to K = 12
-        switch (nc) {
+        e = launch_losses(d_bbox_deltas, t->d_reg, d_bbox_labels, t->d_cls, n, train ? graw_reg : nullptr, train ? graw_cls : nullptr,
+                          d_losses, 1, t->d_lws, s);
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    t->last_B = B;
+    t->d_tap = feat;
+    if (train) {
+        t->pending_B = B;
+        t->pending_imgs = d_imgs;
+    }
+    return RPN_OK;
+}
+
+// the pending forward's B and d_imgs and the Adam parameters are checked by the caller
+static int trainer_backward(rpn_head_trainer *t, const char *what, const float *d_imgs, int B, const float *d_feature_grad, float lr,
+                            float beta_1, float beta_2, float epsilon, void *stream)
+{
+    hipStream_t s = as_stream(stream);
+    const int F = t->F, K = t->K, nc = t->nc;
+    const long long P = (long long)B * F * F;
+    const long long n = P * K;
+    float *graw_reg = t->d_graw, *graw_cls = t->d_graw + P * 4 * K;
+    t->pending_B = 0;                           // consumed, whatever happens below
+    t->pending_imgs = nullptr;
+    hipLaunchKernelGGL(head_dz_kernel, dim3(grid_for(P * nc)), dim3(256), 0, s, graw_reg, graw_cls, t->d_cls, losses_scale(t->d_lws, n), P, K,
+                       t->d_dz);
+    const int chunks = (int)((P + kChunkRows - 1) / kChunkRows);
+    const int dgrid = (int)((P + 15) / 16);
+    // head_{w,d}grad are instantiated for the anchor counts of the reference's configurations (5 K = 45: 3 ratios x 3 scales)
+    // and the other small tables up to K = 12
+    switch (nc) {
 #define RPN_HEAD_NC(NCV)                                                                                                          \
     case NCV:                                                                                                                     \
         hipLaunchKernelGGL(head_wgrad_kernel<NCV>, dim3(chunks), dim3(256), 0, s, t->d_S, t->d_dz, P, t->d_part);                \
@@ -1351,26 +1402,78 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
                            t->d_g + t->off_hk);                                                                                   \
         hipLaunchKernelGGL(head_dgrad_kernel<NCV>, dim3(dgrid), dim3(512), 0, s, t->d_S, t->d_dz, t->d_w + t->off_hk, P, t->d_dS); \
         break;
-            RPN_HEAD_NC(5) RPN_HEAD_NC(10) RPN_HEAD_NC(15) RPN_HEAD_NC(20) RPN_HEAD_NC(25) RPN_HEAD_NC(30) RPN_HEAD_NC(35)
-            RPN_HEAD_NC(40) RPN_HEAD_NC(45) RPN_HEAD_NC(50) RPN_HEAD_NC(55) RPN_HEAD_NC(60)
+        RPN_HEAD_NC(5) RPN_HEAD_NC(10) RPN_HEAD_NC(15) RPN_HEAD_NC(20) RPN_HEAD_NC(25) RPN_HEAD_NC(30) RPN_HEAD_NC(35)
+        RPN_HEAD_NC(40) RPN_HEAD_NC(45) RPN_HEAD_NC(50) RPN_HEAD_NC(55) RPN_HEAD_NC(60)
 #undef RPN_HEAD_NC
-            default: return fail(RPN_ERR_UNSUPPORTED, "rpn_head_trainer_step: %d anchors per position", K);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = launch_wgrad(feat, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
-        if (e == hipSuccess) e = launch_colsum(t->d_dS, P, 512, t->d_part, t->d_g + t->off_cb, s);
-        if (e == hipSuccess && t->bb_from >= 0) e = backbone_backward(t, B, s);
-        if (e == hipSuccess && t->mn_from >= 0) e = mn_backward(t, d_imgs, B, s);
-        if (e == hipSuccess) {
-            ++t->t;
-            hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)t->n)), dim3(256), 0, s, t->d_w, t->d_g, t->d_m, t->d_v, (long long)t->n,
-                               t->t, lr, beta_1, beta_2, epsilon);
-            e = hipGetLastError();
-        }
+        default: return fail(RPN_ERR_UNSUPPORTED, "%s: %d anchors per position", what, K);
     }
-    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: %s", hipGetErrorString(e));
-    t->last_B = B;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_wgrad(t->d_tap, t->d_dS, B, F, F, t->cin, 512, t->d_part, t->d_g + t->off_ck, s);
+    if (e == hipSuccess) e = launch_colsum(t->d_dS, P, 512, t->d_part, t->d_g + t->off_cb, s);
+    if (e == hipSuccess && t->bb_from >= 0) e = backbone_backward(t, B, d_feature_grad, s);
+    if (e == hipSuccess && t->mn_from >= 0) e = mn_backward(t, d_imgs, B, d_feature_grad, s);
+    if (e == hipSuccess) {
+        ++t->t;
+        hipLaunchKernelGGL(adam_kernel, dim3(grid_for((long long)t->n)), dim3(256), 0, s, t->d_w, t->d_g, t->d_m, t->d_v, (long long)t->n,
+                           t->t, lr, beta_1, beta_2, epsilon);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", what, hipGetErrorString(e));
     return RPN_OK;
+}
+
+extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
+                                     const float *d_bbox_labels, int update, float lr, float beta_1, float beta_2, float epsilon,
+                                     float *d_losses, void *stream)
+{
+    const char *what = "rpn_head_trainer_step";
+    int st = trainer_check_forward(t, what, d_imgs, B, d_bbox_deltas, d_bbox_labels, d_losses);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(update == 0 || update == 1, "rpn_head_trainer_step: update must be 0 or 1");
+    if (update && (st = trainer_check_adam(what, lr, beta_1, beta_2, epsilon)) != RPN_OK) return st;
+    if ((st = trainer_check_loaded(t, what)) != RPN_OK) return st;
+    st = trainer_forward(t, what, d_imgs, B, d_bbox_deltas, d_bbox_labels, update, d_losses, stream);
+    if (st != RPN_OK || !update) return st;
+    return trainer_backward(t, what, d_imgs, B, nullptr, lr, beta_1, beta_2, epsilon, stream);
+}
+
+extern "C" int rpn_head_trainer_forward(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_bbox_deltas,
+                                        const float *d_bbox_labels, int train, float *d_losses, void *stream)
+{
+    const char *what = "rpn_head_trainer_forward";
+    int st = trainer_check_forward(t, what, d_imgs, B, d_bbox_deltas, d_bbox_labels, d_losses);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(train == 0 || train == 1, "rpn_head_trainer_forward: train must be 0 or 1");
+    if ((st = trainer_check_loaded(t, what)) != RPN_OK) return st;
+    return trainer_forward(t, what, d_imgs, B, d_bbox_deltas, d_bbox_labels, train, d_losses, stream);
+}
+
+extern "C" int rpn_head_trainer_feature(rpn_head_trainer *t, float *d_out, int B, void *stream)
+{
+    RPN_REQUIRE(t && d_out, "rpn_head_trainer_feature: null argument");
+    RPN_REQUIRE(B >= 1 && B == t->last_B && t->d_tap, "rpn_head_trainer_feature: batch %d, the last forward ran %d images", B, t->last_B);
+    RPN_REQUIRE_DEVICE();
+    RPN_HIP_CHECK(hipMemcpyAsync(d_out, t->d_tap, (size_t)B * t->F * t->F * t->cin * sizeof(float), hipMemcpyDeviceToDevice,
+                                 as_stream(stream)));
+    return RPN_OK;
+}
+
+extern "C" int rpn_head_trainer_backward(rpn_head_trainer *t, const float *d_imgs, int B, const float *d_feature_grad, float lr,
+                                         float beta_1, float beta_2, float epsilon, void *stream)
+{
+    const char *what = "rpn_head_trainer_backward";
+    RPN_REQUIRE(t, "rpn_head_trainer_backward: null argument");
+    RPN_REQUIRE(!d_feature_grad || t->bb_from >= 0 || t->mn_from >= 0,
+                "rpn_head_trainer_backward: d_feature_grad given to a trainer with a frozen backbone: nothing below the feature tap trains "
+                "(create the trainer with rpn_model_trainer_create and a train_from layer)");
+    RPN_REQUIRE(d_imgs, "rpn_head_trainer_backward: null argument");
+    const int st = trainer_check_adam(what, lr, beta_1, beta_2, epsilon);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(t->pending_B > 0, "rpn_head_trainer_backward: no pending rpn_head_trainer_forward with train = 1 on this trainer");
+    RPN_REQUIRE(B == t->pending_B, "rpn_head_trainer_backward: batch %d, the pending forward ran %d images", B, t->pending_B);
+    RPN_REQUIRE(d_imgs == t->pending_imgs, "rpn_head_trainer_backward: d_imgs is not the pending forward's image batch");
+    RPN_REQUIRE(((uintptr_t)d_feature_grad & 3) == 0, "rpn_head_trainer_backward: d_feature_grad must be 4-byte aligned");
+    return trainer_backward(t, what, d_imgs, B, d_feature_grad, lr, beta_1, beta_2, epsilon, stream);
 }
 
 extern "C" long long rpn_head_trainer_steps(const rpn_head_trainer *t) { return t ? t->t : -1; }

@@ -97,6 +97,7 @@ class RPNModel(object):
         self._opt = None
         self._train_from = None         # first trained backbone layer, None: the head only
         self._head_dirty = False        # the trainer's head differs from the handle's: copied before the next inference
+        self._pending = None            # (image batch, B) of a forward_for_training that apply_gradients has not consumed
 
     # ---- introspection ----------------------------------------------------------------
     def _enumerate_layers(self):
@@ -387,6 +388,7 @@ class RPNModel(object):
             L.check(L.lib().rpn_model_trainer_create(self._h, train_backbone_from.encode(), ctypes.byref(t)),
                     "rpn_model_trainer_create")
         self._t = t
+        self._pending = None
         self._train_from = train_backbone_from
         for name in self._head:
             self._trainer_set(name)
@@ -514,7 +516,7 @@ class RPNModel(object):
                     "rpn_model_set_layer(%s)" % name)
         self._head_dirty = False
 
-    def _step(self, x, y, update):
+    def _batch_args(self, x, y):
         if not self._t:
             raise RuntimeError("call compile() before training or evaluating the model")
         if not isinstance(y, (tuple, list)) or len(y) != 2:
@@ -531,6 +533,11 @@ class RPNModel(object):
                              % (F * F * K, F, F, K, tuple(deltas.shape), tuple(labels.shape)))
         if not 1 <= B <= self.max_batch:
             raise ValueError("batch %d outside [1, %d]" % (B, self.max_batch))
+        return imgs, deltas, labels, B
+
+    def _step(self, x, y, update):
+        imgs, deltas, labels, B = self._batch_args(x, y)
+        self._pending = None                    # the library's forward replaces a pending one
         losses = torch.empty((3,), dtype=torch.float32, device="cuda")
         lr, b1, b2, eps = self._opt
         L.check(L.lib().rpn_head_trainer_step(self._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(labels), 1 if update else 0, lr, b1,
@@ -539,11 +546,104 @@ class RPNModel(object):
             self._head_dirty = True
         return losses, B
 
-    def train_on_batch(self, x, y):
+    def _trainer_outputs(self, B):
+        F, K = self.feature_map_shape, self.anchor_count
+        reg = torch.empty((B, F, F, 4 * K), dtype=torch.float32, device="cuda")
+        cls = torch.empty((B, F, F, K), dtype=torch.float32, device="cuda")
+        L.check(L.lib().rpn_head_trainer_outputs(self._t, L.ptr(reg), L.ptr(cls), B, L.stream_ptr()), "rpn_head_trainer_outputs")
+        return [reg, cls]
+
+    def forward_for_training(self, x, y):
+        """The first half of a training step: forward pass and losses, nothing updated yet -> ``(losses, feat, [reg, cls])``.
+
+        ``losses``: CUDA tensor [loss, rpn_reg_loss, rpn_cls_loss] (not read back: no host synchronisation).  ``feat``: a fresh
+        float32 CUDA tensor (B,F,F,C), the trainer's own feature tap -- ``block5_conv3`` after its ReLU / ``block_13_expand`` after
+        its ReLU6, computed in exact float32 from the master weights, BatchNorm with the batch statistics on MobileNetV2 -- that the
+        caller may set ``requires_grad_()`` on and build a second-stage loss from.  ``[reg, cls]``: the float32 head outputs.
+        ``apply_gradients`` runs the second half.  A later ``forward_for_training`` / ``train_on_batch`` / ``test_on_batch`` replaces
+        the pending forward (on MobileNetV2 the moving BatchNorm statistics are updated by every training forward)."""
+        imgs, deltas, labels, B = self._batch_args(x, y)
+        self._pending = None
+        losses = torch.empty((3,), dtype=torch.float32, device="cuda")
+        L.check(L.lib().rpn_head_trainer_forward(self._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(labels), 1, L.ptr(losses),
+                                                 L.stream_ptr()), "rpn_head_trainer_forward")
+        self._pending = (imgs, B)               # the backward reads the same image batch: keep it alive
+        if self._train_from is not None and self.backbone != "vgg16":
+            self._head_dirty = True             # the moving statistics moved
+        C = self.activation_shape(self.tap_layer)[3]
+        feat = torch.empty((B, self.feature_map_shape, self.feature_map_shape, C), dtype=torch.float32, device="cuda")
+        L.check(L.lib().rpn_head_trainer_feature(self._t, L.ptr(feat), B, L.stream_ptr()), "rpn_head_trainer_feature")
+        return losses, feat, self._trainer_outputs(B)
+
+    def apply_gradients(self, feature_grad=None):
+        """The second half of the step ``forward_for_training`` began: head backward, backbone backward, one Adam step.
+
+        ``feature_grad``: None, or a contiguous float32 CUDA tensor (B,F,F,C) -- the gradient of a second-stage loss with respect to
+        ``feat``; the backbone then trains on the RPN's gradient plus this one (it enters before the tap's activation mask).  The
+        head layers' gradients do not depend on it.  ValueError for a bad tensor, and for any ``feature_grad`` on a model compiled
+        without a backbone span (nothing below the tap trains); RuntimeError without a pending ``forward_for_training``."""
+        if not self._t:
+            raise RuntimeError("call compile() before training or evaluating the model")
+        if feature_grad is not None and self._train_from is None:
+            # (rpn_head_trainer_backward refuses the same call with the same reason, for callers of the C ABI)
+            raise ValueError("feature_grad given to a model compiled with a frozen backbone: nothing below the feature tap trains, so "
+                             "the gradient would be dropped -- compile with train_backbone_from=<layer> or train_backbone=True")
+        F = self.feature_map_shape
+        C = self.activation_shape(self.tap_layer)[3]
+        pend = self._pending
+        if feature_grad is not None:
+            g = feature_grad
+            if not isinstance(g, torch.Tensor):
+                raise ValueError("feature_grad must be a torch tensor, got %s" % type(g).__name__)
+            ok_b = int(g.shape[0]) == pend[1] if (pend and g.dim() == 4) else (g.dim() == 4 and 1 <= int(g.shape[0]) <= self.max_batch)
+            if g.dim() != 4 or tuple(g.shape[1:]) != (F, F, C) or not ok_b:
+                raise ValueError("feature_grad must be (%s,%d,%d,%d), the shape of forward_for_training's feat; got %s"
+                                 % (pend[1] if pend else "B", F, F, C, tuple(g.shape)))
+            if g.dtype != torch.float32 or not g.is_contiguous() or not g.is_cuda:
+                raise ValueError("feature_grad must be a contiguous float32 CUDA tensor, got %s on %s%s"
+                                 % (g.dtype, g.device, "" if g.is_contiguous() else ", not contiguous"))
+        if pend is None:
+            raise RuntimeError("apply_gradients needs a pending forward_for_training (each one is applied once; train_on_batch and "
+                               "test_on_batch replace it)")
+        imgs, B = pend
+        self._pending = None
+        lr, b1, b2, eps = self._opt
+        L.check(L.lib().rpn_head_trainer_backward(self._t, L.ptr(imgs), B, L.ptr(feature_grad), lr, b1, b2, eps, L.stream_ptr()),
+                "rpn_head_trainer_backward")
+        self._head_dirty = True
+
+    def train_on_batch(self, x, y, second_stage=None):
         """One Adam step on ``y = (bbox_deltas, bbox_labels)`` (what ``rpn_generator`` yields) -> [loss, rpn_reg_loss,
-        rpn_cls_loss], computed with the weights before the update (Keras order; loss = reg_loss + cls_loss, unit weights)."""
-        losses, _ = self._step(x, y, True)
-        return [float(v) for v in losses.cpu().numpy()]
+        rpn_cls_loss], computed with the weights before the update (Keras order; loss = reg_loss + cls_loss, unit weights).
+
+        ``second_stage(feat, reg, cls)``: joint training.  It gets the trainer's float32 feature tap (requiring grad) and the head
+        outputs of this step and returns a scalar torch loss built from ``feat`` with torch operations (``roi_utils.roi_pooling``
+        first, typically).  The model calls ``.backward()`` on it and hands ``feat.grad`` to the backbone's backward (a loss that does
+        not touch ``feat`` gives none: the plain step); the caller steps its own optimizer for the second stage's parameters.  Returns
+        [loss + second, rpn_reg_loss, rpn_cls_loss, second].  Needs a trained backbone span (``train_backbone_from`` /
+        ``train_backbone``).  Everything stays on the current stream; the one host synchronisation is the losses' readback."""
+        if second_stage is None:
+            losses, _ = self._step(x, y, True)
+            return [float(v) for v in losses.cpu().numpy()]
+        if not self._t:
+            raise RuntimeError("call compile() before training or evaluating the model")
+        if self._train_from is None:
+            raise ValueError("second_stage needs a trained backbone span: this model was compiled with a frozen backbone, so nothing "
+                             "below the feature tap trains and the second stage's gradient would be dropped -- compile with "
+                             "train_backbone_from=<layer> or train_backbone=True")
+        losses, feat, (reg, cls) = self.forward_for_training(x, y)
+        feat.requires_grad_()
+        with torch.enable_grad():
+            second = second_stage(feat, reg, cls)
+        if not isinstance(second, torch.Tensor) or second.numel() != 1 or not second.requires_grad:
+            self._pending = None
+            raise ValueError("second_stage must return a scalar torch loss that requires grad")
+        second.backward()
+        g = feat.grad
+        self.apply_gradients(None if g is None else g.contiguous())
+        vals = torch.cat([losses, second.detach().reshape(1).to(device="cuda", dtype=torch.float32)]).cpu().numpy()
+        total = np.float32(np.float32(vals[1] + vals[2]) + vals[3])
+        return [float(total), float(vals[1]), float(vals[2]), float(vals[3])]
 
     def test_on_batch(self, x, y, return_outputs=False):
         """[loss, rpn_reg_loss, rpn_cls_loss] without an update (Adam's t is not advanced).  ``return_outputs``: also the
@@ -552,32 +652,30 @@ class RPNModel(object):
         out = [float(v) for v in losses.cpu().numpy()]
         if not return_outputs:
             return out
-        F, K = self.feature_map_shape, self.anchor_count
-        reg = torch.empty((B, F, F, 4 * K), dtype=torch.float32, device="cuda")
-        cls = torch.empty((B, F, F, K), dtype=torch.float32, device="cuda")
-        L.check(L.lib().rpn_head_trainer_outputs(self._t, L.ptr(reg), L.ptr(cls), B, L.stream_ptr()), "rpn_head_trainer_outputs")
-        return out, [reg, cls]
+        return out, self._trainer_outputs(B)
 
     def train_steps(self):
         """Adam's t: the number of applied steps since compile."""
         return int(L.lib().rpn_head_trainer_steps(self._t)) if self._t else 0
 
-    def fit(self, generator, steps_per_epoch, epochs=1, validation_data=None, validation_steps=None):
+    def fit(self, generator, steps_per_epoch, epochs=1, validation_data=None, validation_steps=None, second_stage=None):
         """trainer.py:64-69 without the ModelCheckpoint callback: ``steps_per_epoch`` batches of ``generator`` per epoch, then
         ``validation_steps`` batches of ``validation_data`` evaluated.  Returns the history dict of the per-epoch means:
-        {"loss", "rpn_reg_loss", "rpn_cls_loss"} (+ the same with a "val_" prefix)."""
+        {"loss", "rpn_reg_loss", "rpn_cls_loss"} (+ the same with a "val_" prefix).  ``second_stage``: passed to every
+        ``train_on_batch`` (joint training); the history then has "second_stage_loss" too, and "loss" includes it."""
         keys = ("loss", "rpn_reg_loss", "rpn_cls_loss")
-        history = {k: [] for k in keys}
+        tkeys = keys + (("second_stage_loss",) if second_stage is not None else ())
+        history = {k: [] for k in tkeys}
         if validation_data is not None:
             history.update({"val_" + k: [] for k in keys})
         it = iter(generator)
         vit = iter(validation_data) if validation_data is not None else None
         for _epoch in range(int(epochs)):
-            sums = np.zeros(3)
+            sums = np.zeros(len(tkeys))
             for _ in range(int(steps_per_epoch)):
                 x, y = next(it)
-                sums += self.train_on_batch(x, y)
-            for k, v in zip(keys, sums / max(1, int(steps_per_epoch))):
+                sums += self.train_on_batch(x, y) if second_stage is None else self.train_on_batch(x, y, second_stage=second_stage)
+            for k, v in zip(tkeys, sums / max(1, int(steps_per_epoch))):
                 history[k].append(float(v))
             if vit is not None:
                 n = int(validation_steps) if validation_steps else 1
