@@ -256,7 +256,8 @@ int rpn_model_get_profile(rpn_model *m, float *ms, int n, int *n_forwards);
  * Training of the RPN head on a FROZEN backbone                   trainer.py:54-69
  *   The reference fine-tunes the whole Keras model (its base model is trainable); rpn_head_trainer_create trains rpn_conv,
  *   rpn_reg and rpn_cls only (rpn_model_trainer_create below adds backbone layers).  The loss and Adam forms are TF 2.0.0's,
- *   restated from its sources as recalled (tf_rpn_amd/csrc/train_kernels.hip).  Every reduction has a fixed order and
+ *   restated from its sources as recalled (tf_rpn_amd/csrc/train_kernels.hip, with the kernels; the trainer that runs them is
+ *   tf_rpn_amd/csrc/trainer.hip).  Every reduction has a fixed order and
  *   there are no floating-point atomics: a call is bit-identical from run to run.
  *
  * reg_loss(y_true, y_pred) + cls_loss(y_true, y_pred)      utils/train_utils.py:164-185, :146-162

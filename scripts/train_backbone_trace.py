@@ -5,7 +5,7 @@
     python scripts/train_backbone_trace.py OUT/run_kernel_trace.csv --train-backbone-from block1_conv1
 
 A training step ends with its one adam_kernel dispatch.  Between the previous step's adam_kernel (or the start of the trace) and
-this one, the backward's dispatches come in a fixed order (train_kernels.hip, backbone_backward): conv3x3_dgrad_f32_kernel for
+this one, the backward's dispatches come in a fixed order (trainer.hip, backbone_backward): conv3x3_dgrad_f32_kernel for
 rpn_conv's input first, then for conv i = 12 .. first trained: conv3x3_wgrad_wide_f32_kernel (+ wgrad_tree_kernel levels +
 wgrad_wide_finish_kernel), then, above the first trained conv, conv3x3_dgrad_f32_kernel (+ maxpool2x2_backward_kernel where a pool
 sits below).  Each dispatch is attributed to its layer by that order; the evaluation steps and single-layer timings the bench runs

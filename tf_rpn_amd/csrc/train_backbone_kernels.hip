@@ -1,6 +1,6 @@
 // train_backbone_kernels.hip -- the backward pass of the VGG16 backbone (reference models/rpn_vgg16.py:16-21: the Keras base model is
 // trainable, trainer.py:54-69 compiles and fits all of it): 3x3 input gradients (dgrad), 3x3 weight + bias gradients at backbone
-// shapes (wgrad_wide) and the MaxPooling2D(2, 2) backward.  The training step that chains them lives in train_kernels.hip.
+// shapes (wgrad_wide) and the MaxPooling2D(2, 2) backward.  The training step that chains them lives in trainer.hip.
 //
 // Gradient forms (TF 2.0.0, restated from its sources as recalled -- nothing here can run TF):
 //   ReluGrad(grad, op.outputs[0]):  dY * [Y > 0], Y the ReLU OUTPUT (nn_grad.py _ReluGrad).

@@ -1,0 +1,43 @@
+// train_head.h -- host-side interface of the RPN losses, the head's backward kernels, the 3x3 weight gradient at the head's shape and
+// Adam (train_kernels.hip; internal to librpn_hip.so).  Every kernel is float32 (float64 sums inside the losses), writes each output
+// once and uses no floating-point atomics: every sum has a fixed order.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+namespace rpn {
+
+// ---- rpn_reg_loss / rpn_cls_loss over the n = B A anchors: reg (n, 4), cls (n) -----------------------------------------------------
+// out: [reg, cls] or, with_total, [reg + cls, reg, cls]; graw_reg / graw_cls (or null): the UNSCALED gradients with respect to the
+// predictions.  ws: losses_ws_bytes(n) bytes of device scratch; the two gradient scales {1 / max(1, n_pos), 1 / n_valid or 0} land
+// at its end, where losses_scale(ws, n) points.
+size_t losses_ws_bytes(long long n);
+float *losses_scale(void *ws, long long n);
+hipError_t launch_losses(const float *reg_true, const float *reg_pred, const float *cls_true, const float *cls_pred, long long n,
+                         float *graw_reg, float *graw_cls, float *out, int with_total, void *ws, hipStream_t s);
+
+// ---- out (C) = the column sums of x (rows, C): chunks of 64 rows in order, then the chunks in order --------------------------------
+// part: colsum_ws_floats(rows, C) floats of device scratch
+size_t colsum_ws_floats(long long rows, int C);
+hipError_t launch_colsum(const float *x, long long rows, int C, float *part, float *out, hipStream_t s);
+
+// ---- dw (3,3,Cin,Cout) HWIO = the weight gradient of a 3x3 stride-1 'same' conv, x (B,H,W,Cin), dy (B,H,W,Cout) -----------------------
+// four fixed ranges of pixels added as (l0 + l1) + (l2 + l3).  Cin % 4 == 0, Cout % 4 == 0.  part: wgrad_ws_floats(Cin, Cout) floats.
+size_t wgrad_ws_floats(int Cin, int Cout);
+hipError_t launch_wgrad(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, hipStream_t s);
+
+// ---- the fused 1x1 head (512 -> nc = 5 K columns: rpn_reg, then rpn_cls) backward over P pixels ------------------------------------
+// dz (P, nc) = [graw_reg * scale[0] | graw_cls * scale[1] * cls (1 - cls)]; dw_head (513, nc) = S^T dz (rows 0 .. 511: the kernel's
+// gradient) and sum dz (row 512: the bias's); dS (P, 512) = (dz w_head^T) * [S > 0].  part: head_backward_ws_floats(P, nc) floats.
+// *supported = false and nothing after dz launched when nc is no instantiated width (5, 10 .. 60).
+size_t head_backward_ws_floats(long long P, int nc);
+hipError_t launch_head_backward(const float *graw_reg, const float *graw_cls, const float *cls, const float *scale, const float *S,
+                                const float *w_head, long long P, int K, float *dz, float *part, float *dw_head, float *dS,
+                                bool *supported, hipStream_t s);
+
+// ---- Adam (ApplyAdam) over one flat buffer of n floats; t: the number of this step, from 1 ---------------------------------------
+hipError_t launch_adam(float *w, const float *g, float *m, float *v, long long n, long long t, float lr, float b1, float b2, float eps,
+                       hipStream_t s);
+
+}  // namespace rpn

@@ -1,6 +1,6 @@
 // train_mnv2_kernels.hip -- backward of MobileNetV2 (Conv1, expanded_conv, block_1 .. block_12, block_13_expand): BatchNorm in
 // training mode, the 1x1 convs on the float32 MFMA, the depthwise 3x3 convs (stride 1 'same'; stride 2 behind Keras' correct_pad) and
-// the stem's weight gradient.  The trainer that strings them together is in train_kernels.hip (mn_forward / mn_backward).
+// the stem's weight gradient.  The trainer that strings them together is in trainer.hip (mn_forward / mn_backward).
 //
 // BatchNorm form (TF 2.0's fused BatchNorm, restated as recalled -- nothing here can run TF): over the N = B H W pixels of a channel,
 //   mean = sum x / N, var = sum (x - mean)^2 / N (biased), xhat = (x - mean) / sqrt(var + eps), y = gamma xhat + beta;
