@@ -487,6 +487,57 @@ int rpn_roi_pool_backward(const float *d_dy, const float *d_rois, const int *d_v
 int rpn_model_roi_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, const int *d_valid, float *d_out,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Second stage around RoI pooling: targets, losses, detections (no reference counterpart: the reference stops at the proposals;
+ * thresholds and sampling rule are this project's choice).  The counterparts of rpn_rpn_targets / rpn_rpn_losses / rpn_decode_nms.
+ * Everything on `stream`, no host synchronisation, no floating-point atomics: bit-identical from run to run.
+ *
+ * rpn_roi_targets: which proposal trains on which ground-truth box.
+ *   d_rois (B,R,4) normalised [y1,x1,y2,x2]; d_valid (B,) int32 or NULL: rows r >= valid[b] are padding (what rpn_decode_nms
+ *   returns); d_gt_boxes (B,G,4); d_gt_labels (B,G) int32: a gt row is valid iff its label is >= 1 (0 is background, padding is -1);
+ *   variances: HOST pointer, 4 floats; d_random_pos / d_random_neg (B,R) int32 >= 1: the sampling priorities.
+ *   float32, every operation rounded on its own, the arithmetic of generate_iou_map / get_deltas_from_bboxes.  Per live row:
+ *     best = 0, arg = none; for valid gt g in index order: iou = IoU(roi, gt[g]); if (iou > best) { best = iou; arg = g; }
+ *   (strict: the first maximum wins, a NaN never wins, an IoU of 0 never sets arg).
+ *   Positive candidates: live rows with best > pos_iou; the total_pos of highest random_pos priority are kept, ties to the lower
+ *   index.  Negative candidates: live rows not kept as positives with neg_lo <= best < neg_hi; total_pos + total_neg - n_pos_kept
+ *   of them are kept by random_neg the same way (the batch fills up with negatives, as the RPN targets do).
+ *   d_roi_labels (B,R) int32: the matched gt's label for a kept positive, 0 for a kept negative, -1 otherwise (padding included).
+ *   d_roi_deltas (B,R,4): encode(roi, gt[arg]) / variances for a kept positive, exactly +0.0 everywhere else.
+ *   B, R, G >= 1, G <= 2048, 0 <= neg_lo <= neg_hi, pos_iou >= 0; d_workspace: rpn_roi_targets_workspace_bytes(B, R, G) bytes.
+ *   One launch, one workgroup per image; the (B,R,G) IoU map is never written.
+ *
+ * rpn_roi_losses: the detection head's two losses and, optionally, their gradients.
+ *   d_cls_logits (B,R,C) LOGITS (not probabilities); d_reg_pred (B,R,4C) class-specific boxes; d_roi_labels (B,R) int32;
+ *   d_roi_deltas (B,R,4).  A row whose label is outside [0, C) is ignored by both losses and never indexes memory.
+ *     cls_loss = sum over kept rows of (logsumexp(logits) - logits[label]) / max(1, n_kept)
+ *     reg_loss = sum over rows with label >= 1 of sum_k huber_1(pred[4 label + k] - delta[k]) / max(1, n_pos),
+ *                huber_1(e) = 0.5 q^2 + (|e| - q), q = min(|e|, 1)
+ *   d_losses = [reg_loss, cls_loss] (the order of rpn_rpn_losses).  With no kept row / no positive row the loss is 0 and its
+ *   gradient all zeros: NO NaN -- on purpose unlike rpn_rpn_losses, whose cls_loss is Keras' mean of an empty tensor.
+ *   d_grad_logits (B,R,C) or NULL: (softmax - onehot) / n_kept on kept rows, 0 elsewhere.  d_grad_reg (B,R,4C) or NULL:
+ *   clamp(pred - delta, -1, 1) / n_pos on the four entries of the labelled class of positive rows, 0 elsewhere.  Each is the
+ *   gradient of its own loss and is written in full.  Sums in float64, per-thread partials then a fixed tree.
+ *   d_workspace: rpn_roi_losses_workspace_bytes(B, R, C) bytes.
+ *
+ * rpn_roi_decode_scores: head outputs -> what rpn_combined_nms takes (q == C).
+ *   d_boxes (B,R,C,4): boxes[b,r,c] = decode(rois[b,r], reg_pred[b,r,c] * variances), bit-identical to rpn_decode on the expanded
+ *   tensors; not clipped; every row is decoded.  d_scores (B,R,C): softmax(logits[b,r])[c] for c >= 1 on a live row; exactly 0 for
+ *   background (c == 0) and for rows r >= valid[b] -- run the NMS with a score threshold above 0.  variances: HOST pointer.
+ * d_rois, d_gt_boxes, d_roi_deltas, d_reg_pred, d_grad_reg, d_boxes 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+size_t rpn_roi_targets_workspace_bytes(int B, int R, int G);
+int rpn_roi_targets(const float *d_rois, const int32_t *d_valid, const float *d_gt_boxes, const int32_t *d_gt_labels, int B, int R,
+                    int G, int total_pos, int total_neg, float pos_iou, float neg_lo, float neg_hi, const float *variances,
+                    const int32_t *d_random_pos, const int32_t *d_random_neg, float *d_roi_deltas, int32_t *d_roi_labels,
+                    void *d_workspace, size_t workspace_bytes, void *stream);
+size_t rpn_roi_losses_workspace_bytes(int B, int R, int C);
+int rpn_roi_losses(const float *d_cls_logits, const float *d_reg_pred, const int32_t *d_roi_labels, const float *d_roi_deltas, int B,
+                   int R, int C, float *d_losses, float *d_grad_logits, float *d_grad_reg, void *d_workspace, size_t workspace_bytes,
+                   void *stream);
+int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const float *d_reg_pred, const float *d_cls_logits,
+                          const float *variances, int B, int R, int C, float *d_boxes, float *d_scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

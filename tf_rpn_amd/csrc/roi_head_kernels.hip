@@ -1,0 +1,416 @@
+// roi_head_kernels.hip -- what a Faster R-CNN second stage needs around RoI pooling: which proposal trains on which ground-truth
+// box (rpn_roi_targets), the detection head's two losses with their gradients (rpn_roi_losses), and head outputs -> per-class boxes
+// and scores in front of the NMS (rpn_roi_decode_scores).  The second-stage counterparts of rpn_rpn_targets / rpn_rpn_losses /
+// rpn_decode_nms.
+//
+// No reference counterpart: the reference stops at the proposals.  The thresholds and the sampling rule are this project's choice
+// (the usual Faster R-CNN ones: IoU above 0.5 positive, [0.1, 0.5) negative, a fixed batch per image filled up with negatives), the
+// box arithmetic is the reference's (bbox_core.h), and the subsampling is the one of its RPN targets (target_kernels.hip): exact top-K
+// by an explicit random priority, ties to the lower index.
+//
+//   roi_target_kernel     : one 1024-thread workgroup per image.  The gt boxes, their areas and their validity are staged in LDS
+//                           (1024 at a time); every thread walks its RoIs (r = tid, tid + 1024, ...) with max IoU / first argmax
+//                           in registers and writes them to the (B,R) workspace; two radix selects (positives, then negatives) and
+//                           the output pass follow in the same workgroup.  The (B,R,G) IoU map is never written; no memset, no
+//                           atomics on global memory.
+//                           HBM: 16 R + 20 G read, 8 R written and re-read (workspace, L2-resident), 8 R priorities read, 20 R
+//                           written, per image.
+//   roi_loss_kernel       : one thread per RoI row: max, sum of exp and the cross-entropy of kept rows, the Huber sum of positive
+//                           rows, all in float64; per-row (max, 1 / sum) to the workspace; block partials after a fixed LDS tree.
+//   roi_loss_finish_kernel: the partials in a fixed tree -> [reg_loss, cls_loss] and the two gradient scales.
+//   roi_loss_grad_kernel  : elementwise over (B R, C): grad_logits = (softmax - onehot) * scale, and the float4 of grad_reg that
+//                           belongs to (row, class).  Both tensors written in full.
+//                           HBM: 20 C + 20 read per row by the first kernel, 20 C read and 20 C written per row by the last.
+//   roi_decode_scores_kernel : a workgroup per 64 rows: the rows' softmax statistics into LDS, then lanes over (row, class): one
+//                           float4 of deltas in, one float4 box and one score out.  HBM: 20 C + 16 read, 20 C written per row.
+// No floating-point atomics: every reduction has a fixed order, so every entry is bit-identical from run to run.  Compiled with
+// -ffp-contract=off (same arithmetic as generate_iou_map / get_deltas_from_bboxes / get_bboxes_from_deltas).
+#include <algorithm>
+#include <cstdint>
+
+#include "bbox_core.h"
+#include "radix_select.h"
+#include "rpn_common.h"
+
+namespace rpn {
+
+constexpr int kRoiTgtThreads = 1024;
+constexpr int kRoiGtChunk = 1024;          // gt boxes staged in LDS at a time (one per thread)
+
+struct RoiTargetArgs {
+    const float *rois;        // (B,R,4)
+    const int *valid;         // (B,) or null
+    const float *gt;          // (B,G,4)
+    const int *labels;        // (B,G), >= 1 = a gt box
+    const int *rand_pos;      // (B,R) >= 1
+    const int *rand_neg;      // (B,R) >= 1
+    int R, G;
+    int total_pos, total_neg;
+    float var[4];
+    float pos_iou, neg_lo, neg_hi;
+    float *out_deltas;        // (B,R,4)
+    int *out_labels;          // (B,R)
+    // workspace
+    float *best;              // (B,R) max IoU over the valid gt boxes (0 when none overlaps)
+    int *arg;                 // (B,R) first argmax, -1 = none
+};
+
+__global__ void __launch_bounds__(kRoiTgtThreads)
+roi_target_kernel(RoiTargetArgs p)
+{
+    __shared__ unsigned hist[kRsHistWords];
+    __shared__ int ctl[8];
+    __shared__ __attribute__((aligned(16))) float gts[4 * kRoiGtChunk];
+    __shared__ float garea[kRoiGtChunk];
+    __shared__ int gok[kRoiGtChunk];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    const int R = p.R, G = p.G;
+    const float *rois = p.rois + 4 * (size_t)b * R;
+    const float *gt = p.gt + 4 * (size_t)b * G;
+    const int *glab = p.labels + (size_t)b * G;
+    float *best = p.best + (size_t)b * R;
+    int *arg = p.arg + (size_t)b * R;
+    const int *rpos = p.rand_pos + (size_t)b * R, *rneg = p.rand_neg + (size_t)b * R;
+    int live = R;                                           // rows r >= live are padding
+    if (p.valid) live = min(max(p.valid[b], 0), R);
+
+    // max IoU / first argmax of every live row over the valid gt boxes, in gt order
+    for (int g0 = 0; g0 < G; g0 += kRoiGtChunk) {
+        const int ng = min(kRoiGtChunk, G - g0);
+        if (g0) __syncthreads();                            // the previous chunk has been read
+        if (tid < ng) {
+            const Box g = load_box(gt + 4 * (size_t)(g0 + tid));
+            store_box(gts + 4 * tid, g);
+            garea[tid] = box_area_plain(g);
+            gok[tid] = glab[g0 + tid] >= 1;
+        }
+        __syncthreads();
+        for (int r = tid; r < live; r += kRoiTgtThreads) {
+            const Box bb = load_box(rois + 4 * (size_t)r);
+            const float barea = box_area_plain(bb);
+            float bi = 0.0f;
+            int ai = -1;
+            if (g0) { bi = best[r]; ai = arg[r]; }          // (this thread's own earlier writes)
+            for (int g = 0; g < ng; ++g) {
+                if (!gok[g]) continue;                      // workgroup-uniform
+                const float iou = iou_map_pair(bb, barea, load_box(gts + 4 * g), garea[g]);
+                if (iou > bi) {                             // strict: the first maximum wins, a NaN never does
+                    bi = iou;
+                    ai = g0 + g;
+                }
+            }
+            best[r] = bi;
+            arg[r] = ai;
+        }
+    }
+    __syncthreads();
+
+    auto key_pos = [&](int i) -> unsigned long long {
+        const bool m = best[i] > p.pos_iou;
+        return m ? (((unsigned long long)(unsigned)rpos[i] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i)) : 0ull;
+    };
+    int pos_count = 0;
+    unsigned long long thr_pos = 0ull;
+    if (p.total_pos > 0)
+        thr_pos = radix_select<kRoiTgtThreads>(key_pos, live, ~0ull, p.total_pos, p.total_pos, hist, ctl, &pos_count);
+    if (thr_pos == 0ull) pos_count = 0;
+    auto is_pos = [&](int i) -> bool {
+        const unsigned long long k = key_pos(i);
+        return thr_pos != 0ull && k != 0ull && k >= thr_pos;
+    };
+    const int neg_want = p.total_pos + p.total_neg - pos_count;          // the batch fills up with negatives
+    auto key_neg = [&](int i) -> unsigned long long {
+        const float v = best[i];
+        const bool m = v >= p.neg_lo && v < p.neg_hi && !is_pos(i);
+        return m ? (((unsigned long long)(unsigned)rneg[i] << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i)) : 0ull;
+    };
+    int neg_count = 0;
+    unsigned long long thr_neg = 0ull;
+    if (neg_want > 0) thr_neg = radix_select<kRoiTgtThreads>(key_neg, live, ~0ull, neg_want, neg_want, hist, ctl, &neg_count);
+
+    for (int i = tid; i < R; i += kRoiTgtThreads) {
+        int lab = -1;
+        float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (i < live) {
+            if (is_pos(i)) {
+                const int a = arg[i];                       // best > pos_iou >= 0: some gt set it
+                lab = glab[a];
+                d = encode_box(load_box(rois + 4 * (size_t)i), load_box(gt + 4 * (size_t)a));
+                d.x = d.x / p.var[0];
+                d.y = d.y / p.var[1];
+                d.z = d.z / p.var[2];
+                d.w = d.w / p.var[3];
+            } else {
+                const unsigned long long kn = key_neg(i);
+                if (thr_neg != 0ull && kn != 0ull && kn >= thr_neg) lab = 0;
+            }
+        }
+        p.out_labels[(size_t)b * R + i] = lab;
+        *reinterpret_cast<float4 *>(p.out_deltas + 4 * ((size_t)b * R + i)) = d;
+    }
+}
+
+// ---- losses -----------------------------------------------------------------------------------------------------------------
+constexpr int kRoiLossThreads = 256;
+constexpr int kRoiLossMaxBlocks = 512;
+
+__device__ __forceinline__ double4 roi_block_sum(double4 v, double4 *red)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = kRoiLossThreads / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            const double4 a = red[threadIdx.x], b = red[threadIdx.x + w];
+            red[threadIdx.x] = make_double4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+        }
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// rowstat[row] = (max logit, 1 / sum exp(logit - max)); part[block] = (reg sum, cls sum, n_pos, n_kept)
+__global__ void __launch_bounds__(kRoiLossThreads)
+roi_loss_kernel(const float *__restrict__ logits, const float *__restrict__ reg_pred, const int *__restrict__ labels,
+                const float4 *__restrict__ deltas, long long n, int C, float2 *__restrict__ rowstat, double4 *__restrict__ part)
+{
+    __shared__ double4 red[kRoiLossThreads];
+    double reg = 0.0, cls = 0.0, npos = 0.0, nkept = 0.0;
+    for (long long i = (long long)blockIdx.x * kRoiLossThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kRoiLossThreads) {
+        const int lab = labels[i];
+        const bool kept = lab >= 0 && lab < C;               // anything else is ignored and never indexes memory
+        if (!kept && !rowstat) continue;
+        const float *l = logits + i * C;
+        float m = l[0];
+        for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+        double s = 0.0;
+        for (int c = 0; c < C; ++c) s += exp((double)l[c] - (double)m);
+        if (rowstat) rowstat[i] = make_float2(m, (float)(1.0 / s));
+        if (!kept) continue;
+        cls += ((double)m + log(s)) - (double)l[lab];
+        nkept += 1.0;
+        if (lab >= 1) {
+            const float4 p = *reinterpret_cast<const float4 *>(reg_pred + (i * C + lab) * 4), t = deltas[i];
+            const double d[4] = {(double)p.x - t.x, (double)p.y - t.y, (double)p.z - t.z, (double)p.w - t.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double a = fabs(d[k]), q = fmin(a, 1.0);
+                reg += 0.5 * q * q + (a - q);
+            }
+            npos += 1.0;
+        }
+    }
+    const double4 t = roi_block_sum(make_double4(reg, cls, npos, nkept), red);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// out = [reg_loss, cls_loss]; scale = {1 / max(1, n_pos), 1 / max(1, n_kept)}.  An empty sum is 0, so is its loss: no NaN.
+__global__ void __launch_bounds__(kRoiLossThreads)
+roi_loss_finish_kernel(const double4 *__restrict__ part, int nparts, float *__restrict__ out, float *__restrict__ scale)
+{
+    __shared__ double4 red[kRoiLossThreads];
+    double4 s = make_double4(0.0, 0.0, 0.0, 0.0);
+    for (int i = threadIdx.x; i < nparts; i += kRoiLossThreads) {
+        const double4 a = part[i];
+        s = make_double4(s.x + a.x, s.y + a.y, s.z + a.z, s.w + a.w);
+    }
+    const double4 t = roi_block_sum(s, red);
+    if (threadIdx.x == 0) {
+        out[0] = (float)(t.x / fmax(1.0, t.z));
+        out[1] = (float)(t.y / fmax(1.0, t.w));
+        scale[0] = (float)(1.0 / fmax(1.0, t.z));
+        scale[1] = (float)(1.0 / fmax(1.0, t.w));
+    }
+}
+
+// one element per (row, class): its grad_logits value and its float4 of grad_reg
+__global__ void __launch_bounds__(256)
+roi_loss_grad_kernel(const float *__restrict__ logits, const float *__restrict__ reg_pred, const int *__restrict__ labels,
+                     const float4 *__restrict__ deltas, long long n, int C, const float2 *__restrict__ rowstat,
+                     const float *__restrict__ scale, float *__restrict__ g_logits, float4 *__restrict__ g_reg)
+{
+    const float sr = scale[0], sc = scale[1];
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n * C; e += (long long)gridDim.x * 256) {
+        const long long row = e / C;
+        const int c = (int)(e - row * C);
+        const int lab = labels[row];
+        const bool kept = lab >= 0 && lab < C;
+        if (g_logits) {
+            float g = 0.0f;
+            if (kept) {
+                const float2 st = rowstat[row];
+                g = (expf(logits[e] - st.x) * st.y - (c == lab ? 1.0f : 0.0f)) * sc;
+            }
+            g_logits[e] = g;
+        }
+        if (g_reg) {
+            float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (kept && lab >= 1 && c == lab) {
+                const float4 p = *reinterpret_cast<const float4 *>(reg_pred + e * 4), t = deltas[row];
+                g.x = fmaxf(-1.0f, fminf(1.0f, p.x - t.x)) * sr;
+                g.y = fmaxf(-1.0f, fminf(1.0f, p.y - t.y)) * sr;
+                g.z = fmaxf(-1.0f, fminf(1.0f, p.z - t.z)) * sr;
+                g.w = fmaxf(-1.0f, fminf(1.0f, p.w - t.w)) * sr;
+            }
+            g_reg[e] = g;
+        }
+    }
+}
+
+// ---- head outputs -> per-class boxes and scores -----------------------------------------------------------------------------
+constexpr int kRoiDecRows = 64;            // rows per workgroup
+
+struct RoiVar {
+    float v[4];
+};
+
+__global__ void __launch_bounds__(256)
+roi_decode_scores_kernel(const float *__restrict__ rois, const int *__restrict__ valid, const float4 *__restrict__ reg_pred,
+                         const float *__restrict__ logits, RoiVar var, long long n, int R, int C, float4 *__restrict__ boxes,
+                         float *__restrict__ scores)
+{
+    __shared__ float2 stat[kRoiDecRows];                    // (max, 1 / sum exp), (0, 0) for a padding row
+    const long long row0 = (long long)blockIdx.x * kRoiDecRows;
+    const int nrows = (int)min((long long)kRoiDecRows, n - row0);
+    if ((int)threadIdx.x < nrows) {
+        const long long row = row0 + threadIdx.x;
+        const int b = (int)(row / R), r = (int)(row - (long long)b * R);
+        float2 st = make_float2(0.0f, 0.0f);
+        if (!valid || r < valid[b]) {
+            const float *l = logits + row * C;
+            float m = l[0];
+            for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+            double s = 0.0;
+            for (int c = 0; c < C; ++c) s += exp((double)l[c] - (double)m);
+            st = make_float2(m, (float)(1.0 / s));
+        }
+        stat[threadIdx.x] = st;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nrows * C; e += 256) {
+        const int lr = e / C, c = e - lr * C;
+        const long long row = row0 + lr, i = row * C + c;
+        const float4 d = reg_pred[i];
+        store_box(reinterpret_cast<float *>(boxes + i),
+                  decode_box(load_box(rois + 4 * row), d.x * var.v[0], d.y * var.v[1], d.z * var.v[2], d.w * var.v[3]));
+        const float2 st = stat[lr];
+        // background and padding rows: exactly 0 (st.y == 0 marks a padding row; a live row's 1 / sum is at least 1 / C)
+        scores[i] = (c >= 1 && st.y != 0.0f) ? expf(logits[i] - st.x) * st.y : 0.0f;
+    }
+}
+
+static size_t rh_a256(size_t v) { return (v + 255) & ~(size_t)255; }
+static bool rh_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static int roi_loss_blocks(long long n)
+{
+    return (int)std::max<long long>(1, std::min<long long>((n + kRoiLossThreads - 1) / kRoiLossThreads, kRoiLossMaxBlocks));
+}
+
+}  // namespace rpn
+
+using namespace rpn;
+
+extern "C" size_t rpn_roi_targets_workspace_bytes(int B, int R, int G)
+{
+    if (B <= 0 || R <= 0 || G <= 0) return 0;
+    return 2 * rh_a256((size_t)B * R * 4);
+}
+
+extern "C" int rpn_roi_targets(const float *d_rois, const int32_t *d_valid, const float *d_gt_boxes, const int32_t *d_gt_labels, int B,
+                               int R, int G, int total_pos, int total_neg, float pos_iou, float neg_lo, float neg_hi,
+                               const float *variances, const int32_t *d_random_pos, const int32_t *d_random_neg, float *d_roi_deltas,
+                               int32_t *d_roi_labels, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    const char *who = "rpn_roi_targets";
+    RPN_REQUIRE(d_rois && d_gt_boxes && d_gt_labels && variances && d_random_pos && d_random_neg && d_roi_deltas && d_roi_labels,
+                "%s: null pointer", who);
+    RPN_REQUIRE(B >= 1 && R >= 1 && G >= 1, "%s: B, R and G must be >= 1 (got %d, %d, %d)", who, B, R, G);
+    RPN_REQUIRE(G <= 2048, "%s: G = %d > 2048", who, G);
+    RPN_REQUIRE((long long)B * R < (1ll << 31), "%s: B * R = %lld RoIs do not fit one launch", who, (long long)B * R);
+    RPN_REQUIRE(total_pos >= 0 && total_neg >= 0 && (long long)total_pos + total_neg < (1ll << 31),
+                "%s: total_pos = %d, total_neg = %d", who, total_pos, total_neg);
+    RPN_REQUIRE(neg_lo >= 0.0f && neg_lo <= neg_hi && pos_iou >= 0.0f,
+                "%s: thresholds need 0 <= neg_lo <= neg_hi and pos_iou >= 0 (got neg_lo %g, neg_hi %g, pos_iou %g)", who, (double)neg_lo,
+                (double)neg_hi, (double)pos_iou);
+    RPN_REQUIRE(rh_aligned16(d_rois) && rh_aligned16(d_gt_boxes) && rh_aligned16(d_roi_deltas),
+                "%s: rois, gt boxes and deltas must be 16-byte aligned", who);
+    const size_t need = rpn_roi_targets_workspace_bytes(B, R, G);
+    if (!d_workspace || workspace_bytes < need)
+        return fail(RPN_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    RPN_REQUIRE_DEVICE();
+    RoiTargetArgs p{};
+    p.rois = d_rois; p.valid = d_valid; p.gt = d_gt_boxes; p.labels = d_gt_labels;
+    p.rand_pos = d_random_pos; p.rand_neg = d_random_neg;
+    p.R = R; p.G = G; p.total_pos = total_pos; p.total_neg = total_neg;
+    for (int i = 0; i < 4; ++i) p.var[i] = variances[i];
+    p.pos_iou = pos_iou; p.neg_lo = neg_lo; p.neg_hi = neg_hi;
+    p.out_deltas = d_roi_deltas; p.out_labels = d_roi_labels;
+    p.best = reinterpret_cast<float *>(d_workspace);
+    p.arg = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(d_workspace) + rh_a256((size_t)B * R * 4));
+    hipLaunchKernelGGL(roi_target_kernel, dim3(B), dim3(kRoiTgtThreads), 0, as_stream(stream), p);
+    RPN_CHECK_LAUNCH();
+    return RPN_OK;
+}
+
+extern "C" size_t rpn_roi_losses_workspace_bytes(int B, int R, int C)
+{
+    if (B <= 0 || R <= 0 || C <= 0) return 0;
+    const long long n = (long long)B * R;
+    return rh_a256((size_t)roi_loss_blocks(n) * sizeof(double4)) + 256 + rh_a256((size_t)n * sizeof(float2));
+}
+
+extern "C" int rpn_roi_losses(const float *d_cls_logits, const float *d_reg_pred, const int32_t *d_roi_labels, const float *d_roi_deltas,
+                              int B, int R, int C, float *d_losses, float *d_grad_logits, float *d_grad_reg, void *d_workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    const char *who = "rpn_roi_losses";
+    RPN_REQUIRE(d_cls_logits && d_reg_pred && d_roi_labels && d_roi_deltas && d_losses, "%s: null pointer", who);
+    RPN_REQUIRE(B >= 1 && R >= 1 && C >= 1, "%s: B, R and C must be >= 1 (got %d, %d, %d)", who, B, R, C);
+    RPN_REQUIRE((long long)B * R < (1ll << 31), "%s: B * R = %lld rows do not fit one launch", who, (long long)B * R);
+    RPN_REQUIRE(rh_aligned16(d_reg_pred) && rh_aligned16(d_roi_deltas) && rh_aligned16(d_grad_reg),
+                "%s: reg_pred, roi_deltas and grad_reg must be 16-byte aligned", who);
+    const size_t need = rpn_roi_losses_workspace_bytes(B, R, C);
+    if (!d_workspace || workspace_bytes < need)
+        return fail(RPN_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    RPN_REQUIRE_DEVICE();
+    hipStream_t s = as_stream(stream);
+    const long long n = (long long)B * R;
+    const int nb = roi_loss_blocks(n);
+    unsigned char *ws = reinterpret_cast<unsigned char *>(d_workspace);
+    double4 *part = reinterpret_cast<double4 *>(ws);
+    float *scale = reinterpret_cast<float *>(ws + rh_a256((size_t)nb * sizeof(double4)));
+    float2 *rowstat = reinterpret_cast<float2 *>(ws + rh_a256((size_t)nb * sizeof(double4)) + 256);
+    const float4 *deltas = reinterpret_cast<const float4 *>(d_roi_deltas);
+    hipLaunchKernelGGL(roi_loss_kernel, dim3(nb), dim3(kRoiLossThreads), 0, s, d_cls_logits, d_reg_pred, d_roi_labels, deltas, n, C,
+                       d_grad_logits ? rowstat : nullptr, part);
+    RPN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(roi_loss_finish_kernel, dim3(1), dim3(kRoiLossThreads), 0, s, part, nb, d_losses, scale);
+    RPN_CHECK_LAUNCH();
+    if (d_grad_logits || d_grad_reg) {
+        const int grid = (int)std::max<long long>(1, std::min<long long>((n * C + 255) / 256, 4096));
+        hipLaunchKernelGGL(roi_loss_grad_kernel, dim3(grid), dim3(256), 0, s, d_cls_logits, d_reg_pred, d_roi_labels, deltas, n, C, rowstat,
+                           scale, d_grad_logits, reinterpret_cast<float4 *>(d_grad_reg));
+        RPN_CHECK_LAUNCH();
+    }
+    return RPN_OK;
+}
+
+extern "C" int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const float *d_reg_pred, const float *d_cls_logits,
+                                     const float *variances, int B, int R, int C, float *d_boxes, float *d_scores, void *stream)
+{
+    const char *who = "rpn_roi_decode_scores";
+    RPN_REQUIRE(d_rois && d_reg_pred && d_cls_logits && variances && d_boxes && d_scores, "%s: null pointer", who);
+    RPN_REQUIRE(B >= 1 && R >= 1 && C >= 1, "%s: B, R and C must be >= 1 (got %d, %d, %d)", who, B, R, C);
+    RPN_REQUIRE((long long)B * R < (1ll << 31), "%s: B * R = %lld rows do not fit one launch", who, (long long)B * R);
+    RPN_REQUIRE(rh_aligned16(d_rois) && rh_aligned16(d_reg_pred) && rh_aligned16(d_boxes),
+                "%s: rois, reg_pred and boxes must be 16-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const long long n = (long long)B * R;
+    RoiVar var;
+    for (int i = 0; i < 4; ++i) var.v[i] = variances[i];
+    hipLaunchKernelGGL(roi_decode_scores_kernel, dim3((unsigned)((n + kRoiDecRows - 1) / kRoiDecRows)), dim3(256), 0, as_stream(stream),
+                       d_rois, d_valid, reinterpret_cast<const float4 *>(d_reg_pred), d_cls_logits, var, n, R, C,
+                       reinterpret_cast<float4 *>(d_boxes), d_scores);
+    RPN_CHECK_LAUNCH();
+    return RPN_OK;
+}

@@ -10,13 +10,23 @@ with ``box_indices`` fixed to "RoI r of image b samples image b" (the shape ``Pr
 
     roi_pooling(feature_map, rois, pooling_size=(7, 7), valid=None)   -> rpn_roi_pool (+ rpn_roi_pool_backward under autograd)
 
+and, around it, what a second stage trains on and how its outputs become detections (the counterparts of the RPN's
+``calculate_rpn_actual_outputs`` / ``reg_loss`` + ``cls_loss`` / ``decode_and_nms``; thresholds and sampling rule are this project's
+choice):
+
+    calculate_roi_targets(rois, gt_boxes, gt_labels, hyper_params, ...)   -> rpn_roi_targets
+    roi_losses(cls_logits, reg_pred, roi_labels, roi_deltas)              -> rpn_roi_losses (gradients under autograd)
+    roi_detections(rois, reg_pred, cls_logits, variances, ...)            -> rpn_roi_decode_scores + rpn_combined_nms
+
 Arguments may be torch tensors (any device; results come back as CUDA tensors) or numpy arrays (results come back as numpy).
 Everything runs on the current torch HIP stream.  There is no CPU path: without a GPU ``roi_pooling`` raises ``RuntimeError``.
 The arithmetic contract (float32, each operation rounded on its own, bit-exact) is stated in ``include/rpn_hip.h``.
 """
+import numpy as np
 import torch
 
 from .. import _lib as L
+from . import bbox_utils
 
 
 def _pool_size(pooling_size):
@@ -98,3 +108,176 @@ def roi_pooling(feature_map, rois, pooling_size=(7, 7), valid=None):
     if needs_grad:
         return _RoIPooling.apply(x, r, v, ph, pw)
     return L.from_device(_forward(x.detach(), r, v, ph, pw), was_np)
+
+
+# ---- second stage: targets, losses, detections ------------------------------------------------------------------------------
+def _shape(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+def calculate_roi_targets(rois, gt_boxes, gt_labels, hyper_params, valid=None, total_pos=None, total_neg=None, pos_iou=0.5,
+                          neg_iou=(0.1, 0.5), random_pos=None, random_neg=None):
+    """Training targets of the detection head, one launch on the device (``rpn_roi_targets``; contract in ``include/rpn_hip.h``).
+
+    rois (B,R,4) normalised [y1,x1,y2,x2]; gt_boxes (B,G,4); gt_labels (B,G) int: a row is a gt box iff its label is >= 1 (0 is
+    background, padding is -1); ``valid`` (B,) int32, optional: rows ``r >= valid[b]`` are padding (the count ``decode_and_nms``
+    returns).  Returns (roi_deltas (B,R,4) float32, roi_labels (B,R) int32).
+
+    A live row's gt is the valid one of highest IoU (the first on ties; none when every IoU is 0 or NaN).  Rows with IoU above
+    ``pos_iou`` are positive candidates; ``total_pos`` of them are kept, by the priorities ``random_pos`` ((B,R) int32 >= 1, highest
+    first, ties to the lower index).  Rows not kept as positives with ``neg_iou[0] <= IoU < neg_iou[1]`` are negative candidates;
+    ``total_pos + total_neg`` minus the kept positives of them are kept by ``random_neg``.  Labels: the gt's label, 0 for a kept
+    negative, -1 otherwise; deltas: ``get_deltas_from_bboxes(roi, gt) / variances`` for kept positives, +0.0 elsewhere.  The counts
+    default to ``hyper_params["total_pos_bboxes"]`` / ``["total_neg_bboxes"]``; priorities that are not given come from torch's
+    generator on the device (no readback).  The (B,R,G) IoU map is never materialised."""
+    rs, gs, ls = _shape(rois), _shape(gt_boxes), _shape(gt_labels)
+    if len(rs) != 3 or rs[2] != 4 or len(gs) != 3 or gs[2] != 4 or gs[0] != rs[0] or ls != gs[:2]:
+        raise ValueError("expected rois (B,R,4), gt_boxes (B,G,4), gt_labels (B,G); got %s %s %s" % (rs, gs, ls))
+    B, R, G = rs[0], rs[1], gs[1]
+    if B < 1 or R < 1 or G < 1:
+        raise ValueError("B, R and G must be >= 1 (gt_boxes needs at least one, possibly padded, row per image); got %d, %d, %d" % (B, R, G))
+    if valid is not None and _shape(valid) != (B,):
+        raise ValueError("valid must be (%d,) int32, got %s" % (B, _shape(valid)))
+    for name, r in (("random_pos", random_pos), ("random_neg", random_neg)):
+        if r is not None and _shape(r) != (B, R):
+            raise ValueError("%s must be (%d, %d) int32, got %s" % (name, B, R, _shape(r)))
+    total_pos = int(hyper_params["total_pos_bboxes"] if total_pos is None else total_pos)
+    total_neg = int(hyper_params["total_neg_bboxes"] if total_neg is None else total_neg)
+    neg_lo, neg_hi = (float(v) for v in neg_iou)
+    if total_pos < 0 or total_neg < 0:
+        raise ValueError("total_pos and total_neg must be >= 0, got %d and %d" % (total_pos, total_neg))
+    if not (0.0 <= neg_lo <= neg_hi) or not float(pos_iou) >= 0.0:
+        raise ValueError("thresholds need 0 <= neg_iou[0] <= neg_iou[1] and pos_iou >= 0, got %r and %r" % (neg_iou, pos_iou))
+
+    def given(r, what):
+        if not isinstance(r, torch.Tensor):
+            r = torch.from_numpy(np.ascontiguousarray(np.asarray(r)))
+        if r.numel() and int(r.min()) < 1:          # key 0 marks a non-candidate: a priority <= 0 would silently drop the row
+            raise ValueError("%s: priorities must be >= 1" % what)
+        return r.to(device="cuda", dtype=torch.int32).contiguous()
+
+    r, was_np = L.to_device(rois.detach() if isinstance(rois, torch.Tensor) else rois)
+    g, _ = L.to_device(gt_boxes)
+    lab, _ = L.to_device(gt_labels, dtype=torch.int32)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+
+    def draw():
+        return torch.randint(1, 2 ** 31 - 1, (B, R), dtype=torch.int32, device="cuda")
+
+    rp = given(random_pos, "random_pos") if random_pos is not None else draw()
+    rn = given(random_neg, "random_neg") if random_neg is not None else draw()
+    deltas = torch.empty((B, R, 4), dtype=torch.float32, device="cuda")
+    labels = torch.empty((B, R), dtype=torch.int32, device="cuda")
+    lib = L.lib()
+    ws_bytes = int(lib.rpn_roi_targets_workspace_bytes(B, R, G))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device="cuda")
+    _keep, vptr = L.host_floats(hyper_params["variances"])
+    st = lib.rpn_roi_targets(L.ptr(r), L.ptr(v), L.ptr(g), L.ptr(lab), B, R, G, total_pos, total_neg, float(pos_iou), neg_lo, neg_hi,
+                             vptr, L.ptr(rp), L.ptr(rn), L.ptr(deltas), L.ptr(labels), L.ptr(ws), ws_bytes, L.stream_ptr())
+    L.check(st, "calculate_roi_targets")
+    return L.from_device(deltas, was_np), L.from_device(labels, was_np)
+
+
+def _check_losses(cs, ps, ls, ds):
+    if len(cs) != 3 or len(ps) != 3 or cs[:2] != ps[:2] or ps[2] != 4 * cs[2] or ls != cs[:2] or ds != cs[:2] + (4,):
+        raise ValueError("expected cls_logits (B,R,C), reg_pred (B,R,4C), roi_labels (B,R), roi_deltas (B,R,4); got %s %s %s %s"
+                         % (cs, ps, ls, ds))
+    if min(cs) < 1:
+        raise ValueError("B, R and C must be >= 1, got %s" % (cs,))
+
+
+def _losses(logits, reg, labels, deltas, with_grads):
+    """-> (losses (2,) [reg, cls], grad_logits or None, grad_reg or None), all on the device"""
+    B, R, C = (int(v) for v in logits.shape)
+    losses = torch.empty((2,), dtype=torch.float32, device="cuda")
+    g_logits = torch.empty_like(logits) if with_grads else None
+    g_reg = torch.empty_like(reg) if with_grads else None
+    lib = L.lib()
+    ws_bytes = int(lib.rpn_roi_losses_workspace_bytes(B, R, C))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device="cuda")
+    st = lib.rpn_roi_losses(L.ptr(logits), L.ptr(reg), L.ptr(labels), L.ptr(deltas), B, R, C, L.ptr(losses), L.ptr(g_logits),
+                            L.ptr(g_reg), L.ptr(ws), ws_bytes, L.stream_ptr())
+    L.check(st, "roi_losses")
+    return losses, g_logits, g_reg
+
+
+class _RoILosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, reg, labels, deltas):
+        losses, g_logits, g_reg = _losses(logits, reg, labels, deltas, True)
+        ctx.save_for_backward(g_logits, g_reg)
+        reg_loss, cls_loss = losses.clone().unbind()
+        return reg_loss, cls_loss
+
+    @staticmethod
+    def backward(ctx, d_reg_loss, d_cls_loss):
+        g_logits, g_reg = ctx.saved_tensors
+        return (g_logits * d_cls_loss if ctx.needs_input_grad[0] else None,
+                g_reg * d_reg_loss if ctx.needs_input_grad[1] else None, None, None)
+
+
+def roi_losses(cls_logits, reg_pred, roi_labels, roi_deltas):
+    """The detection head's losses on the device (``rpn_roi_losses``) -> (reg_loss, cls_loss), 0-d CUDA tensors for torch input, numpy
+    float32 scalars for numpy input.
+
+    cls_logits (B,R,C) logits; reg_pred (B,R,4C) class-specific boxes; roi_labels (B,R) int and roi_deltas (B,R,4) as
+    ``calculate_roi_targets`` returns them.  Rows with a label outside [0, C) are ignored.  cls_loss is the softmax cross-entropy
+    averaged over the kept rows, reg_loss the Huber (delta 1) sum of the labelled class's four coordinates over the positive rows
+    divided by their count; either is 0, never NaN, when it has no row.  When a prediction requires grad the result is part of the
+    torch graph: the forward pass computes both gradients, the backward pass scales them; labels and deltas get none."""
+    _check_losses(_shape(cls_logits), _shape(reg_pred), _shape(roi_labels), _shape(roi_deltas))
+    needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (cls_logits, reg_pred))
+    logits, was_np = L.to_device(cls_logits)
+    reg, _ = L.to_device(reg_pred)
+    labels, _ = L.to_device(roi_labels.detach() if isinstance(roi_labels, torch.Tensor) else roi_labels, dtype=torch.int32)
+    deltas, _ = L.to_device(roi_deltas.detach() if isinstance(roi_deltas, torch.Tensor) else roi_deltas)
+    if needs_grad:
+        return _RoILosses.apply(logits, reg, labels, deltas)
+    losses = _losses(logits.detach(), reg.detach(), labels, deltas, False)[0]
+    if was_np:
+        host = losses.cpu().numpy()
+        return host[0], host[1]
+    return losses[0], losses[1]
+
+
+def roi_decode_scores(rois, reg_pred, cls_logits, variances, valid=None):
+    """Head outputs -> (boxes (B,R,C,4), scores (B,R,C)) in one launch (``rpn_roi_decode_scores``): boxes[b,r,c] =
+    ``get_bboxes_from_deltas(rois, reg_pred[..., c, :], variances)``, not clipped; scores = softmax(cls_logits) with background
+    (class 0) and rows ``r >= valid[b]`` exactly 0."""
+    rs, ps, cs = _shape(rois), _shape(reg_pred), _shape(cls_logits)
+    if len(rs) != 3 or rs[2] != 4 or len(cs) != 3 or cs[:2] != rs[:2] or ps != rs[:2] + (4 * cs[2],):
+        raise ValueError("expected rois (B,R,4), reg_pred (B,R,4C), cls_logits (B,R,C); got %s %s %s" % (rs, ps, cs))
+    B, R, C = cs
+    if min(cs) < 1:
+        raise ValueError("B, R and C must be >= 1, got %s" % (cs,))
+    if valid is not None and _shape(valid) != (B,):
+        raise ValueError("valid must be (%d,) int32, got %s" % (B, _shape(valid)))
+    r, was_np = L.to_device(rois.detach() if isinstance(rois, torch.Tensor) else rois)
+    reg, _ = L.to_device(reg_pred.detach() if isinstance(reg_pred, torch.Tensor) else reg_pred)
+    logits, _ = L.to_device(cls_logits.detach() if isinstance(cls_logits, torch.Tensor) else cls_logits)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+    boxes = torch.empty((B, R, C, 4), dtype=torch.float32, device="cuda")
+    scores = torch.empty((B, R, C), dtype=torch.float32, device="cuda")
+    _keep, vptr = L.host_floats(variances)
+    st = L.lib().rpn_roi_decode_scores(L.ptr(r), L.ptr(v), L.ptr(reg), L.ptr(logits), vptr, B, R, C, L.ptr(boxes), L.ptr(scores),
+                                       L.stream_ptr())
+    L.check(st, "roi_decode_scores")
+    return L.from_device(boxes, was_np), L.from_device(scores, was_np)
+
+
+def roi_detections(rois, reg_pred, cls_logits, variances, valid=None, max_output_size_per_class=100, max_total_size=300,
+                   iou_threshold=0.5, score_threshold=0.5, return_indices=False):
+    """A trained head's outputs -> detections: ``roi_decode_scores`` then ``bbox_utils.non_max_suppression`` with class-specific
+    boxes.  Returns (boxes (B,M,4) clipped to [0, 1], scores (B,M), classes (B,M), valid_detections (B,) int32), M =
+    ``max_total_size`` (+ the selected RoI indices (B,M) int32 with ``return_indices=True``).  ``score_threshold`` must be above 0:
+    background and padding rows carry a score of exactly 0 and must never be selected."""
+    if not float(score_threshold) > 0.0:
+        raise ValueError("score_threshold must be > 0 (background and padding rows have score 0), got %r" % (score_threshold,))
+    was_np = not isinstance(rois, torch.Tensor)
+    if was_np:
+        rois = torch.from_numpy(np.ascontiguousarray(np.asarray(rois, dtype=np.float32)))
+    boxes, scores = roi_decode_scores(rois, reg_pred, cls_logits, variances, valid=valid)          # stay on the device
+    res = bbox_utils.non_max_suppression(boxes, scores, max_output_size_per_class=int(max_output_size_per_class),
+                                         max_total_size=int(max_total_size), iou_threshold=float(iou_threshold),
+                                         score_threshold=float(score_threshold), return_indices=bool(return_indices))
+    return tuple(L.from_device(t, was_np) for t in res)
