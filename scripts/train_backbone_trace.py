@@ -6,8 +6,8 @@
 
 A training step ends with its one adam_kernel dispatch.  Between the previous step's adam_kernel (or the start of the trace) and
 this one, the backward's dispatches come in a fixed order (trainer.hip, backbone_backward): conv3x3_dgrad_f32_kernel for
-rpn_conv's input first, then for conv i = 12 .. first trained: conv3x3_wgrad_wide_f32_kernel (+ wgrad_tree_kernel levels +
-wgrad_wide_finish_kernel), then, above the first trained conv, conv3x3_dgrad_f32_kernel (+ maxpool2x2_backward_kernel where a pool
+rpn_conv's input first, then for conv i = 12 .. first trained: conv3x3_wgrad_f32_kernel<true> (the instance with the row of ones
+behind db; the head's rpn_conv runs <false>) (+ wgrad_tree_kernel levels + wgrad_wide_finish_kernel), then, above the first trained conv, conv3x3_dgrad_f32_kernel (+ maxpool2x2_backward_kernel where a pool
 sits below).  Each dispatch is attributed to its layer by that order; the evaluation steps and single-layer timings the bench runs
 afterwards follow the last adam_kernel and are not counted.  Prints one line per layer: mean us per step of each kernel, with the
 dgrad / wgrad GEMM rate against the 157.3 TF/s float32-MFMA peak at the bench's batch and 500 x 500.
@@ -24,7 +24,7 @@ VGG16 = [("block1_conv1", 3, 64, False), ("block1_conv2", 64, 64, True), ("block
 
 
 def kind(name):
-    for k in ("conv3x3_dgrad_f32_kernel", "conv3x3_wgrad_wide_f32_kernel", "wgrad_tree_kernel", "wgrad_wide_finish_kernel",
+    for k in ("conv3x3_dgrad_f32_kernel", "conv3x3_wgrad_f32_kernel<true>", "wgrad_tree_kernel", "wgrad_wide_finish_kernel",
               "maxpool2x2_backward_kernel", "dgrad_weights_kernel", "adam_kernel"):
         if k in name:
             return k
@@ -60,7 +60,7 @@ def main():
             if k == "conv3x3_dgrad_f32_kernel":
                 layer, what = ("rpn_conv" if n_d == 0 else VGG16[13 - n_d][0]), "dgrad"
                 n_d += 1
-            elif k == "conv3x3_wgrad_wide_f32_kernel":
+            elif k == "conv3x3_wgrad_f32_kernel<true>":
                 layer, what = VGG16[12 - n_w][0], "wgrad"
                 n_w += 1
             elif layer is None:

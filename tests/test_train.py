@@ -181,10 +181,11 @@ def test_loss_argument_forms():
 
 def test_wgrad_kernel_register_budget(lib):
     """No scratch; registers and LDS of the 3x3 weight-gradient kernel pinned (four waves of 112 registers, 40 KB of LDS:
-    three workgroups per CU by LDS)."""
+    three workgroups per CU by LDS).  <false> is the head's instance; the backbone's <true> (the row of ones behind db) is held to the
+    same budget by test_train_backbone.test_backbone_kernel_budgets."""
     import codeobj
     tab = codeobj.table(L.LIB_PATH)
-    budgets = {"conv3x3_wgrad_f32_kernel": (128, 0, 40960), "rpn_loss_kernel": (64, 0, 8192),
+    budgets = {"conv3x3_wgrad_f32_kernel<false>": (128, 0, 40960), "rpn_loss_kernel": (64, 0, 8192),
                "head_wgrad_kernel<45>": (128, 0, 11520), "head_dgrad_kernel<45>": (160, 0, 2880), "adam_kernel": (48, 0, 0)}
     for name, (vgpr, sspill, lds) in budgets.items():
         assert name in tab, name

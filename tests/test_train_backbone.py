@@ -159,12 +159,14 @@ def test_backbone_entries_need_a_device(lib):
 
 
 def test_backbone_kernel_budgets(lib):
-    """No scratch; registers and LDS of the backbone backward kernels pinned.  dgrad<2> / wgrad_wide: four waves, 2 x 2 32x32 f32
-    accumulator blocks (64 registers) + staging, 40 KB of LDS (three workgroups per CU by LDS); dgrad<1>: 2 x 1 blocks, 32 KB."""
+    """No scratch; registers and LDS of the backbone backward kernels pinned.  dgrad<2> / wgrad (both instances of the one kernel,
+    <true> with the row of ones behind db): four waves, 2 x 2 32x32 f32 accumulator blocks (64 registers) + staging, 40 KB of LDS
+    (three workgroups per CU by LDS); dgrad<1>: 2 x 1 blocks, 32 KB."""
     import codeobj
     tab = codeobj.table(L.LIB_PATH)
     budgets = {"conv3x3_dgrad_f32_kernel<2>": (128, 0, 40960), "conv3x3_dgrad_f32_kernel<1>": (96, 0, 32768),
-               "conv3x3_wgrad_wide_f32_kernel": (128, 0, 40960), "maxpool2x2_backward_kernel": (48, 0, 0),
+               "conv3x3_wgrad_f32_kernel<true>": (128, 0, 40960), "conv3x3_wgrad_f32_kernel<false>": (128, 0, 40960),
+               "maxpool2x2_backward_kernel": (48, 0, 0),
                "dgrad_weights_kernel": (40, 0, 0), "wgrad_tree_kernel": (16, 0, 0), "wgrad_wide_finish_kernel": (32, 0, 0),
                "pad_channels3to4_kernel": (16, 0, 0)}
     for name, (vgpr, sspill, lds) in budgets.items():

@@ -160,6 +160,22 @@ def test_new_entries_need_a_device(lib):
     assert b"no CPU fallback" in lib.rpn_last_error()
 
 
+def test_depthwise_and_tree_kernel_budgets(lib):
+    """The stride-1 / stride-2 instances of the one depthwise backward pair, the two slab trees and the stem's weight gradient, each at
+    what its separate predecessor (dwconv3x3[_s2]_dgrad_kernel, dwconv3x3[_s2]_wgrad_partial_kernel, leaf_tree_kernel, stem_tree_kernel)
+    compiled to: registers, SGPR spills (the trees' go to register lanes, not to memory) and LDS; no scratch."""
+    import codeobj
+    tab = codeobj.table(L.LIB_PATH)
+    budgets = {"dwconv3x3_dgrad_kernel<1>": (38, 0, 0), "dwconv3x3_dgrad_kernel<2>": (36, 0, 0),
+               "dwconv3x3_wgrad_partial_kernel<1,16,16>": (68, 0, 36864), "dwconv3x3_wgrad_partial_kernel<2,8,32>": (70, 0, 36864),
+               "slab_tree_kernel<1>": (39, 40, 0), "slab_tree_kernel<8>": (56, 500, 0),
+               "conv3x3_s2_cin3_wgrad_partial_kernel": (139, 0, 36864)}
+    for name, (vgpr, sspill, lds) in budgets.items():
+        assert name in tab, name
+        v, ss, vs, scratch, lds_b, _wg = tab[name]
+        assert v <= vgpr and ss <= sspill and vs == 0 and scratch == 0 and lds_b <= lds, (name, tab[name])
+
+
 # ---- GPU: single kernels, bit-exact on small integers -----------------------------------------------------------------------
 def pad_s2(x):
     """Keras ZeroPadding2D(correct_pad(x, 3)) on an NCHW tensor: (0, 1) on an even side, (1, 1) on an odd one."""

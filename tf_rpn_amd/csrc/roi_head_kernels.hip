@@ -299,7 +299,6 @@ roi_decode_scores_kernel(const float *__restrict__ rois, const int *__restrict__
     }
 }
 
-static size_t rh_a256(size_t v) { return (v + 255) & ~(size_t)255; }
 static bool rh_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static int roi_loss_blocks(long long n)
 {
@@ -313,7 +312,7 @@ using namespace rpn;
 extern "C" size_t rpn_roi_targets_workspace_bytes(int B, int R, int G)
 {
     if (B <= 0 || R <= 0 || G <= 0) return 0;
-    return 2 * rh_a256((size_t)B * R * 4);
+    return 2 * a256((size_t)B * R * 4);
 }
 
 extern "C" int rpn_roi_targets(const float *d_rois, const int32_t *d_valid, const float *d_gt_boxes, const int32_t *d_gt_labels, int B,
@@ -346,7 +345,7 @@ extern "C" int rpn_roi_targets(const float *d_rois, const int32_t *d_valid, cons
     p.pos_iou = pos_iou; p.neg_lo = neg_lo; p.neg_hi = neg_hi;
     p.out_deltas = d_roi_deltas; p.out_labels = d_roi_labels;
     p.best = reinterpret_cast<float *>(d_workspace);
-    p.arg = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(d_workspace) + rh_a256((size_t)B * R * 4));
+    p.arg = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(d_workspace) + a256((size_t)B * R * 4));
     hipLaunchKernelGGL(roi_target_kernel, dim3(B), dim3(kRoiTgtThreads), 0, as_stream(stream), p);
     RPN_CHECK_LAUNCH();
     return RPN_OK;
@@ -356,7 +355,7 @@ extern "C" size_t rpn_roi_losses_workspace_bytes(int B, int R, int C)
 {
     if (B <= 0 || R <= 0 || C <= 0) return 0;
     const long long n = (long long)B * R;
-    return rh_a256((size_t)roi_loss_blocks(n) * sizeof(double4)) + 256 + rh_a256((size_t)n * sizeof(float2));
+    return a256((size_t)roi_loss_blocks(n) * sizeof(double4)) + 256 + a256((size_t)n * sizeof(float2));
 }
 
 extern "C" int rpn_roi_losses(const float *d_cls_logits, const float *d_reg_pred, const int32_t *d_roi_labels, const float *d_roi_deltas,
@@ -378,8 +377,8 @@ extern "C" int rpn_roi_losses(const float *d_cls_logits, const float *d_reg_pred
     const int nb = roi_loss_blocks(n);
     unsigned char *ws = reinterpret_cast<unsigned char *>(d_workspace);
     double4 *part = reinterpret_cast<double4 *>(ws);
-    float *scale = reinterpret_cast<float *>(ws + rh_a256((size_t)nb * sizeof(double4)));
-    float2 *rowstat = reinterpret_cast<float2 *>(ws + rh_a256((size_t)nb * sizeof(double4)) + 256);
+    float *scale = reinterpret_cast<float *>(ws + a256((size_t)nb * sizeof(double4)));
+    float2 *rowstat = reinterpret_cast<float2 *>(ws + a256((size_t)nb * sizeof(double4)) + 256);
     const float4 *deltas = reinterpret_cast<const float4 *>(d_roi_deltas);
     hipLaunchKernelGGL(roi_loss_kernel, dim3(nb), dim3(kRoiLossThreads), 0, s, d_cls_logits, d_reg_pred, d_roi_labels, deltas, n, C,
                        d_grad_logits ? rowstat : nullptr, part);

@@ -31,6 +31,8 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// workspace sections start on 256-byte boundaries
+inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace rpn
 

@@ -146,7 +146,6 @@ target_select_kernel(TargetArgs p)
     }
 }
 
-static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace rpn
 

@@ -1,5 +1,7 @@
 // train_backbone.h -- host-side interface of the VGG16 backbone backward kernels (train_backbone_kernels.hip; internal to
-// librpn_hip.so).  Every kernel is float32, writes each output once, and uses no floating-point atomics.
+// librpn_hip.so).  Every kernel is float32, writes each output once, and uses no floating-point atomics.  launch_wgrad_wide runs the
+// 3x3 weight-gradient kernel of train_kernels.hip (train_head.h: launch_wgrad_slabs); the helpers the training kernel files share are
+// in train_common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,7 +25,7 @@ hipError_t launch_maxpool2x2_backward(const float *y, const float *dpool, int B,
 // weight + bias gradient of a 3x3 stride-1 'same' conv at backbone shapes: x (B,H,W,cin_x) -- cin_x = Cin rounded up to 4; the
 // extra channels, if any, must be 0 -- and dy (B,H,W,Cout) -> dw (3,3,Cin,Cout) HWIO, db (Cout).  The pixels are split into
 // wgrad_wide_leaves(...) fixed ranges (a power of two, from the shape alone) that are summed in a fixed pairwise tree; db is one
-// more row of the same GEMM (a row of ones).  part: wgrad_wide_ws_floats(...) floats of device scratch.
+// more row of the same GEMM (a row of ones: conv3x3_wgrad_f32_kernel<true>).  part: wgrad_wide_ws_floats(...) floats of device scratch.
 int wgrad_wide_leaves(int B, int H, int W, int Cin, int Cout);
 size_t wgrad_wide_ws_floats(int B, int H, int W, int Cin, int Cout);
 hipError_t launch_wgrad_wide(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, float *db,

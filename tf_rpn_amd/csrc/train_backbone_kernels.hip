@@ -1,6 +1,8 @@
 // train_backbone_kernels.hip -- the backward pass of the VGG16 backbone (reference models/rpn_vgg16.py:16-21: the Keras base model is
 // trainable, trainer.py:54-69 compiles and fits all of it): 3x3 input gradients (dgrad), 3x3 weight + bias gradients at backbone
-// shapes (wgrad_wide) and the MaxPooling2D(2, 2) backward.  The training step that chains them lives in trainer.hip.
+// shapes (wgrad_wide) and the MaxPooling2D(2, 2) backward.  The training step that chains them lives in trainer.hip.  The wgrad's MFMA
+// kernel is conv3x3_wgrad_f32_kernel<true> of train_kernels.hip (launch_wgrad_slabs, train_head.h): here are its leaf rule and its
+// slab tree.  The helpers shared with the other training kernel files are in train_common.h.
 //
 // Gradient forms (TF 2.0.0, restated from its sources as recalled -- nothing here can run TF):
 //   ReluGrad(grad, op.outputs[0]):  dY * [Y > 0], Y the ReLU OUTPUT (nn_grad.py _ReluGrad).
@@ -13,13 +15,12 @@
 
 #include "rpn_common.h"
 #include "train_backbone.h"
+#include "train_common.h"
+#include "train_head.h"
 
 namespace rpn {
 
-static size_t a256b(size_t v) { return (v + 255) & ~(size_t)255; }
-static int grid_1d(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
-
-using f32x16b = __attribute__((ext_vector_type(16))) float;
+constexpr int kGridCap = 4096;          // workgroups of this file's grid-stride kernels
 
 // ---- dgrad: dX (P x Cin) = A (P x 9 Cout) Wt (9 Cout x Cin) on v_mfma_f32_32x32x2_f32 -----------------------------------------
 // A[p][tap Cout + co] = dY[b][y + r - 1][x + s - 1][co] (tap = 3 r + s, zero outside the image), Wt[tap Cout + co][ci] =
@@ -87,7 +88,7 @@ __device__ __forceinline__ void conv3x3_dgrad_f32_body(const float *__restrict__
         for (int u = 0; u < WN; ++u) *reinterpret_cast<float4 *>(&Bs[buf][bk + RPP * u][4 * bq]) = rb[u];
     };
 
-    f32x16b acc[2][WN];
+    f32x16t acc[2][WN];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -177,7 +178,7 @@ bool conv3x3_dgrad_wide_tile(int B, int H, int W, int Cin)
 hipError_t launch_conv3x3_dgrad(const float *dy, const float *w_hwio, const float *mask, const float *add, int B, int H, int W, int Cin,
                                 int Cout, float *wt, float *dx, hipStream_t s)
 {
-    hipLaunchKernelGGL(dgrad_weights_kernel, dim3(grid_1d(9LL * Cin * Cout)), dim3(256), 0, s, w_hwio, Cin, Cout, wt);
+    hipLaunchKernelGGL(dgrad_weights_kernel, dim3(grid_1d(9LL * Cin * Cout, kGridCap)), dim3(256), 0, s, w_hwio, Cin, Cout, wt);
     const unsigned mt = (unsigned)(((long long)B * H * W + kDgBM - 1) / kDgBM);
     const bool wide = conv3x3_dgrad_wide_tile(B, H, W, Cin);
     const dim3 grid(mt, wide ? (Cin + 127) / 128 : (Cin + 63) / 64);
@@ -236,127 +237,14 @@ __global__ void __launch_bounds__(256) maxpool2x2_backward_kernel(const float *_
 
 hipError_t launch_maxpool2x2_backward(const float *y, const float *dpool, int B, int H, int W, int C, float *dy, hipStream_t s)
 {
-    hipLaunchKernelGGL(maxpool2x2_backward_kernel, dim3(grid_1d((long long)B * H * W * (C / 4))), dim3(256), 0, s, y, dpool, B, H, W, C, dy);
+    hipLaunchKernelGGL(maxpool2x2_backward_kernel, dim3(grid_1d((long long)B * H * W * (C / 4), kGridCap)), dim3(256), 0, s, y, dpool, B, H, W, C, dy);
     return hipGetLastError();
 }
 
 // ---- wgrad at backbone shapes ---------------------------------------------------------------------------------------------------
-// C (M1 x Cout) = A^T B over the pixels, M1 = 9 Cin + 1: rows 0 .. 9 Cin - 1 as in conv3x3_wgrad_f32_kernel (row (3 r + s) Cin + ci),
-// row 9 Cin a row of ones (-> db).  Leaf blockIdx.z of `leaves` takes pixels [l P / leaves, (l + 1) P / leaves) and writes its own
-// slab; wgrad_tree_kernel / wgrad_wide_finish_kernel add the slabs pairwise.  Same tiling and staging as the head's wgrad kernel.
-constexpr int kWwBM = 128, kWwBN = 128, kWwBK = 16, kWwLd = 160;
-
-__global__ void __launch_bounds__(256) conv3x3_wgrad_wide_f32_kernel(const float *__restrict__ X, const float *__restrict__ dY, int B, int H,
-                                                                   int W, int Cin, int Cout, int leaves, float *__restrict__ part)
-{
-    __shared__ float As[2][kWwBK][kWwLd];
-    __shared__ float Bs[2][kWwBK][kWwLd];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int M = 9 * Cin, M1 = M + 1, n0 = blockIdx.x * kWwBN, m0 = blockIdx.y * kWwBM, leaf = blockIdx.z;
-    const long long P = (long long)B * H * W;
-    const long long pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
-    const int nsteps = (int)((pend - pbeg + kWwBK - 1) / kWwBK);
-
-    const int kr = tid >> 5, q = tid & 31;
-    const int m = m0 + 4 * q, n = n0 + 4 * q;
-    const bool m_ok = m < M, ones = m == M, n_ok = n < Cout;
-    const int tap = m_ok ? m / Cin : 0, ci = m_ok ? m - tap * Cin : 0;
-    const int dr = tap / 3 - 1, ds = tap % 3 - 1;
-    int pb[2], py[2], px[2];
-    long long pp[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        pp[u] = pbeg + kr + 8 * u;
-        const long long hw = (long long)H * W;
-        pb[u] = (int)(pp[u] / hw);
-        const int rem = (int)(pp[u] - (long long)pb[u] * hw);
-        py[u] = rem / W;
-        px[u] = rem - py[u] * W;
-    }
-    float4 ra[2], rb[2];
-    auto load_global = [&]() {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            ra[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            rb[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (pp[u] < pend) {
-                const int yy = py[u] + dr, xx = px[u] + ds;
-                if (m_ok && yy >= 0 && yy < H && xx >= 0 && xx < W)
-                    ra[u] = *reinterpret_cast<const float4 *>(X + (((size_t)pb[u] * H + yy) * W + xx) * Cin + ci);
-                if (ones) ra[u].x = 1.0f;
-                if (n_ok) rb[u] = *reinterpret_cast<const float4 *>(dY + (size_t)pp[u] * Cout + n);
-            }
-        }
-    };
-    auto advance = [&]() {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            pp[u] += kWwBK;
-            px[u] += kWwBK;
-            while (px[u] >= W) {
-                px[u] -= W;
-                if (++py[u] == H) { py[u] = 0; ++pb[u]; }
-            }
-        }
-    };
-    auto store_lds = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            *reinterpret_cast<float4 *>(&As[buf][kr + 8 * u][4 * q]) = ra[u];
-            *reinterpret_cast<float4 *>(&Bs[buf][kr + 8 * u][4 * q]) = rb[u];
-        }
-    };
-
-    f32x16b acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    const int am = wm * 64 + (lane & 31), bn = wn * 64 + (lane & 31), kh = lane >> 5;
-
-    load_global();
-    store_lds(0);
-    __syncthreads();
-    int cur = 0;
-    for (int step = 0; step < nsteps; ++step) {
-        const bool more = step + 1 < nsteps;
-        if (more) {
-            advance();
-            load_global();
-        }
-#pragma unroll
-        for (int kk = 0; kk < kWwBK / 2; ++kk) {
-            float av[2], bv[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) av[i] = As[cur][2 * kk + kh][am + 32 * i];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bv[j] = Bs[cur][2 * kk + kh][bn + 32 * j];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
-        if (more) store_lds(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    float *slab = part + (size_t)leaf * M1 * Cout;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wn * 64 + 32 * j + (lane & 31);
-            if (col >= Cout) continue;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = m0 + wm * 64 + 32 * i + 8 * (e >> 2) + 4 * kh + (e & 3);
-                if (row < M1) slab[(size_t)row * Cout + col] = acc[i][j][e];
-            }
-        }
-}
+// C (M1 x Cout) = A^T B over the pixels, M1 = 9 Cin + 1, on conv3x3_wgrad_f32_kernel<true> (train_kernels.hip): rows 0 .. 9 Cin - 1
+// the weight gradient (row (3 r + s) Cin + ci), row 9 Cin a row of ones (-> db).  Leaf l of wgrad_wide_leaves(...) takes pixels
+// [l P / leaves, (l + 1) P / leaves) and writes its own slab; wgrad_tree_kernel / wgrad_wide_finish_kernel add the slabs pairwise.
 
 // one level of the fixed tree: slab i += slab i + half, i < half
 __global__ void __launch_bounds__(256) wgrad_tree_kernel(float *__restrict__ part, long long len, int half)
@@ -385,7 +273,7 @@ __global__ void __launch_bounds__(256) wgrad_wide_finish_kernel(const float *__r
 int wgrad_wide_leaves(int B, int H, int W, int Cin, int Cout)
 {
     const int cin_x = (Cin + 3) & ~3;
-    const long long tiles = (long long)((Cout + kWwBN - 1) / kWwBN) * ((9 * cin_x + 1 + kWwBM - 1) / kWwBM);
+    const long long tiles = (long long)((Cout + kWgBN - 1) / kWgBN) * ((9 * cin_x + 1 + kWgBM - 1) / kWgBM);
     const long long P = (long long)B * H * W;
     int L = 1;                                     // 1024 workgroups (four per CU of 256) or >= 512 pixels per leaf
     while (L < 1024 && tiles * L < 1024 && P / (2 * L) >= 512) L *= 2;
@@ -402,12 +290,11 @@ hipError_t launch_wgrad_wide(const float *x, const float *dy, int B, int H, int 
                              hipStream_t s)
 {
     const int cin_x = (Cin + 3) & ~3, M1 = 9 * cin_x + 1, L = wgrad_wide_leaves(B, H, W, Cin, Cout);
-    hipLaunchKernelGGL(conv3x3_wgrad_wide_f32_kernel, dim3((Cout + kWwBN - 1) / kWwBN, (M1 + kWwBM - 1) / kWwBM, L), dim3(256), 0, s, x, dy,
-                       B, H, W, cin_x, Cout, L, part);
+    launch_wgrad_slabs(x, dy, B, H, W, cin_x, Cout, L, true, part, s);
     const long long len = (long long)M1 * Cout;
     for (int half = L / 2; half >= 2; half /= 2)
-        hipLaunchKernelGGL(wgrad_tree_kernel, dim3(grid_1d(half * len)), dim3(256), 0, s, part, len, half);
-    hipLaunchKernelGGL(wgrad_wide_finish_kernel, dim3(grid_1d(len)), dim3(256), 0, s, part, L >= 2 ? 1 : 0, cin_x, Cin, Cout, dw, db);
+        hipLaunchKernelGGL(wgrad_tree_kernel, dim3(grid_1d(half * len, kGridCap)), dim3(256), 0, s, part, len, half);
+    hipLaunchKernelGGL(wgrad_wide_finish_kernel, dim3(grid_1d(len, kGridCap)), dim3(256), 0, s, part, L >= 2 ? 1 : 0, cin_x, Cin, Cout, dw, db);
     return hipGetLastError();
 }
 
@@ -419,7 +306,7 @@ __global__ void __launch_bounds__(256) pad_channels3to4_kernel(const float *__re
 
 hipError_t launch_pad_channels3to4(const float *x, long long P, float *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(pad_channels3to4_kernel, dim3(grid_1d(P)), dim3(256), 0, s, x, P, out);
+    hipLaunchKernelGGL(pad_channels3to4_kernel, dim3(grid_1d(P, kGridCap)), dim3(256), 0, s, x, P, out);
     return hipGetLastError();
 }
 
@@ -431,7 +318,7 @@ using namespace rpn;
 extern "C" size_t rpn_conv3x3_dgrad_workspace_bytes(int Cin, int Cout)
 {
     if (Cin < 1 || Cout < 1) return 0;
-    return a256b((size_t)9 * Cin * Cout * sizeof(float));
+    return a256((size_t)9 * Cin * Cout * sizeof(float));
 }
 
 extern "C" int rpn_conv3x3_dgrad(const float *d_dy, const float *d_w, const float *d_mask, int B, int H, int W, int Cin, int Cout,
@@ -491,8 +378,8 @@ static bool wgrad_wide_shape_ok(int B, int H, int W, int Cin, int Cout)
 extern "C" size_t rpn_conv3x3_wgrad_wide_workspace_bytes(int B, int H, int W, int Cin, int Cout)
 {
     if (!wgrad_wide_shape_ok(B, H, W, Cin, Cout)) return 0;
-    const size_t pad = Cin == 3 ? a256b((size_t)B * H * W * 4 * sizeof(float)) : 0;
-    return a256b(wgrad_wide_ws_floats(B, H, W, Cin, Cout) * sizeof(float)) + pad;
+    const size_t pad = Cin == 3 ? a256((size_t)B * H * W * 4 * sizeof(float)) : 0;
+    return a256(wgrad_wide_ws_floats(B, H, W, Cin, Cout) * sizeof(float)) + pad;
 }
 
 extern "C" int rpn_conv3x3_wgrad_wide(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw, float *d_db,
@@ -510,7 +397,7 @@ extern "C" int rpn_conv3x3_wgrad_wide(const float *d_x, const float *d_dy, int B
     const float *x = d_x;
     hipError_t e = hipSuccess;
     if (Cin == 3) {
-        float *x4 = part + a256b(wgrad_wide_ws_floats(B, H, W, Cin, Cout) * sizeof(float)) / sizeof(float);
+        float *x4 = part + a256(wgrad_wide_ws_floats(B, H, W, Cin, Cout) * sizeof(float)) / sizeof(float);
         e = launch_pad_channels3to4(d_x, (long long)B * H * W, x4, s);
         x = x4;
     }

@@ -1,5 +1,6 @@
 // train_head.h -- host-side interface of the RPN losses, the head's backward kernels, the 3x3 weight gradient at the head's shape and
-// Adam (train_kernels.hip; internal to librpn_hip.so).  Every kernel is float32 (float64 sums inside the losses), writes each output
+// Adam (train_kernels.hip; internal to librpn_hip.so); the helpers the training kernel files share are in train_common.h (a256 in
+// rpn_common.h).  Every kernel is float32 (float64 sums inside the losses), writes each output
 // once and uses no floating-point atomics: every sum has a fixed order.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,14 @@ hipError_t launch_losses(const float *reg_true, const float *reg_pred, const flo
 // part: colsum_ws_floats(rows, C) floats of device scratch
 size_t colsum_ws_floats(long long rows, int C);
 hipError_t launch_colsum(const float *x, long long rows, int C, float *part, float *out, hipStream_t s);
+
+// ---- the 3x3 stride-1 'same' weight-gradient GEMM on the float32 MFMA (conv3x3_wgrad_f32_kernel: the one kernel behind launch_wgrad
+// and train_backbone.h's launch_wgrad_wide), x (B,H,W,Cin), dy (B,H,W,Cout), Cin % 4 == 0, Cout % 4 == 0 --------------------------------
+// writes `leaves` slabs of (9 Cin + ones) x Cout floats to part and nothing else: slab l = the gradient over the pixels
+// [l P / leaves, (l + 1) P / leaves), row (3 r + s) Cin + ci; with `ones`, row 9 Cin = the sum of dy over the same pixels (db).
+// The caller adds the slabs in its own fixed order.  No error is read here: the caller's hipGetLastError covers the launch.
+void launch_wgrad_slabs(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, int leaves, bool ones, float *part,
+                        hipStream_t s);
 
 // ---- dw (3,3,Cin,Cout) HWIO = the weight gradient of a 3x3 stride-1 'same' conv, x (B,H,W,Cin), dy (B,H,W,Cout) -----------------------
 // four fixed ranges of pixels added as (l0 + l1) + (l2 + l3).  Cin % 4 == 0, Cout % 4 == 0.  part: wgrad_ws_floats(Cin, Cout) floats.

@@ -2,7 +2,10 @@
 // Adam(1e-5) and loss=[reg_loss, cls_loss], then fit): the two losses and their gradients, the backward of the fused 1x1 head, the
 // 3x3 weight gradient of rpn_conv, column sums and Adam, each with its host launcher (train_head.h), and the two stand-alone entries
 // rpn_rpn_losses and rpn_conv3x3_wgrad.  The trainer that strings them together -- and the backbones' backward kernels of
-// train_backbone_kernels.hip / train_mnv2_kernels.hip behind them -- is trainer.hip.  Of a step these kernels compute
+// train_backbone_kernels.hip / train_mnv2_kernels.hip behind them -- is trainer.hip.  The 3x3 weight-gradient MFMA kernel here is the
+// only one: the VGG16 backbone's wgrad (train_backbone_kernels.hip) runs its other instance through launch_wgrad_slabs.  What the
+// three kernel files share (grid rule, accumulator type, the wgrad tile, the fixed trees) is in train_common.h.  Of a step these
+// kernels compute
 //   losses + their gradients (one pass, fixed-order reductions)
 //   dZ = [dreg | dcls * p (1 - p)] (P,5K);  dW_head = S^T dZ, db_head = sum dZ;  dS = (dZ W_head^T) * [S > 0]
 //   dW_conv = 3x3 weight gradient of X and dS on the float32 MFMA (split K, fixed tree), db_conv = sum dS
@@ -24,6 +27,7 @@
 #include <cmath>
 
 #include "rpn_common.h"
+#include "train_common.h"
 #include "train_head.h"
 
 namespace rpn {
@@ -31,11 +35,11 @@ namespace rpn {
 constexpr int kLossThreads = 256;
 constexpr int kLossMaxBlocks = 512;
 constexpr int kChunkRows = 64;          // rows per partial of the column sums / the head weight gradient
-constexpr int kLeaves = 4;              // K leaves of the 3x3 weight gradient: the value is (l0 + l1) + (l2 + l3) at every grid
+constexpr int kLeaves = 4;              // K leaves of the head's 3x3 weight gradient: the value is (l0 + l1) + (l2 + l3) at every grid
+constexpr int kGridCap = 2048;          // workgroups of this file's grid-stride kernels
 constexpr float kClipLo = 1e-7f, kClipHi = 1.0f - 1e-7f;   // keras epsilon() and 1 - epsilon() as float32 constants
 constexpr double kLogEps = (double)1e-7f;
 
-static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
 static int loss_blocks(long long n) { return (int)std::min<long long>((n + kLossThreads - 1) / kLossThreads, kLossMaxBlocks); }
 
 // ---- losses: pass 1 ---------------------------------------------------------------------------------------------------
@@ -237,31 +241,31 @@ __global__ void __launch_bounds__(256) reduce_chunks_kernel(const float *__restr
 // dW[r][s][ci][co] = sum_{b,y,x} X[b][y+r-1][x+s-1][ci] * dY[b][y][x][co] (zero padding): a GEMM C (M x N) = A^T B with
 // M = 9 Cin (row m = (3 r + s) Cin + ci), N = Cout, K = the P = B H W pixels; both operands are pixel-major (A^T[p][m] is a
 // shifted row of X, B[p][n] a row of dY), so a K slice of either is a contiguous run of channels per pixel.
-// Workgroup: a 128 x 128 tile of C over ONE of kLeaves fixed ranges of pixels (leaf l: [l P / 4, (l + 1) P / 4)); four waves of
-// 64 x 64 (2 x 2 v_mfma_f32_32x32x2_f32 blocks).  K slices of 16 pixels are staged global -> registers -> LDS (double-buffered,
-// one barrier per slice, the next slice's loads in flight under the current slice's MFMAs), as conv_igemm_f32 stages its
-// operands.  Each leaf's tile goes to its own slab of the workspace; wgrad_reduce_kernel adds (l0 + l1) + (l2 + l3).  The
-// leaves do not depend on the grid: the same bits at every launch.
-constexpr int kWgBM = 128, kWgBN = 128, kWgBK = 16, kWgLd = 160;   // LDS row stride: the two half-waves of a fragment read hit disjoint banks
-
-using f32x16w = __attribute__((ext_vector_type(16))) float;
-
+// With ONES the GEMM has one more row, M1 = M + 1: row 9 Cin is a row of ones, which yields db = sum dY.
+// Workgroup: a 128 x 128 tile of C (train_common.h) over ONE of `leaves` fixed ranges of pixels (leaf l = blockIdx.z:
+// [l P / leaves, (l + 1) P / leaves)); four waves of 64 x 64 (2 x 2 v_mfma_f32_32x32x2_f32 blocks).  K slices of 16 pixels are
+// staged global -> registers -> LDS (double-buffered, one barrier per slice, the next slice's loads in flight under the current
+// slice's MFMAs), as conv_igemm_f32 stages its operands.  Each leaf's tile goes to its own slab of M1 x Cout floats; the callers
+// add the slabs, each in its own fixed order: the head (launch_wgrad, 4 leaves) as (l0 + l1) + (l2 + l3) in wgrad_reduce_kernel,
+// the VGG16 backbone (launch_wgrad_wide, train_backbone_kernels.hip) slab i with slab i + half.  The leaves do not depend on the
+// grid: the same bits at every launch.
+template <bool ONES>
 __global__ void __launch_bounds__(256) conv3x3_wgrad_f32_kernel(const float *__restrict__ X, const float *__restrict__ dY, int B, int H,
-                                                              int W, int Cin, int Cout, float *__restrict__ part)
+                                                              int W, int Cin, int Cout, int leaves, float *__restrict__ part)
 {
     __shared__ float As[2][kWgBK][kWgLd];
     __shared__ float Bs[2][kWgBK][kWgLd];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int M = 9 * Cin, n0 = blockIdx.x * kWgBN, m0 = blockIdx.y * kWgBM, leaf = blockIdx.z;
+    const int M = 9 * Cin, M1 = M + (ONES ? 1 : 0), n0 = blockIdx.x * kWgBN, m0 = blockIdx.y * kWgBM, leaf = blockIdx.z;
     const long long P = (long long)B * H * W;
-    const long long pbeg = P * leaf / kLeaves, pend = P * (leaf + 1) / kLeaves;
+    const long long pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
     const int nsteps = (int)((pend - pbeg + kWgBK - 1) / kWgBK);
 
     // loader: thread -> (pixel row kr and kr + 8 of the slice, 4-channel quad q); the same (tap, ci) / n for every slice
     const int kr = tid >> 5, q = tid & 31;
     const int m = m0 + 4 * q, n = n0 + 4 * q;
-    const bool m_ok = m < M, n_ok = n < Cout;
+    const bool m_ok = m < M, ones = ONES && m == M, n_ok = n < Cout;
     const int tap = m_ok ? m / Cin : 0, ci = m_ok ? m - tap * Cin : 0;
     const int dr = tap / 3 - 1, ds = tap % 3 - 1;
     // pixel coordinates of this thread's two rows at the current slice, advanced by 16 pixels per slice
@@ -286,6 +290,7 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_f32_kernel(const float *__r
                 const int yy = py[u] + dr, xx = px[u] + ds;
                 if (m_ok && yy >= 0 && yy < H && xx >= 0 && xx < W)
                     ra[u] = *reinterpret_cast<const float4 *>(X + (((size_t)pb[u] * H + yy) * W + xx) * Cin + ci);
+                if (ones) ra[u].x = 1.0f;
                 if (n_ok) rb[u] = *reinterpret_cast<const float4 *>(dY + (size_t)pp[u] * Cout + n);
             }
         }
@@ -309,7 +314,7 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_f32_kernel(const float *__r
         }
     };
 
-    f32x16w acc[2][2];
+    f32x16t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -345,7 +350,7 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_f32_kernel(const float *__r
         cur ^= 1;
     }
     // accumulator element e of block (i, j): row 8 (e / 4) + 4 kh + e % 4, column lane % 32
-    float *slab = part + (size_t)leaf * M * Cout;
+    float *slab = part + (size_t)leaf * M1 * Cout;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -355,7 +360,7 @@ __global__ void __launch_bounds__(256) conv3x3_wgrad_f32_kernel(const float *__r
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int row = m0 + wm * 64 + 32 * i + 8 * (e >> 2) + 4 * kh + (e & 3);
-                if (row < M) slab[(size_t)row * Cout + col] = acc[i][j][e];
+                if (row < M1) slab[(size_t)row * Cout + col] = acc[i][j][e];
             }
         }
 }
@@ -382,8 +387,6 @@ __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ w, const 
     }
 }
 
-static int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 2048)); }
-
 // ---- host launchers ----------------------------------------------------------------------------------------------------------
 size_t losses_ws_bytes(long long n) { return a256((size_t)loss_blocks(n) * sizeof(double4)) + 256; }
 
@@ -408,19 +411,27 @@ hipError_t launch_colsum(const float *x, long long rows, int C, float *part, flo
 {
     const int nchunks = (int)((rows + kChunkRows - 1) / kChunkRows);
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(nchunks), dim3(256), 0, s, x, rows, C, part);
-    hipLaunchKernelGGL(reduce_chunks_kernel, dim3(grid_for(C)), dim3(256), 0, s, part, nchunks, (long long)C, out);
+    hipLaunchKernelGGL(reduce_chunks_kernel, dim3(grid_1d(C, kGridCap)), dim3(256), 0, s, part, nchunks, (long long)C, out);
     return hipGetLastError();
 }
 
 size_t wgrad_ws_floats(int Cin, int Cout) { return (size_t)kLeaves * 9 * Cin * Cout; }
 
+void launch_wgrad_slabs(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, int leaves, bool ones, float *part,
+                        hipStream_t s)
+{
+    const dim3 grid((Cout + kWgBN - 1) / kWgBN, (9 * Cin + (ones ? 1 : 0) + kWgBM - 1) / kWgBM, leaves);
+    if (ones)
+        hipLaunchKernelGGL(conv3x3_wgrad_f32_kernel<true>, grid, dim3(256), 0, s, x, dy, B, H, W, Cin, Cout, leaves, part);
+    else
+        hipLaunchKernelGGL(conv3x3_wgrad_f32_kernel<false>, grid, dim3(256), 0, s, x, dy, B, H, W, Cin, Cout, leaves, part);
+}
+
 hipError_t launch_wgrad(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, hipStream_t s)
 {
-    const int M = 9 * Cin;
-    hipLaunchKernelGGL(conv3x3_wgrad_f32_kernel, dim3((Cout + kWgBN - 1) / kWgBN, (M + kWgBM - 1) / kWgBM, kLeaves), dim3(256), 0, s, x,
-                       dy, B, H, W, Cin, Cout, part);
-    const long long len = (long long)M * Cout;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_for(len)), dim3(256), 0, s, part, len, dw);
+    launch_wgrad_slabs(x, dy, B, H, W, Cin, Cout, kLeaves, false, part, s);
+    const long long len = 9LL * Cin * Cout;
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_1d(len, kGridCap)), dim3(256), 0, s, part, len, dw);
     return hipGetLastError();
 }
 
@@ -431,7 +442,7 @@ hipError_t launch_head_backward(const float *graw_reg, const float *graw_cls, co
                                 bool *supported, hipStream_t s)
 {
     const int nc = 5 * K;
-    hipLaunchKernelGGL(head_dz_kernel, dim3(grid_for(P * nc)), dim3(256), 0, s, graw_reg, graw_cls, cls, scale, P, K, dz);
+    hipLaunchKernelGGL(head_dz_kernel, dim3(grid_1d(P * nc, kGridCap)), dim3(256), 0, s, graw_reg, graw_cls, cls, scale, P, K, dz);
     const int chunks = (int)((P + kChunkRows - 1) / kChunkRows);
     const int dgrid = (int)((P + 15) / 16);
     *supported = true;
@@ -441,7 +452,7 @@ hipError_t launch_head_backward(const float *graw_reg, const float *graw_cls, co
 #define RPN_HEAD_NC(NCV)                                                                                                    \
     case NCV:                                                                                                               \
         hipLaunchKernelGGL(head_wgrad_kernel<NCV>, dim3(chunks), dim3(256), 0, s, S, dz, P, part);                          \
-        hipLaunchKernelGGL(reduce_chunks_kernel, dim3(grid_for(513 * NCV)), dim3(256), 0, s, part, chunks, 513LL * NCV, dw_head); \
+        hipLaunchKernelGGL(reduce_chunks_kernel, dim3(grid_1d(513 * NCV, kGridCap)), dim3(256), 0, s, part, chunks, 513LL * NCV, dw_head); \
         hipLaunchKernelGGL(head_dgrad_kernel<NCV>, dim3(dgrid), dim3(512), 0, s, S, dz, w_head, P, dS);                     \
         break;
         RPN_HEAD_NC(5) RPN_HEAD_NC(10) RPN_HEAD_NC(15) RPN_HEAD_NC(20) RPN_HEAD_NC(25) RPN_HEAD_NC(30) RPN_HEAD_NC(35)
@@ -455,7 +466,7 @@ hipError_t launch_head_backward(const float *graw_reg, const float *graw_cls, co
 hipError_t launch_adam(float *w, const float *g, float *m, float *v, long long n, long long t, float lr, float b1, float b2, float eps,
                        hipStream_t s)
 {
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, s, w, g, m, v, n, t, lr, b1, b2, eps);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_1d(n, kGridCap)), dim3(256), 0, s, w, g, m, v, n, t, lr, b1, b2, eps);
     return hipGetLastError();
 }
 
@@ -482,7 +493,7 @@ extern "C" int rpn_rpn_losses(const float *d_reg_true, const float *d_reg_pred, 
     hipStream_t s = as_stream(stream);
     hipError_t e = launch_losses(d_reg_true, d_reg_pred, d_cls_true, d_cls_pred, n, d_grad_reg, d_grad_cls, d_losses, 0, d_ws, s);
     if (e == hipSuccess && (d_grad_reg || d_grad_cls)) {
-        hipLaunchKernelGGL(rpn_loss_scale_kernel, dim3(grid_for(n)), dim3(256), 0, s, d_grad_reg, d_grad_cls, n, losses_scale(d_ws, n));
+        hipLaunchKernelGGL(rpn_loss_scale_kernel, dim3(grid_1d(n, kGridCap)), dim3(256), 0, s, d_grad_reg, d_grad_cls, n, losses_scale(d_ws, n));
         e = hipGetLastError();
     }
     return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_rpn_losses: %s", hipGetErrorString(e));

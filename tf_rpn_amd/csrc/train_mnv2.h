@@ -1,6 +1,7 @@
 // train_mnv2.h -- host-side interface of the MobileNetV2 backward kernels (train_mnv2_kernels.hip; internal to librpn_hip.so):
 // training-mode BatchNorm, the 1x1 conv backward on the float32 MFMA, the depthwise 3x3 backward (stride 1 and stride 2) and the
-// stem's weight gradient.  Every kernel is
+// stem's weight gradient.  The two depthwise strides are instances of one kernel pair; the fixed 32-leaf tree (tree_sum32), the
+// lane-sum epilogue of the per-channel weight gradients and the other shared helpers are in train_common.h.  Every kernel is
 // float32 (float64 partial sums inside the BatchNorm reductions), writes each output once and uses no floating-point atomics; every
 // reduction is a fixed number of leaves, chosen from the shape alone, added in a fixed tree.
 #pragma once

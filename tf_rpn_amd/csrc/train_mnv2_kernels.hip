@@ -1,6 +1,8 @@
 // train_mnv2_kernels.hip -- backward of MobileNetV2 (Conv1, expanded_conv, block_1 .. block_12, block_13_expand): BatchNorm in
 // training mode, the 1x1 convs on the float32 MFMA, the depthwise 3x3 convs (stride 1 'same'; stride 2 behind Keras' correct_pad) and
-// the stem's weight gradient.  The trainer that strings them together is in trainer.hip (mn_forward / mn_backward).
+// the stem's weight gradient.  The trainer that strings them together is in trainer.hip (mn_forward / mn_backward).  tree_sum32, the
+// lane-sum epilogue of the per-channel weight gradients (lane_sum_store) and the helpers shared with the other training kernel files
+// are in train_common.h.
 //
 // BatchNorm form (TF 2.0's fused BatchNorm, restated as recalled -- nothing here can run TF): over the N = B H W pixels of a channel,
 //   mean = sum x / N, var = sum (x - mean)^2 / N (biased), xhat = (x - mean) / sqrt(var + eps), y = gamma xhat + beta;
@@ -17,35 +19,19 @@
 #include <cstdint>
 
 #include "rpn_common.h"
+#include "train_common.h"
 #include "train_mnv2.h"
 
 namespace rpn {
 
 constexpr int kRedQuads = 16, kRedLanes = 16;   // a reduction workgroup: 16 channel quads x 16 row lanes
-constexpr int kMaxLeaves = 32;
-
-static size_t a256m(size_t v) { return (v + 255) & ~(size_t)255; }
-static int grid_1dm(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 4096)); }
+constexpr int kGridCap = 4096;                  // workgroups of this file's grid-stride kernels
 
 int mn_reduce_leaves(long long P)
 {
     int L = 1;
     while (L < kMaxLeaves && P / (2 * L) >= 16) L *= 2;
     return L;
-}
-
-// sum of `leaves` (a power of two <= 32) values stride apart, in a fixed tree: absent leaves are zeros, which change no bit
-template <class T>
-__device__ inline T tree_sum32(const T *p, size_t stride, int leaves)
-{
-    T v[kMaxLeaves];
-#pragma unroll
-    for (int i = 0; i < kMaxLeaves; ++i) v[i] = i < leaves ? p[(size_t)i * stride] : T(0);
-#pragma unroll
-    for (int w = kMaxLeaves / 2; w > 0; w >>= 1)
-#pragma unroll
-        for (int i = 0; i < w; ++i) v[i] = v[i] + v[i + w];
-    return v[0];
 }
 
 __device__ inline float bn_rstd_of(float var, float eps) { return (float)(1.0 / sqrt((double)var + (double)eps)); }
@@ -234,7 +220,7 @@ hipError_t launch_bn_apply(const float *x, long long P, int C, const float *mean
 {
     const long long total4 = P * (C / 4);
     auto f4 = [](const float *p) { return reinterpret_cast<const float4 *>(p); };
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_1dm(total4)), dim3(256), 0, s, f4(x), total4, C / 4, f4(mean), f4(rstd), f4(gamma),
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_1d(total4, kGridCap)), dim3(256), 0, s, f4(x), total4, C / 4, f4(mean), f4(rstd), f4(gamma),
                        f4(beta), relu6, f4(res), reinterpret_cast<float4 *>(y));
     return hipGetLastError();
 }
@@ -249,7 +235,7 @@ hipError_t launch_bn_backward(const float *x, const float *dy, long long P, int 
     hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((C + 63) / 64, leaves), dim3(256), 0, s, x, dy, P, C, f4(mean), f4(rstd), f4(gamma),
                        f4(beta), relu6, leaves, part);
     hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, leaves, C, dgamma, dbeta);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_1dm(total4)), dim3(256), 0, s, f4(x), f4(dy), total4, C / 4, f4(mean), f4(rstd),
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_1d(total4, kGridCap)), dim3(256), 0, s, f4(x), f4(dy), total4, C / 4, f4(mean), f4(rstd),
                        f4(gamma), f4(beta), f4(dgamma), f4(dbeta), (float)(1.0 / (double)P), relu6, reinterpret_cast<float4 *>(dx));
     return hipGetLastError();
 }
@@ -264,8 +250,6 @@ hipError_t launch_bn_backward(const float *x, const float *dy, long long P, int 
 // buffered with one barrier per slice, as conv3x3_wgrad_f32_kernel stages its operands.  Each leaf writes its own slab of `out`
 // (out + leaf M N); `add` (M x N, leaves == 1 only) is added in the epilogue.  M, N, the row lengths and K (KCONTIG) are multiples of 4.
 constexpr int kGmT = 64, kGmK = 16, kGmLd = 96;   // LDS row stride 96: the two half-waves of a fragment read hit disjoint banks
-
-using f32x16m = __attribute__((ext_vector_type(16))) float;
 
 template <bool KCONTIG>
 __global__ void __launch_bounds__(256) gemm1x1_f32_kernel(const float *__restrict__ A, const float *__restrict__ Bm, int M, int N, long long K,
@@ -307,7 +291,7 @@ __global__ void __launch_bounds__(256) gemm1x1_f32_kernel(const float *__restric
             Bs[buf][4 * kq + 0][r] = rb.x; Bs[buf][4 * kq + 1][r] = rb.y; Bs[buf][4 * kq + 2][r] = rb.z; Bs[buf][4 * kq + 3][r] = rb.w;
         }
     };
-    f32x16m acc;
+    f32x16t acc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
     const int am = wm * 32 + (lane & 31), bn = wn * 32 + (lane & 31), kh = lane >> 5;
@@ -340,11 +324,26 @@ __global__ void __launch_bounds__(256) gemm1x1_f32_kernel(const float *__restric
     }
 }
 
-// out[j] = the fixed tree over the `leaves` slabs of len floats
-__global__ void __launch_bounds__(256) leaf_tree_kernel(const float *__restrict__ part, long long len, int leaves, float *__restrict__ out)
+// out[j] = the fixed tree over the `leaves` (a power of two <= 32 GROUPS) slabs of len floats: tree_sum32 over each group of 32, then
+// the groups pairwise, neighbours first: ((g0 + g1) + (g2 + g3)) + ((g4 + g5) + (g6 + g7)) at GROUPS = 8 (an absent group is a
+// zero).  GROUPS = 1 is tree_sum32 alone -- the 32-leaf reductions must not run through a wider form: adding the absent groups'
+// zeros would turn a sum of -0.0 into +0.0.
+template <int GROUPS>
+__global__ void __launch_bounds__(256) slab_tree_kernel(const float *__restrict__ part, long long len, int leaves, float *__restrict__ out)
 {
-    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256)
-        out[j] = tree_sum32<float>(part + j, (size_t)len, leaves);
+    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256) {
+        float v[GROUPS];
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int n = leaves - g * kMaxLeaves;
+            v[g] = n > 0 ? tree_sum32<float>(part + (size_t)g * kMaxLeaves * len + j, (size_t)len, n < kMaxLeaves ? n : kMaxLeaves) : 0.0f;
+        }
+#pragma unroll
+        for (int n = GROUPS; n > 1; n >>= 1)
+#pragma unroll
+            for (int i = 0; i < n / 2; ++i) v[i] = v[2 * i] + v[2 * i + 1];
+        out[j] = v[0];
+    }
 }
 
 int conv1x1_wgrad_leaves(long long P, int Cin, int Cout)
@@ -368,7 +367,7 @@ hipError_t launch_conv1x1_wgrad(const float *x, const float *dy, long long P, in
                        P, Cin, Cout, L, (const float *)nullptr, L > 1 ? part : dw);
     if (L > 1) {
         const long long len = (long long)Cin * Cout;
-        hipLaunchKernelGGL(leaf_tree_kernel, dim3(grid_1dm(len)), dim3(256), 0, s, part, len, L, dw);
+        hipLaunchKernelGGL(slab_tree_kernel<1>, dim3(grid_1d(len, kGridCap)), dim3(256), 0, s, part, len, L, dw);
     }
     return hipGetLastError();
 }
@@ -381,117 +380,19 @@ hipError_t launch_conv1x1_dgrad(const float *dy, const float *w, const float *ad
     return hipGetLastError();
 }
 
-// ---- depthwise 3x3 stride-1 'same' backward ------------------------------------------------------------------------------------------
-// dgrad: the depthwise conv of dy with the taps flipped; a float4 of channels per lane, as dwconv3x3_kernel
-__global__ void __launch_bounds__(256) dwconv3x3_dgrad_kernel(const float4 *__restrict__ dy, const float4 *__restrict__ w, int H, int W, int C4,
-                                                             long long total, float4 *__restrict__ dx)
+// ---- depthwise 3x3 backward, stride 1 ('same') and stride 2 (block_1, block_3, block_6 and block_13's depthwise; Keras
+// ZeroPadding2D(correct_pad) + 'valid') --------------------------------------------------------------------------------------------------
+// The forward reads x[STRIDE oy + r - pt][STRIDE ox + s - pl] for output (oy, ox).  Stride 1 is pt = pl = 1, OH = H, OW = W (folded in
+// at compile time); stride 2 has pt = H % 2, pl = W % 2 (mn_s2_geom).
+// dgrad: input pixel (y, x) is read by output ((y + pt - r) / STRIDE, (x + pl - s) / STRIDE) where both are exact and in range: the
+// depthwise conv of dy with the taps flipped at stride 1, at most 2 x 2 taps at stride 2.  Every dx element is written once (pixels
+// no output reads get zeros); a float4 of channels per lane, as dwconv3x3_kernel.
+template <int STRIDE>
+__global__ void __launch_bounds__(256) dwconv3x3_dgrad_kernel(const float4 *__restrict__ dy, const float4 *__restrict__ w, int H, int W,
+                                                             int OH_, int OW_, int pt_, int pl_, int C4, long long total,
+                                                             float4 *__restrict__ dx)
 {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        long long t = i / C4;
-        const int ox = (int)(t % W);
-        t /= W;
-        const int oy = (int)(t % H);
-        const long long b = t / H;
-        float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int iy = oy + 1 - r;
-            if (iy < 0 || iy >= H) continue;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const int ix = ox + 1 - s;
-                if (ix < 0 || ix >= W) continue;
-                const float4 v = dy[((b * H + iy) * W + ix) * C4 + c];
-                const float4 k = w[(r * 3 + s) * C4 + c];
-                acc.x = fmaf(v.x, k.x, acc.x);
-                acc.y = fmaf(v.y, k.y, acc.y);
-                acc.z = fmaf(v.z, k.z, acc.z);
-                acc.w = fmaf(v.w, k.w, acc.w);
-            }
-        }
-        dx[i] = acc;
-    }
-}
-
-// wgrad: part[leaf][9][C] = the nine per-channel sums over the leaf's pixels.  grid (ceil(C / 64), leaves)
-__global__ void __launch_bounds__(256) dwconv3x3_wgrad_partial_kernel(const float4 *__restrict__ x, const float4 *__restrict__ dy, int B, int H,
-                                                                     int W, int C, int leaves, float *__restrict__ part)
-{
-    __shared__ float red[kRedLanes][kRedQuads * 36];
-    const int q = threadIdx.x & (kRedQuads - 1), rl = threadIdx.x / kRedQuads;
-    const int C4 = C / 4, cq = blockIdx.x * kRedQuads + q, leaf = blockIdx.y;
-    const long long P = (long long)B * H * W, pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
-    float4 acc[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (cq < C4) {
-        for (long long p = pbeg + rl; p < pend; p += kRedLanes) {
-            const int px = (int)(p % W), py = (int)((p / W) % H);
-            const long long b = p / ((long long)W * H);
-            const float4 d = dy[p * C4 + cq];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int iy = py + r - 1;
-                if (iy < 0 || iy >= H) continue;
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    const int ix = px + s - 1;
-                    if (ix < 0 || ix >= W) continue;
-                    const float4 v = x[((b * H + iy) * W + ix) * C4 + cq];
-                    float4 &a = acc[r * 3 + s];
-                    a.x = fmaf(v.x, d.x, a.x);
-                    a.y = fmaf(v.y, d.y, a.y);
-                    a.z = fmaf(v.z, d.z, a.z);
-                    a.w = fmaf(v.w, d.w, a.w);
-                }
-            }
-        }
-    }
-    // red[lane][tap][64 channels of the tile]
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        red[rl][t * 64 + 4 * q + 0] = acc[t].x;
-        red[rl][t * 64 + 4 * q + 1] = acc[t].y;
-        red[rl][t * 64 + 4 * q + 2] = acc[t].z;
-        red[rl][t * 64 + 4 * q + 3] = acc[t].w;
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < 9 * 64; o += 256) {
-        const int t = o / 64, ch = blockIdx.x * 64 + (o % 64);
-        float a = 0.0f;
-        for (int l = 0; l < kRedLanes; ++l) a += red[l][o];
-        if (ch < C) part[((size_t)leaf * 9 + t) * C + ch] = a;
-    }
-}
-
-hipError_t launch_dwconv3x3_dgrad(const float *dy, const float *w, int B, int H, int W, int C, float *dx, hipStream_t s)
-{
-    const long long total = (long long)B * H * W * (C / 4);
-    hipLaunchKernelGGL(dwconv3x3_dgrad_kernel, dim3(grid_1dm(total)), dim3(256), 0, s, reinterpret_cast<const float4 *>(dy),
-                       reinterpret_cast<const float4 *>(w), H, W, C / 4, total, reinterpret_cast<float4 *>(dx));
-    return hipGetLastError();
-}
-
-size_t dwconv3x3_wgrad_ws_floats(long long P, int C) { return (size_t)mn_reduce_leaves(P) * 9 * C; }
-
-hipError_t launch_dwconv3x3_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *part, float *dw, hipStream_t s)
-{
-    const int leaves = mn_reduce_leaves((long long)B * H * W);
-    hipLaunchKernelGGL(dwconv3x3_wgrad_partial_kernel, dim3((C + 63) / 64, leaves), dim3(256), 0, s, reinterpret_cast<const float4 *>(x),
-                       reinterpret_cast<const float4 *>(dy), B, H, W, C, leaves, part);
-    hipLaunchKernelGGL(leaf_tree_kernel, dim3(grid_1dm(9LL * C)), dim3(256), 0, s, part, 9LL * C, leaves, dw);
-    return hipGetLastError();
-}
-
-// ---- depthwise 3x3 stride-2 backward (block_1, block_3, block_6 and block_13's depthwise; Keras ZeroPadding2D(correct_pad) + 'valid') --
-// The forward reads x[2 oy + r - pt][2 ox + s - pl] for output (oy, ox), pt = H % 2, pl = W % 2 (mn_s2_geom).
-// dgrad: input pixel (y, x) is read by output ((y + pt - r) / 2, (x + pl - s) / 2) where both are exact and in range: at most 2 x 2 taps.
-// Every dx element is written once (pixels no output reads get zeros); a float4 of channels per lane.
-__global__ void __launch_bounds__(256) dwconv3x3_s2_dgrad_kernel(const float4 *__restrict__ dy, const float4 *__restrict__ w, int H, int W,
-                                                                int OH, int OW, int pt, int pl, int C4, long long total,
-                                                                float4 *__restrict__ dx)
-{
+    const int OH = STRIDE == 1 ? H : OH_, OW = STRIDE == 1 ? W : OW_, pt = STRIDE == 1 ? 1 : pt_, pl = STRIDE == 1 ? 1 : pl_;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % C4);
         long long t = i / C4;
@@ -503,12 +404,12 @@ __global__ void __launch_bounds__(256) dwconv3x3_s2_dgrad_kernel(const float4 *_
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const int ny = iy + pt - r;
-            if (ny < 0 || (ny & 1) || (ny >> 1) >= OH) continue;
+            if (ny < 0 || (STRIDE == 2 && (ny & 1)) || ny / STRIDE >= OH) continue;
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
                 const int nx = ix + pl - s;
-                if (nx < 0 || (nx & 1) || (nx >> 1) >= OW) continue;
-                const float4 v = dy[((b * OH + (ny >> 1)) * OW + (nx >> 1)) * C4 + c];
+                if (nx < 0 || (STRIDE == 2 && (nx & 1)) || nx / STRIDE >= OW) continue;
+                const float4 v = dy[((b * OH + ny / STRIDE) * OW + nx / STRIDE) * C4 + c];
                 const float4 k = w[(r * 3 + s) * C4 + c];
                 acc.x = fmaf(v.x, k.x, acc.x);
                 acc.y = fmaf(v.y, k.y, acc.y);
@@ -520,35 +421,39 @@ __global__ void __launch_bounds__(256) dwconv3x3_s2_dgrad_kernel(const float4 *_
     }
 }
 
-// wgrad: part[leaf][9][C] = the nine per-channel sums over the leaf's OUTPUT pixels.  grid (ceil(C / 32), leaves); a workgroup is 8
-// channel quads x 32 row lanes (the stride-2 layers have 96 .. 576 channels and up to 125 000 output pixels: narrower channel tiles
-// give the grid three times the workgroups of the stride-1 kernel's 64-channel tile at the same leaf count).  The nine taps of a
-// lane's four channels stay in registers; a leaf is summed lane by lane in order.
+// wgrad: part[leaf][9][C] = the nine per-channel sums over the leaf's OUTPUT pixels.  grid (ceil(C / (4 QUADS)), leaves); a workgroup
+// is QUADS channel quads x LANES pixel lanes: 16 x 16 at stride 1; 8 x 32 at stride 2 (those layers have 96 .. 576 channels and up to
+// 125 000 output pixels: narrower channel tiles give the grid three times the workgroups of the 64-channel tile at the same leaf
+// count).  The nine taps of a lane's four channels stay in registers; a lane takes its pixels in order, and a leaf is summed lane by
+// lane in order (lane_sum_store).
 constexpr int kS2Quads = 8, kS2Lanes = 32;
 
-__global__ void __launch_bounds__(256) dwconv3x3_s2_wgrad_partial_kernel(const float4 *__restrict__ x, const float4 *__restrict__ dy, int B,
-                                                                        int H, int W, int OH, int OW, int pt, int pl, int C, int leaves,
-                                                                        float *__restrict__ part)
+template <int STRIDE, int QUADS, int LANES>
+__global__ void __launch_bounds__(256) dwconv3x3_wgrad_partial_kernel(const float4 *__restrict__ x, const float4 *__restrict__ dy, int B,
+                                                                     int H, int W, int OH_, int OW_, int pt_, int pl_, int C, int leaves,
+                                                                     float *__restrict__ part)
 {
-    __shared__ float red[kS2Lanes][9 * kS2Quads * 4];
-    const int q = threadIdx.x & (kS2Quads - 1), rl = threadIdx.x / kS2Quads;
-    const int C4 = C / 4, cq = blockIdx.x * kS2Quads + q, leaf = blockIdx.y;
+    static_assert(QUADS * LANES == 256, "a workgroup of 256 threads");
+    __shared__ float red[LANES][9 * QUADS * 4];
+    const int OH = STRIDE == 1 ? H : OH_, OW = STRIDE == 1 ? W : OW_, pt = STRIDE == 1 ? 1 : pt_, pl = STRIDE == 1 ? 1 : pl_;
+    const int q = threadIdx.x & (QUADS - 1), rl = threadIdx.x / QUADS;
+    const int C4 = C / 4, cq = blockIdx.x * QUADS + q, leaf = blockIdx.y;
     const long long P = (long long)B * OH * OW, pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
     float4 acc[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (cq < C4) {
-        for (long long p = pbeg + rl; p < pend; p += kS2Lanes) {
+        for (long long p = pbeg + rl; p < pend; p += LANES) {
             const int ox = (int)(p % OW), oy = (int)((p / OW) % OH);
             const long long b = p / ((long long)OW * OH);
             const float4 d = dy[p * C4 + cq];
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
-                const int iy = 2 * oy + r - pt;
+                const int iy = STRIDE * oy + r - pt;
                 if (iy < 0 || iy >= H) continue;
 #pragma unroll
                 for (int s = 0; s < 3; ++s) {
-                    const int ix = 2 * ox + s - pl;
+                    const int ix = STRIDE * ox + s - pl;
                     if (ix < 0 || ix >= W) continue;
                     const float4 v = x[((b * H + iy) * W + ix) * C4 + cq];
                     float4 &a = acc[r * 3 + s];
@@ -560,22 +465,26 @@ __global__ void __launch_bounds__(256) dwconv3x3_s2_wgrad_partial_kernel(const f
             }
         }
     }
-    // red[lane][tap][32 channels of the tile]
-    constexpr int TC = kS2Quads * 4;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        red[rl][t * TC + 4 * q + 0] = acc[t].x;
-        red[rl][t * TC + 4 * q + 1] = acc[t].y;
-        red[rl][t * TC + 4 * q + 2] = acc[t].z;
-        red[rl][t * TC + 4 * q + 3] = acc[t].w;
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < 9 * TC; o += 256) {
-        const int t = o / TC, ch = blockIdx.x * TC + (o % TC);
-        float a = 0.0f;
-        for (int l = 0; l < kS2Lanes; ++l) a += red[l][o];
-        if (ch < C) part[((size_t)leaf * 9 + t) * C + ch] = a;
-    }
+    lane_sum_store<QUADS, LANES>(red, acc, q, rl, blockIdx.x, C, part + (size_t)leaf * 9 * C);
+}
+
+hipError_t launch_dwconv3x3_dgrad(const float *dy, const float *w, int B, int H, int W, int C, float *dx, hipStream_t s)
+{
+    const long long total = (long long)B * H * W * (C / 4);
+    hipLaunchKernelGGL(dwconv3x3_dgrad_kernel<1>, dim3(grid_1d(total, kGridCap)), dim3(256), 0, s, reinterpret_cast<const float4 *>(dy),
+                       reinterpret_cast<const float4 *>(w), H, W, H, W, 1, 1, C / 4, total, reinterpret_cast<float4 *>(dx));
+    return hipGetLastError();
+}
+
+size_t dwconv3x3_wgrad_ws_floats(long long P, int C) { return (size_t)mn_reduce_leaves(P) * 9 * C; }
+
+hipError_t launch_dwconv3x3_wgrad(const float *x, const float *dy, int B, int H, int W, int C, float *part, float *dw, hipStream_t s)
+{
+    const int leaves = mn_reduce_leaves((long long)B * H * W);
+    hipLaunchKernelGGL((dwconv3x3_wgrad_partial_kernel<1, kRedQuads, kRedLanes>), dim3((C + 63) / 64, leaves), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(x), reinterpret_cast<const float4 *>(dy), B, H, W, H, W, 1, 1, C, leaves, part);
+    hipLaunchKernelGGL(slab_tree_kernel<1>, dim3(grid_1d(9LL * C, kGridCap)), dim3(256), 0, s, part, 9LL * C, leaves, dw);
+    return hipGetLastError();
 }
 
 hipError_t launch_dwconv3x3_s2_dgrad(const float *dy, const float *w, int B, int H, int W, int C, float *dx, hipStream_t s)
@@ -584,7 +493,7 @@ hipError_t launch_dwconv3x3_s2_dgrad(const float *dy, const float *w, int B, int
     mn_s2_geom(H, &pt, &OH);
     mn_s2_geom(W, &pl, &OW);
     const long long total = (long long)B * H * W * (C / 4);
-    hipLaunchKernelGGL(dwconv3x3_s2_dgrad_kernel, dim3(grid_1dm(total)), dim3(256), 0, s, reinterpret_cast<const float4 *>(dy),
+    hipLaunchKernelGGL(dwconv3x3_dgrad_kernel<2>, dim3(grid_1d(total, kGridCap)), dim3(256), 0, s, reinterpret_cast<const float4 *>(dy),
                        reinterpret_cast<const float4 *>(w), H, W, OH, OW, pt, pl, C / 4, total, reinterpret_cast<float4 *>(dx));
     return hipGetLastError();
 }
@@ -603,9 +512,10 @@ hipError_t launch_dwconv3x3_s2_wgrad(const float *x, const float *dy, int B, int
     mn_s2_geom(H, &pt, &OH);
     mn_s2_geom(W, &pl, &OW);
     const int leaves = mn_reduce_leaves((long long)B * OH * OW);
-    hipLaunchKernelGGL(dwconv3x3_s2_wgrad_partial_kernel, dim3((C + kS2Quads * 4 - 1) / (kS2Quads * 4), leaves), dim3(256), 0, s,
-                       reinterpret_cast<const float4 *>(x), reinterpret_cast<const float4 *>(dy), B, H, W, OH, OW, pt, pl, C, leaves, part);
-    hipLaunchKernelGGL(leaf_tree_kernel, dim3(grid_1dm(9LL * C)), dim3(256), 0, s, part, 9LL * C, leaves, dw);
+    hipLaunchKernelGGL((dwconv3x3_wgrad_partial_kernel<2, kS2Quads, kS2Lanes>), dim3((C + kS2Quads * 4 - 1) / (kS2Quads * 4), leaves),
+                       dim3(256), 0, s, reinterpret_cast<const float4 *>(x), reinterpret_cast<const float4 *>(dy), B, H, W, OH, OW, pt, pl,
+                       C, leaves, part);
+    hipLaunchKernelGGL(slab_tree_kernel<1>, dim3(grid_1d(9LL * C, kGridCap)), dim3(256), 0, s, part, 9LL * C, leaves, dw);
     return hipGetLastError();
 }
 
@@ -615,8 +525,8 @@ hipError_t launch_dwconv3x3_s2_wgrad(const float *x, const float *dy, int B, int
 // stem_wgrad_leaves(P) leaves (a power of two <= 256 from P alone: 32 leaves would leave 7/8 of the device idle); a leaf is one
 // workgroup per 32 output channels, 8 channel quads x 32 pixel lanes, a lane keeping its 27 taps x 4 channels in registers (dy read
 // once as a float4, the 27 image values of the pixel's window shared by the 8 quads through the cache).  The lanes are summed in order
-// through LDS, one filter row at a time; the leaves in a fixed tree: tree_sum32 over each group of 32, then the (up to 8) groups
-// pairwise.
+// through LDS, one filter row at a time (lane_sum_store); the leaves in a fixed tree (slab_tree_kernel<8>): tree_sum32 over each group
+// of 32, then the (up to 8) groups pairwise.
 constexpr int kStemMaxLeaves = 256;
 
 int stem_wgrad_leaves(long long P)
@@ -630,8 +540,7 @@ __global__ void __launch_bounds__(256) conv3x3_s2_cin3_wgrad_partial_kernel(cons
                                                                            int H, int W, int OH, int OW, int pt, int pl, int Cout,
                                                                            int leaves, float *__restrict__ part)
 {
-    constexpr int TC = kS2Quads * 4;
-    __shared__ float red[kS2Lanes][9 * TC];
+    __shared__ float red[kS2Lanes][9 * kS2Quads * 4];
     const int q = threadIdx.x & (kS2Quads - 1), rl = threadIdx.x / kS2Quads;
     const int C4 = Cout / 4, cq = blockIdx.x * kS2Quads + q, leaf = blockIdx.y;
     const long long P = (long long)B * OH * OW, pbeg = P * leaf / leaves, pend = P * (leaf + 1) / leaves;
@@ -668,34 +577,7 @@ __global__ void __launch_bounds__(256) conv3x3_s2_cin3_wgrad_partial_kernel(cons
 #pragma unroll
     for (int r = 0; r < 3; ++r) {                   // red[lane][(s, ci)][32 channels of the tile], one filter row per pass
         if (r) __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            red[rl][t * TC + 4 * q + 0] = acc[r * 9 + t].x;
-            red[rl][t * TC + 4 * q + 1] = acc[r * 9 + t].y;
-            red[rl][t * TC + 4 * q + 2] = acc[r * 9 + t].z;
-            red[rl][t * TC + 4 * q + 3] = acc[r * 9 + t].w;
-        }
-        __syncthreads();
-        for (int o = threadIdx.x; o < 9 * TC; o += 256) {
-            const int t = o / TC, ch = blockIdx.x * TC + (o % TC);
-            float a = 0.0f;
-            for (int l = 0; l < kS2Lanes; ++l) a += red[l][o];
-            if (ch < Cout) part[((size_t)leaf * 27 + r * 9 + t) * Cout + ch] = a;
-        }
-    }
-}
-
-// out[j] = the fixed two-level tree over the `leaves` (a power of two <= 256) slabs of len floats
-__global__ void __launch_bounds__(256) stem_tree_kernel(const float *__restrict__ part, long long len, int leaves, float *__restrict__ out)
-{
-    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < len; j += (long long)gridDim.x * 256) {
-        float v[kStemMaxLeaves / kMaxLeaves];
-#pragma unroll
-        for (int g = 0; g < kStemMaxLeaves / kMaxLeaves; ++g) {     // (an absent group is a zero, which changes no bit)
-            const int n = leaves - g * kMaxLeaves;
-            v[g] = n > 0 ? tree_sum32<float>(part + (size_t)g * kMaxLeaves * len + j, (size_t)len, n < kMaxLeaves ? n : kMaxLeaves) : 0.0f;
-        }
-        out[j] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+        lane_sum_store<kS2Quads, kS2Lanes>(red, acc + r * 9, q, rl, blockIdx.x, Cout, part + ((size_t)leaf * 27 + r * 9) * Cout);
     }
 }
 
@@ -716,7 +598,7 @@ hipError_t launch_conv3x3_s2_cin3_wgrad(const float *x, const float *dy, int B, 
     const int leaves = stem_wgrad_leaves((long long)B * OH * OW);
     hipLaunchKernelGGL(conv3x3_s2_cin3_wgrad_partial_kernel, dim3((Cout + kS2Quads * 4 - 1) / (kS2Quads * 4), leaves), dim3(256), 0, s, x,
                        reinterpret_cast<const float4 *>(dy), B, H, W, OH, OW, pt, pl, Cout, leaves, part);
-    hipLaunchKernelGGL(stem_tree_kernel, dim3(grid_1dm(27LL * Cout)), dim3(256), 0, s, part, 27LL * Cout, leaves, dw);
+    hipLaunchKernelGGL(slab_tree_kernel<kStemMaxLeaves / kMaxLeaves>, dim3(grid_1d(27LL * Cout, kGridCap)), dim3(256), 0, s, part, 27LL * Cout, leaves, dw);
     return hipGetLastError();
 }
 
@@ -730,7 +612,7 @@ template <typename... T> static bool al16(const T *...p) { return ((... | (uintp
 #define MN_ALIGNED(what, ...) RPN_REQUIRE(al16(__VA_ARGS__), what ": every device pointer must be 16-byte aligned")
 
 static bool pc_ok(long long P, int C) { return P >= 1 && P <= (1ll << 31) && C >= 4 && C % 4 == 0 && C <= (1 << 16); }
-static size_t bn_ws_bytes(long long P, int C) { return a256m(bn_part_doubles(P, C) * sizeof(double)) + a256m((size_t)C * sizeof(float)); }
+static size_t bn_ws_bytes(long long P, int C) { return a256(bn_part_doubles(P, C) * sizeof(double)) + a256((size_t)C * sizeof(float)); }
 
 extern "C" size_t rpn_batchnorm_workspace_bytes(long long P, int C) { return pc_ok(P, C) ? bn_ws_bytes(P, C) : 0; }
 
@@ -749,7 +631,7 @@ extern "C" int rpn_batchnorm_train_forward(const float *d_x, long long P, int C,
     RPN_REQUIRE_DEVICE();
     hipStream_t s = as_stream(stream);
     double *part = reinterpret_cast<double *>(d_ws);
-    float *rstd = reinterpret_cast<float *>((char *)d_ws + a256m(bn_part_doubles(P, C) * sizeof(double)));
+    float *rstd = reinterpret_cast<float *>((char *)d_ws + a256(bn_part_doubles(P, C) * sizeof(double)));
     hipError_t e = launch_bn_train_stats(d_x, P, C, eps, momentum, part, d_mean, d_var, rstd, d_moving_mean, d_moving_var, s);
     if (e == hipSuccess) e = launch_bn_apply(d_x, P, C, d_mean, rstd, d_gamma, d_beta, relu6, nullptr, d_y, s);
     return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_batchnorm_train_forward: %s", hipGetErrorString(e));
@@ -769,7 +651,7 @@ extern "C" int rpn_batchnorm_train_backward(const float *d_x, const float *d_dy,
     RPN_REQUIRE_DEVICE();
     hipStream_t s = as_stream(stream);
     double *part = reinterpret_cast<double *>(d_ws);
-    float *rstd = reinterpret_cast<float *>((char *)d_ws + a256m(bn_part_doubles(P, C) * sizeof(double)));
+    float *rstd = reinterpret_cast<float *>((char *)d_ws + a256(bn_part_doubles(P, C) * sizeof(double)));
     hipError_t e = launch_bn_rstd(d_var, C, eps, rstd, s);
     if (e == hipSuccess) e = launch_bn_backward(d_x, d_dy, P, C, d_mean, rstd, d_gamma, d_beta, relu6, part, d_dgamma, d_dbeta, d_dx, s);
     return e == hipSuccess ? RPN_OK : fail(RPN_ERR_NO_DEVICE, "rpn_batchnorm_train_backward: %s", hipGetErrorString(e));
@@ -782,7 +664,7 @@ static bool gemm_ok(long long P, int Cin, int Cout)
 
 extern "C" size_t rpn_conv1x1_wgrad_workspace_bytes(long long P, int Cin, int Cout)
 {
-    return gemm_ok(P, Cin, Cout) ? a256m(conv1x1_wgrad_ws_floats(P, Cin, Cout) * sizeof(float)) : 0;
+    return gemm_ok(P, Cin, Cout) ? a256(conv1x1_wgrad_ws_floats(P, Cin, Cout) * sizeof(float)) : 0;
 }
 
 extern "C" int rpn_conv1x1_wgrad(const float *d_x, const float *d_dy, long long P, int Cin, int Cout, float *d_dw, void *d_ws, size_t ws_bytes,
@@ -826,7 +708,7 @@ extern "C" int rpn_dwconv3x3_dgrad(const float *d_dy, const float *d_w, int B, i
 
 extern "C" size_t rpn_dwconv3x3_wgrad_workspace_bytes(int B, int H, int W, int C)
 {
-    return dw_ok(B, H, W, C) ? a256m(dwconv3x3_wgrad_ws_floats((long long)B * H * W, C) * sizeof(float)) : 0;
+    return dw_ok(B, H, W, C) ? a256(dwconv3x3_wgrad_ws_floats((long long)B * H * W, C) * sizeof(float)) : 0;
 }
 
 extern "C" int rpn_dwconv3x3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws, size_t ws_bytes,
@@ -854,7 +736,7 @@ extern "C" int rpn_dwconv3x3_s2_dgrad(const float *d_dy, const float *d_w, int B
 
 extern "C" size_t rpn_dwconv3x3_s2_wgrad_workspace_bytes(int B, int H, int W, int C)
 {
-    return dw_ok(B, H, W, C) ? a256m(dwconv3x3_s2_wgrad_ws_floats(B, H, W, C) * sizeof(float)) : 0;
+    return dw_ok(B, H, W, C) ? a256(dwconv3x3_s2_wgrad_ws_floats(B, H, W, C) * sizeof(float)) : 0;
 }
 
 extern "C" int rpn_dwconv3x3_s2_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int C, float *d_dw, void *d_ws,
@@ -872,7 +754,7 @@ extern "C" int rpn_dwconv3x3_s2_wgrad(const float *d_x, const float *d_dy, int B
 
 extern "C" size_t rpn_conv3x3_s2_cin3_wgrad_workspace_bytes(int B, int H, int W, int Cout)
 {
-    return dw_ok(B, H, W, Cout) ? a256m(conv3x3_s2_cin3_wgrad_ws_floats(B, H, W, Cout) * sizeof(float)) : 0;
+    return dw_ok(B, H, W, Cout) ? a256(conv3x3_s2_cin3_wgrad_ws_floats(B, H, W, Cout) * sizeof(float)) : 0;
 }
 
 extern "C" int rpn_conv3x3_s2_cin3_wgrad(const float *d_x, const float *d_dy, int B, int H, int W, int Cout, float *d_dw, void *d_ws,
