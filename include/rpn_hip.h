@@ -538,6 +538,61 @@ int rpn_roi_losses(const float *d_cls_logits, const float *d_reg_pred, const int
 int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const float *d_reg_pred, const float *d_cls_logits,
                           const float *variances, int B, int R, int C, float *d_boxes, float *d_scores, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Detection head: the fully-connected second stage on the RoI features (no reference counterpart: the reference stops at the
+ * proposals; the architecture -- two ReLU layers and a class-specific box regressor, the Fast R-CNN head -- is this project's choice,
+ * as the thresholds of rpn_roi_targets are).
+ *   pooled (B,R,ph,pw,Cf), what rpn_roi_pool writes, read as x (M = B R, K1 = ph pw Cf): Keras' Flatten of NHWC, index (i pw + j) Cf + c
+ *   fc1: h1 = relu(x  W1 + b1)    W1 (K1, H1)   Keras Dense layout, (in, out) row-major
+ *   fc2: h2 = relu(h1 W2 + b2)    W2 (H1, H2)
+ *   cls: logits = h2 Wc + bc      Wc (H2, C)    -> d_logits (M, C)    LOGITS: what rpn_roi_losses / rpn_roi_decode_scores take
+ *   reg: deltas = h2 Wr + br      Wr (H2, 4C)   -> d_deltas (M, 4C)   class-specific
+ *   Cf, H1, H2 multiples of 4; C >= 2.  No dropout (it would break the run-to-run bit identity of every training entry point).
+ * Arithmetic: exact float32 on v_mfma_f32_32x32x2_f32.  Forward: every output element is ONE fmaf chain in k order over the whole
+ *   of K starting from +0, then + bias, then max(., 0) where there is a ReLU; no split of K.  A row's result depends on that row
+ *   of the input and on the weights alone: the same RoI features give the same bits at any M and beside any other rows.
+ *   Backward: dW = in^T dZ and d_in = dZ W^T as rpn_conv1x1_wgrad / rpn_conv1x1_dgrad compute them (cls and reg as one matrix padded
+ *   to a multiple of 4 columns), db = the column sums of dZ (chunks of 64 rows in order, then the chunks in order), the ReLU mask
+ *   [h > 0] applied to d_h1 / d_h2 in place.  No floating-point atomics, every sum in a fixed order chosen from the shapes alone:
+ *   bit-identical from run to run.  Adam is the head trainer's (TF 2.0 ApplyAdam, alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t)
+ *   on the device), ONE launch over one flat buffer holding all eight tensors.
+ * The object owns all its device memory -- weights, and with trainable = 1 their gradients, Adam's m and v (zero at creation) and
+ *   the backward's buffers -- allocated at the first call that needs the device; create, memory_bytes and every argument check run
+ *   without one.  trainable = 0 (the inference head) holds the weights and the two hidden activations, which a forward overwrites,
+ *   and nothing else: memory_bytes reports weights (x 4 when trainable) and workspace separately.
+ *   set_layer / get_layer / get_gradient: HOST arrays, kernel (in, out) + bias (out), names "fc1" | "fc2" | "cls" | "reg"; every
+ *   layer must be set before a forward.  get_* synchronise `stream`; nothing else synchronises.
+ *   forward: M <= max_rows rows.  keep = 1 (trainable heads only) leaves the hidden activations for ONE use, the backward of that
+ *     forward: the head keeps one forward at a time.  Any later forward (kept or not) replaces it, set_layer and adam_step drop it
+ *     (the weights it was made with are gone); a forward with keep = 0 leaves nothing to go back through.
+ *   backward: d_pooled is the kept forward's input again -- the SAME pointer and M (it is not copied; its contents must not have
+ *     changed); anything else, or no kept forward, is RPN_ERR_INVALID: a backward never reads another forward's activations.  (A
+ *     second kept forward of the same buffer cannot be told from the first by this check; models.DetectionHead counts calls.)
+ *     d_grad_logits (M, C) and d_grad_deltas (M, 4C) are what rpn_roi_losses writes.  The eight parameter gradients REPLACE the
+ *     stored ones (get_gradient): they do not accumulate over calls.  d_grad_pooled (M, K1) or NULL: the gradient with respect to
+ *     the pooled features, what rpn_roi_pool_backward takes -- NULL skips that product.
+ *   adam_step: one update from the stored gradients; t += 1 (rpn_det_head_steps).
+ *   Sizes one launch can grid: K1, H1, H2 <= 65535 * 64, max_rows <= 65535 * 64 (create), M <= 65535 * 128 (rpn_fc_forward);
+ *   beyond them RPN_ERR_INVALID.  Every argument and state check (unset layers included) comes before the first device call.
+ * rpn_fc_forward: the forward product on its own, d_out (M, N) = act(d_a (M, K) d_w (K, N; leading dimension ldw) + d_bias (N) or
+ *   NULL), relu = 1: max(., 0).  K % 4 == 0, ldw % 4 == 0, ldw >= N (N itself is free: pad the rows of d_w); M free.
+ * d_pooled, d_grad_pooled, d_a, d_w 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct rpn_det_head rpn_det_head;
+int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, rpn_det_head **out);
+void rpn_det_head_destroy(rpn_det_head *h);
+int rpn_det_head_memory_bytes(const rpn_det_head *h, size_t *weights, size_t *workspace);
+int rpn_det_head_set_layer(rpn_det_head *h, const char *name, const float *kernel, const float *bias);
+int rpn_det_head_get_layer(rpn_det_head *h, const char *name, float *kernel, float *bias, void *stream);
+int rpn_det_head_get_gradient(rpn_det_head *h, const char *name, float *kernel, float *bias, void *stream);
+int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int M, int keep, float *d_logits, float *d_deltas, void *stream);
+int rpn_det_head_backward(rpn_det_head *h, const float *d_pooled, int M, const float *d_grad_logits, const float *d_grad_deltas,
+                          float *d_grad_pooled, void *stream);
+int rpn_det_head_adam_step(rpn_det_head *h, float lr, float beta_1, float beta_2, float epsilon, void *stream);
+long long rpn_det_head_steps(const rpn_det_head *h);
+int rpn_fc_forward(const float *d_a, const float *d_w, const float *d_bias, int M, int K, int N, int ldw, int relu, float *d_out,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,156 @@
+"""Times the detection head (B = 8, R = 300 -> M = 2400 rows, C = 21) in ONE process with HIP events, the variants interleaved round
+by round (median and minimum over the rounds), at the VGG16 (7 x 7 x 512) and MobileNetV2 (7 x 7 x 576) feature widths and hidden
+widths 4096 and 1024:
+
+    head forward     rpn_det_head_forward (keep = 1): fc1, fc2, cls | reg
+    head backward    rpn_det_head_backward with the gradient of the pooled features
+    head adam        rpn_det_head_adam_step (one launch over all eight tensors)
+    torch fwd+bwd+adam  the same four layers as torch.nn.Linear, float32, forward + backward (to the input) + torch.optim.Adam
+    fc1 rpn_fc_forward  the first layer alone on the new GEMM (bias, no activation), with its TFLOP/s
+    fc1 torch.addmm     the same product through torch
+    fc1 rpn_conv2d      the same product as a 1 x 1 conv on an (M, 1, 1, K) tensor: the library's way before rpn_fc_forward existed
+                        (a single-layer test entry: every call allocates, packs the kernel for its tiles and synchronises)
+
+Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
+    python scripts/det_head_bench.py [--rounds 5] [--iters 3] [--json PATH]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tf_rpn_amd import _lib as L  # noqa: E402
+from tf_rpn_amd.models import DetectionHead  # noqa: E402
+
+B, R, C = 8, 300, 21
+M = B * R
+PEAK_TF, GUIDE_TF = 157.3, 122.0          # float32 matrix peak of the MI355X; an untuned LDS-tiled f32 MFMA GEMM at 4096^3
+
+
+def time_variants(variants, rounds, iters):
+    """{name: callable} -> {name: (median_us, min_us)}; each round times every variant once (iters calls between two events)."""
+    for fn in variants.values():
+        fn()
+    torch.cuda.synchronize()
+    samples = {n: [] for n in variants}
+    for _ in range(rounds):
+        for name, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            samples[name].append(e0.elapsed_time(e1) * 1e3 / iters)
+    return {n: (float(np.median(v)), float(np.min(v))) for n, v in samples.items()}
+
+
+def bench_config(lib, channels, hidden, rounds, iters):
+    K1 = 7 * 7 * channels
+    head = DetectionHead(C, pooling_size=(7, 7), channels=channels, hidden=(hidden, hidden), max_rois=M, seed=1)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    pooled = torch.rand((B, R, 7, 7, channels), device="cuda", generator=gen)
+    logits, deltas = torch.empty((B, R, C), device="cuda"), torch.empty((B, R, 4 * C), device="cuda")
+    g_logits = torch.randn((B, R, C), device="cuda", generator=gen) / M
+    g_deltas = torch.randn((B, R, 4 * C), device="cuda", generator=gen) / M
+    g_pooled = torch.empty_like(pooled)
+    stream = L.stream_ptr()
+    h = head._h
+
+    def fwd():
+        L.check(lib.rpn_det_head_forward(h, L.ptr(pooled), M, 1, L.ptr(logits), L.ptr(deltas), stream), "forward")
+
+    def bwd():
+        L.check(lib.rpn_det_head_backward(h, L.ptr(pooled), M, L.ptr(g_logits), L.ptr(g_deltas), L.ptr(g_pooled), stream), "backward")
+
+    def adam():
+        L.check(lib.rpn_det_head_adam_step(h, 1e-4, 0.9, 0.999, 1e-7, stream), "adam")
+
+    # the same layers in torch
+    fc1, fc2 = torch.nn.Linear(K1, hidden, device="cuda"), torch.nn.Linear(hidden, hidden, device="cuda")
+    cls, reg = torch.nn.Linear(hidden, C, device="cuda"), torch.nn.Linear(hidden, 4 * C, device="cuda")
+    params = [p for m in (fc1, fc2, cls, reg) for p in m.parameters()]
+    opt = torch.optim.Adam(params, lr=1e-4, eps=1e-7)
+    x_t = pooled.reshape(M, K1).clone().requires_grad_()
+
+    def torch_step():
+        opt.zero_grad(set_to_none=True)
+        x_t.grad = None
+        h2 = torch.relu(fc2(torch.relu(fc1(x_t))))
+        torch.autograd.backward([cls(h2), reg(h2)], [g_logits.reshape(M, C), g_deltas.reshape(M, 4 * C)])
+        opt.step()
+
+    # the first layer alone
+    w1 = fc1.weight.detach().t().contiguous()                  # (K1, hidden), the Dense layout
+    b1 = fc1.bias.detach().clone()
+    x2 = pooled.reshape(M, K1)
+    out = torch.empty((M, hidden), device="cuda")
+
+    def fc_new():
+        L.check(lib.rpn_fc_forward(L.ptr(x2), L.ptr(w1), L.ptr(b1), M, K1, hidden, hidden, 0, L.ptr(out), stream), "rpn_fc_forward")
+
+    def fc_torch():
+        torch.addmm(b1, x2, w1, out=out)
+
+    def fc_conv():
+        L.check(lib.rpn_conv2d(L.ptr(x2), M, 1, 1, K1, L.ptr(w1), L.ptr(b1), 1, 1, hidden, 1, 0, 0, 1, 1, 0, 0, L.ptr(out), stream),
+                "rpn_conv2d")
+
+    variants = {"head forward": fwd, "head backward": bwd, "head adam": adam, "torch fwd+bwd+adam": torch_step, "fc1 rpn_fc_forward": fc_new,
+                "fc1 torch.addmm": fc_torch}
+    fwd()                                                       # the backward needs a kept forward; every timed backward reuses the last one
+    conv_note = None
+    try:
+        fc_conv()
+        conv = out.clone()
+        fc_new()
+        conv_note = "max |rpn_conv2d - rpn_fc_forward| = %.3e" % float((conv - out).abs().max())
+        variants["fc1 rpn_conv2d"] = fc_conv
+    except (ValueError, RuntimeError) as e:
+        conv_note = "rpn_conv2d refuses this shape: %s" % e
+    order = ["head forward", "head backward", "head adam", "torch fwd+bwd+adam", "fc1 rpn_fc_forward", "fc1 torch.addmm", "fc1 rpn_conv2d"]
+    variants = {n: variants[n] for n in order if n in variants}
+    res = time_variants(variants, rounds, iters)
+    flop1 = 2.0 * M * K1 * hidden
+    tf = {n: flop1 / (res[n][0] * 1e-6) / 1e12 for n in res if n.startswith("fc1")}
+    w_bytes, ws_bytes = head.memory_bytes()
+    return dict(us_median_min=res, fc1_tflops=tf, conv_note=conv_note, weights_bytes=w_bytes, workspace_bytes=ws_bytes)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--json", default=None)
+    args = ap.parse_args()
+    L.require_gpu()
+    lib = L.lib()
+    results = {}
+    for backbone, channels in (("vgg16", 512), ("mobilenet_v2", 576)):
+        for hidden in (4096, 1024):
+            label = "%s K1=%d H=%d" % (backbone, 49 * channels, hidden)
+            results[label] = bench_config(lib, channels, hidden, args.rounds, args.iters)
+            torch.cuda.empty_cache()
+    print("%-32s %-20s %12s %12s %10s" % ("shape (M = %d)" % M, "variant", "median us", "min us", "TFLOP/s"))
+    for label, row in results.items():
+        for name, v in row["us_median_min"].items():
+            tf = row["fc1_tflops"].get(name)
+            print("%-32s %-20s %12.1f %12.1f %10s" % (label, name, v[0], v[1], "%.1f" % tf if tf else ""))
+        print("%-32s %s" % (label, row["conv_note"]))
+    print("float32 matrix peak %.1f TFLOP/s; untuned LDS-tiled f32 MFMA GEMM (4096^3) %.1f TFLOP/s" % (PEAK_TF, GUIDE_TF))
+    line = json.dumps({"B": B, "R": R, "C": C, "rounds": args.rounds, "iters": args.iters, "peak_tflops": PEAK_TF, "guide_tflops": GUIDE_TF,
+                       "results": results})
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()

@@ -124,6 +124,17 @@ _SIGNATURES = {
     "rpn_roi_losses_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "rpn_roi_losses": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "rpn_roi_decode_scores": (ctypes.c_int, [vp, vp, vp, vp, c_float_p] + [ctypes.c_int] * 3 + [vp, vp, vp]),
+    "rpn_det_head_create": (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(vp)]),
+    "rpn_det_head_destroy": (None, [vp]),
+    "rpn_det_head_memory_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "rpn_det_head_set_layer": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p]),
+    "rpn_det_head_get_layer": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p, vp]),
+    "rpn_det_head_get_gradient": (ctypes.c_int, [vp, ctypes.c_char_p, c_float_p, c_float_p, vp]),
+    "rpn_det_head_forward": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    "rpn_det_head_backward": (ctypes.c_int, [vp, vp, ctypes.c_int, vp, vp, vp, vp]),
+    "rpn_det_head_adam_step": (ctypes.c_int, [vp] + [ctypes.c_float] * 4 + [vp]),
+    "rpn_det_head_steps": (ctypes.c_longlong, [vp]),
+    "rpn_fc_forward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp]),
 }
 
 _lib = None

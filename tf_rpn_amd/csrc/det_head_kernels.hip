@@ -1,0 +1,459 @@
+// det_head_kernels.hip -- the detection head: two fully-connected ReLU layers on the flattened RoI features and the cls | reg output
+// pair (rpn_det_head_*, rpn_fc_forward; contract in include/rpn_hip.h).  New here: the forward GEMM (fc_forward_f32_kernel) and two
+// small element-wise kernels.  The backward reuses the 1x1-conv backward GEMMs (train_mnv2.h), the column sums and Adam
+// (train_head.h) unchanged; after each input-gradient GEMM one in-place pass applies the ReLU mask (launch_relu_mask).
+#include <cstdint>
+#include <cstring>
+
+#include "det_head.h"
+#include "rpn_common.h"
+#include "train_common.h"
+#include "train_head.h"
+#include "train_mnv2.h"
+
+namespace rpn {
+
+static constexpr int kGridCap = 4096;          // workgroups of this file's grid-stride kernels
+
+// ---- forward GEMM on v_mfma_f32_32x32x2_f32 ------------------------------------------------------------------------------------------
+// out (M x N) = act(A (M x K, K contiguous) W (K x N, N contiguous, leading dimension ldw) + bias).
+// Workgroup: a 128 x 128 tile, four waves of 64 x 64 = 2 x 2 MFMA blocks of 32 x 32 (four independent accumulators per wave: the
+// 64-cycle dependent latency of the instruction is covered inside one wave).  K slices of 32 are staged global -> registers -> LDS,
+// double buffered with one barrier per slice, the next slice's loads in flight under this slice's 64 MFMAs per wave.
+//   A: a thread loads float4s along K (rows tid / 8 + 32 i, K quad tid % 8) and stores them transposed, As[k][m ^ 4 (k / 4 % 8)]:
+//      ds_write_b32 banks are (address / 4) % 32 per 32-lane half; a half holds 8 K quads x 4 consecutive rows, and the XOR sends
+//      quad q of row 4 g + r to bank 4 (g ^ q) + r -- 32 different banks.  The XOR permutes columns inside an aligned group of 32,
+//      so a fragment read (32 consecutive rows of one k per half-wave) stays conflict free, and k / 4 % 8 of the k = 2 kk + lane / 32
+//      a lane reads at step kk is kk / 2 % 8: the same for the whole wave.
+//   W: float4s along N (K rows tid / 32 + 8 i, column quad tid % 32), stored as they are: a half-wave writes one whole row.
+// 2 x 32 x (128 + 128) floats = 64 KB of LDS: two workgroups per CU.
+// Each accumulator element is one fmaf chain in k order over the whole of K (no split of K, no partial tiles added later); slices
+// beyond K and rows / columns beyond the matrix enter as zeros.  Row m's result reads row m of A only.
+// M, N and K tails are guarded; stores are scalar and guarded (N need not be a multiple of 4), columns < split to out0, the others
+// to out1.
+constexpr int kFcBM = 128, kFcBN = 128, kFcBK = 32;
+// grid.y holds the row tiles of the forward (128 rows) and of launch_conv1x1_dgrad (64 rows), and the input-channel tiles of
+// launch_conv1x1_wgrad (64 channels): what one launch can cover
+constexpr long long kMaxGridY = 65535;
+constexpr long long kFcMaxRows = kMaxGridY * kFcBM, kHeadMaxRows = kMaxGridY * 64, kHeadMaxWidth = kMaxGridY * 64;
+
+__global__ void __launch_bounds__(256) fc_forward_f32_kernel(const float *__restrict__ A, const float *__restrict__ W,
+                                                            const float *__restrict__ bias, int M, int K, int N, int ldw, int relu,
+                                                            int split, float *__restrict__ out0, float *__restrict__ out1)
+{
+    __shared__ __attribute__((aligned(16))) float As[2][kFcBK][kFcBM];
+    __shared__ __attribute__((aligned(16))) float Bs[2][kFcBK][kFcBN];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, kh = lane >> 5;
+    const int n0 = blockIdx.x * kFcBN, m0 = blockIdx.y * kFcBM;
+    const int nsteps = (K + kFcBK - 1) / kFcBK;
+    const int ar = tid >> 3, akq = tid & 7, bk = tid >> 5, bq = tid & 31;
+    float4 ra[4], rb[4];
+    auto load_global = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ra[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            rb[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const int row = m0 + ar + 32 * i, ka = k0 + 4 * akq;
+            if (row < M && ka < K) ra[i] = *reinterpret_cast<const float4 *>(A + (size_t)row * K + ka);
+            const int kb = k0 + bk + 8 * i, col = n0 + 4 * bq;
+            if (kb < K && col < ldw) rb[i] = *reinterpret_cast<const float4 *>(W + (size_t)kb * ldw + col);
+        }
+    };
+    auto store_lds = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int m = (ar + 32 * i) ^ (4 * akq);
+            As[buf][4 * akq + 0][m] = ra[i].x;
+            As[buf][4 * akq + 1][m] = ra[i].y;
+            As[buf][4 * akq + 2][m] = ra[i].z;
+            As[buf][4 * akq + 3][m] = ra[i].w;
+            *reinterpret_cast<float4 *>(&Bs[buf][bk + 8 * i][4 * bq]) = rb[i];
+        }
+    };
+    f32x16t acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+
+    load_global(0);
+    store_lds(0);
+    __syncthreads();
+    int cur = 0;
+    for (int step = 0; step < nsteps; ++step) {
+        const bool more = step + 1 < nsteps;
+        if (more) load_global((step + 1) * kFcBK);
+#pragma unroll
+        for (int kk = 0; kk < kFcBK / 2; ++kk) {
+            const int k = 2 * kk + kh, sw = 4 * ((kk >> 1) & 7);
+            const float a0 = As[cur][k][(wm * 64 + l32) ^ sw], a1 = As[cur][k][(wm * 64 + 32 + l32) ^ sw];
+            const float b0 = Bs[cur][k][wn * 64 + l32], b1 = Bs[cur][k][wn * 64 + 32 + l32];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        if (more) store_lds(cur ^ 1);
+        __syncthreads();
+        cur ^= 1;
+    }
+    // accumulator element e: row 8 (e / 4) + 4 kh + e % 4, column lane % 32
+    const int n1 = N - split;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + wn * 64 + 32 * j + l32;
+        if (col >= N) continue;
+        const float bv = bias ? bias[col] : 0.0f;
+        float *dst = col < split ? out0 + col : out1 + (col - split);
+        const int ld = col < split ? split : n1;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = m0 + wm * 64 + 32 * i + 8 * (e >> 2) + 4 * kh + (e & 3);
+                if (row < M) {
+                    float v = bias ? acc[i][j][e] + bv : acc[i][j][e];
+                    if (relu) v = fmaxf(v, 0.0f);
+                    dst[(size_t)row * ld] = v;
+                }
+            }
+    }
+}
+
+__global__ void __launch_bounds__(256) pack_pair_grad_kernel(const float *__restrict__ gl, const float *__restrict__ gd, long long total,
+                                                            int C, int npad, float *__restrict__ dz)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long m = i / npad;
+        const int j = (int)(i - m * npad);
+        dz[i] = j < C ? gl[m * C + j] : j < 5 * C ? gd[m * 4 * C + (j - C)] : 0.0f;
+    }
+}
+
+__global__ void __launch_bounds__(256) relu_mask_kernel(float4 *__restrict__ g, const float4 *__restrict__ h, long long n4)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        float4 v = g[i];
+        const float4 a = h[i];
+        v.x = a.x > 0.0f ? v.x : 0.0f;
+        v.y = a.y > 0.0f ? v.y : 0.0f;
+        v.z = a.z > 0.0f ? v.z : 0.0f;
+        v.w = a.w > 0.0f ? v.w : 0.0f;
+        g[i] = v;
+    }
+}
+
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+hipError_t launch_fc_forward(const float *a, const float *w, const float *bias, int M, int K, int N, int ldw, int relu, int split,
+                             float *out0, float *out1, hipStream_t s)
+{
+    hipLaunchKernelGGL(fc_forward_f32_kernel, dim3((N + kFcBN - 1) / kFcBN, (M + kFcBM - 1) / kFcBM), dim3(256), 0, s, a, w, bias, M, K, N,
+                       ldw, relu, split, out0, out1);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_pair_grad(const float *grad_logits, const float *grad_deltas, int M, int C, int npad, float *dz, hipStream_t s)
+{
+    const long long total = (long long)M * npad;
+    hipLaunchKernelGGL(pack_pair_grad_kernel, dim3(grid_1d(total, kGridCap)), dim3(256), 0, s, grad_logits, grad_deltas, total, C, npad, dz);
+    return hipGetLastError();
+}
+
+hipError_t launch_relu_mask(float *g, const float *h, long long n, hipStream_t s)
+{
+    hipLaunchKernelGGL(relu_mask_kernel, dim3(grid_1d(n / 4, kGridCap)), dim3(256), 0, s, reinterpret_cast<float4 *>(g),
+                       reinterpret_cast<const float4 *>(h), n / 4);
+    return hipGetLastError();
+}
+
+}  // namespace rpn
+
+// ---- the head object -------------------------------------------------------------------------------------------------------------------
+// One flat parameter buffer w of n floats: W1 (K1, H1) | b1 (H1) | W2 (H1, H2) | b2 (H2) | Wp (H2, npad) | bp (npad), where Wp / bp
+// hold the cls | reg pair side by side, columns [0, C) cls, [C, 5 C) reg, [5 C, npad) zeros, npad = 5 C rounded up to 4.  A trainable
+// head has g, m and v of the same layout (the padding's gradient is zero, so Adam leaves it zero).  Device memory is allocated at the
+// first call that needs it; create itself touches no device.
+struct rpn_det_head {
+    int ph, pw, cf, h1, h2, c, max_rows, trainable;
+    int k1, npad;
+    size_t off[6], n;            // W1, b1, W2, b2, Wp, bp; the total
+    size_t part_floats;          // reduction scratch of the backward (weight-gradient slabs or column-sum chunks, whichever is larger)
+    float *w = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
+    float *a1 = nullptr, *a2 = nullptr;                       // the two hidden activations (max_rows, H1) / (max_rows, H2)
+    float *dz = nullptr, *d1 = nullptr, *d2 = nullptr, *part = nullptr;
+    unsigned loaded = 0;         // bit per layer: fc1, fc2, cls, reg
+    int kept_rows = 0;           // rows of the forward whose activations the backward may read; 0: none
+    const float *kept_pooled = nullptr;   // ... and that forward's input: the backward must be handed the same tensor
+    long long t = 0;
+};
+
+namespace {
+using namespace rpn;
+
+const char *const kLayerNames[4] = {"fc1", "fc2", "cls", "reg"};
+
+int layer_index(const char *name)
+{
+    for (int i = 0; name && i < 4; ++i)
+        if (!strcmp(name, kLayerNames[i])) return i;
+    return -1;
+}
+
+// where layer i's kernel and bias live inside a buffer of the parameter layout: rows x cols floats at leading dimension ld
+struct LayerView {
+    size_t kernel, bias;
+    int rows, cols, ld;
+};
+
+LayerView layer_view(const rpn_det_head *h, int i)
+{
+    switch (i) {
+    case 0: return {h->off[0], h->off[1], h->k1, h->h1, h->h1};
+    case 1: return {h->off[2], h->off[3], h->h1, h->h2, h->h2};
+    case 2: return {h->off[4], h->off[5], h->h2, h->c, h->npad};
+    default: return {h->off[4] + (size_t)h->c, h->off[5] + (size_t)h->c, h->h2, 4 * h->c, h->npad};
+    }
+}
+
+size_t head_workspace_bytes(const rpn_det_head *h)
+{
+    const size_t R = (size_t)h->max_rows;
+    size_t b = a256(R * h->h1 * sizeof(float)) + a256(R * h->h2 * sizeof(float));
+    if (h->trainable)
+        b += a256(R * h->npad * sizeof(float)) + a256(R * h->h1 * sizeof(float)) + a256(R * h->h2 * sizeof(float)) +
+             a256(h->part_floats * sizeof(float));
+    return b;
+}
+
+void head_free(rpn_det_head *h)
+{
+    for (float **p : {&h->w, &h->g, &h->m, &h->v, &h->a1, &h->a2, &h->dz, &h->d1, &h->d2, &h->part}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    h->loaded = 0;               // the weights went with the buffers
+    h->kept_rows = 0;
+}
+
+// the head's device memory, once; zeros everywhere (the padding columns of the pair stay zero for ever)
+int head_ensure_device(rpn_det_head *h)
+{
+    if (h->w) return RPN_OK;
+    RPN_REQUIRE_DEVICE();
+    const size_t R = (size_t)h->max_rows;
+    struct { float **p; size_t n; bool zero; } bufs[] = {
+        {&h->w, h->n, true}, {&h->a1, R * h->h1, false}, {&h->a2, R * h->h2, false},
+        {&h->g, h->trainable ? h->n : 0, true}, {&h->m, h->trainable ? h->n : 0, true}, {&h->v, h->trainable ? h->n : 0, true},
+        {&h->dz, h->trainable ? R * h->npad : 0, false}, {&h->d1, h->trainable ? R * h->h1 : 0, false},
+        {&h->d2, h->trainable ? R * h->h2 : 0, false}, {&h->part, h->trainable ? h->part_floats : 0, false}};
+    for (auto &b : bufs) {
+        if (!b.n) continue;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(b.p), b.n * sizeof(float));
+        if (e == hipSuccess && b.zero) e = hipMemset(*b.p, 0, b.n * sizeof(float));
+        if (e != hipSuccess) {
+            head_free(h);
+            return fail(RPN_ERR_NO_DEVICE, "rpn_det_head: device allocation of %zu bytes failed: %s", b.n * sizeof(float),
+                        hipGetErrorString(e));
+        }
+    }
+    return RPN_OK;
+}
+
+// kernel / bias of layer `name` between HOST arrays and the buffer `base` (the weights or their gradient)
+int head_copy_layer(rpn_det_head *h, float *base, const char *name, float *kernel, float *bias, bool to_device, hipStream_t s)
+{
+    const LayerView lv = layer_view(h, layer_index(name));
+    const size_t wbytes = (size_t)lv.cols * sizeof(float);
+    if (to_device) {
+        RPN_HIP_CHECK(hipMemcpy2D(base + lv.kernel, (size_t)lv.ld * sizeof(float), kernel, wbytes, wbytes, lv.rows, hipMemcpyHostToDevice));
+        RPN_HIP_CHECK(hipMemcpy(base + lv.bias, bias, wbytes, hipMemcpyHostToDevice));
+    } else {
+        RPN_HIP_CHECK(hipMemcpy2DAsync(kernel, wbytes, base + lv.kernel, (size_t)lv.ld * sizeof(float), wbytes, lv.rows,
+                                       hipMemcpyDeviceToHost, s));
+        RPN_HIP_CHECK(hipMemcpyAsync(bias, base + lv.bias, wbytes, hipMemcpyDeviceToHost, s));
+        RPN_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    return RPN_OK;
+}
+
+}  // namespace
+
+extern "C" int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, rpn_det_head **out)
+{
+    const char *who = "rpn_det_head_create";
+    RPN_REQUIRE(out, "%s: null out", who);
+    *out = nullptr;
+    RPN_REQUIRE(ph >= 1 && pw >= 1, "%s: pooling size %d x %d", who, ph, pw);
+    RPN_REQUIRE(Cf >= 4 && Cf % 4 == 0, "%s: Cf = %d must be a positive multiple of 4", who, Cf);
+    RPN_REQUIRE(H1 >= 4 && H1 % 4 == 0 && H2 >= 4 && H2 % 4 == 0, "%s: H1 = %d and H2 = %d must be positive multiples of 4", who, H1, H2);
+    RPN_REQUIRE(C >= 2 && C <= (1 << 20), "%s: C = %d labels (background included) must be >= 2", who, C);
+    RPN_REQUIRE(max_rows >= 1, "%s: max_rows = %d", who, max_rows);
+    RPN_REQUIRE(trainable == 0 || trainable == 1, "%s: trainable must be 0 or 1", who);
+    const long long k1 = (long long)ph * pw * Cf;
+    const int npad = (5 * C + 3) / 4 * 4;
+    RPN_REQUIRE(k1 <= kHeadMaxWidth && H1 <= kHeadMaxWidth && H2 <= kHeadMaxWidth,
+                "%s: %d x %d x %d = %lld features, H1 = %d, H2 = %d: a layer's input may be at most %lld wide (one weight-gradient launch)", who,
+                ph, pw, Cf, k1, H1, H2, kHeadMaxWidth);
+    RPN_REQUIRE(max_rows <= kHeadMaxRows, "%s: max_rows = %d, at most %lld rows fit one input-gradient launch", who, max_rows, kHeadMaxRows);
+    rpn_det_head *h = new rpn_det_head();
+    h->ph = ph, h->pw = pw, h->cf = Cf, h->h1 = H1, h->h2 = H2, h->c = C, h->max_rows = max_rows, h->trainable = trainable;
+    h->k1 = (int)k1, h->npad = npad;
+    const size_t sizes[6] = {(size_t)k1 * H1, (size_t)H1, (size_t)H1 * H2, (size_t)H2, (size_t)H2 * npad, (size_t)npad};
+    h->n = 0;
+    for (int i = 0; i < 6; ++i) {
+        h->off[i] = h->n;
+        h->n += sizes[i];
+    }
+    const long long R = max_rows;
+    h->part_floats = std::max({conv1x1_wgrad_ws_floats(R, h->k1, H1), conv1x1_wgrad_ws_floats(R, H1, H2), conv1x1_wgrad_ws_floats(R, H2, npad),
+                               colsum_ws_floats(R, H1), colsum_ws_floats(R, H2), colsum_ws_floats(R, npad)});
+    *out = h;
+    return RPN_OK;
+}
+
+extern "C" void rpn_det_head_destroy(rpn_det_head *h)
+{
+    if (!h) return;
+    head_free(h);
+    delete h;
+}
+
+extern "C" int rpn_det_head_memory_bytes(const rpn_det_head *h, size_t *weights, size_t *workspace)
+{
+    RPN_REQUIRE(h && weights && workspace, "rpn_det_head_memory_bytes: null pointer");
+    *weights = h->n * sizeof(float) * (h->trainable ? 4 : 1);
+    *workspace = head_workspace_bytes(h);
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_set_layer(rpn_det_head *h, const char *name, const float *kernel, const float *bias)
+{
+    const char *who = "rpn_det_head_set_layer";
+    RPN_REQUIRE(h && name && kernel && bias, "%s: null pointer", who);
+    const int i = layer_index(name);
+    RPN_REQUIRE(i >= 0, "%s: unknown layer '%s' (fc1, fc2, cls, reg)", who, name);
+    int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    h->kept_rows = 0;            // a kept forward was made with the weights this call replaces
+    st = head_copy_layer(h, h->w, name, const_cast<float *>(kernel), const_cast<float *>(bias), true, nullptr);
+    if (st == RPN_OK) h->loaded |= 1u << i;
+    return st;
+}
+
+extern "C" int rpn_det_head_get_layer(rpn_det_head *h, const char *name, float *kernel, float *bias, void *stream)
+{
+    const char *who = "rpn_det_head_get_layer";
+    RPN_REQUIRE(h && name && kernel && bias, "%s: null pointer", who);
+    const int i = layer_index(name);
+    RPN_REQUIRE(i >= 0, "%s: unknown layer '%s' (fc1, fc2, cls, reg)", who, name);
+    RPN_REQUIRE(h->loaded >> i & 1u, "%s: layer '%s' was never set", who, name);
+    return head_copy_layer(h, h->w, name, kernel, bias, false, as_stream(stream));
+}
+
+extern "C" int rpn_det_head_get_gradient(rpn_det_head *h, const char *name, float *kernel, float *bias, void *stream)
+{
+    const char *who = "rpn_det_head_get_gradient";
+    RPN_REQUIRE(h && name && kernel && bias, "%s: null pointer", who);
+    const int i = layer_index(name);
+    RPN_REQUIRE(i >= 0, "%s: unknown layer '%s' (fc1, fc2, cls, reg)", who, name);
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
+    const int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    return head_copy_layer(h, h->g, name, kernel, bias, false, as_stream(stream));
+}
+
+extern "C" long long rpn_det_head_steps(const rpn_det_head *h) { return h ? h->t : 0; }
+
+extern "C" int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int M, int keep, float *d_logits, float *d_deltas,
+                                    void *stream)
+{
+    const char *who = "rpn_det_head_forward";
+    RPN_REQUIRE(h && d_pooled && d_logits && d_deltas, "%s: null pointer", who);
+    RPN_REQUIRE(M >= 1 && M <= h->max_rows, "%s: M = %d rows, the head was created for 1 .. %d", who, M, h->max_rows);
+    RPN_REQUIRE(keep == 0 || (keep == 1 && h->trainable), "%s: keep = %d on a head created with trainable = %d", who, keep, h->trainable);
+    RPN_REQUIRE(aligned16(d_pooled), "%s: the pooled features must be 16-byte aligned", who);
+    RPN_REQUIRE(h->loaded == 15u, "%s: set_layer has not been called for every layer (fc1, fc2, cls, reg)", who);
+    const int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    const hipStream_t s = as_stream(stream);
+    h->kept_rows = 0;                    // the activations of an earlier forward are overwritten from here on
+    hipError_t e = launch_fc_forward(d_pooled, h->w + h->off[0], h->w + h->off[1], M, h->k1, h->h1, h->h1, 1, h->h1, h->a1, nullptr, s);
+    if (e == hipSuccess) e = launch_fc_forward(h->a1, h->w + h->off[2], h->w + h->off[3], M, h->h1, h->h2, h->h2, 1, h->h2, h->a2, nullptr, s);
+    if (e == hipSuccess)
+        e = launch_fc_forward(h->a2, h->w + h->off[4], h->w + h->off[5], M, h->h2, 5 * h->c, h->npad, 0, h->c, d_logits, d_deltas, s);
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    if (keep) h->kept_rows = M, h->kept_pooled = d_pooled;
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_backward(rpn_det_head *h, const float *d_pooled, int M, const float *d_grad_logits,
+                                     const float *d_grad_deltas, float *d_grad_pooled, void *stream)
+{
+    const char *who = "rpn_det_head_backward";
+    RPN_REQUIRE(h && d_pooled && d_grad_logits && d_grad_deltas, "%s: null pointer", who);
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
+    RPN_REQUIRE(M >= 1 && M <= h->max_rows, "%s: M = %d rows, the head was created for 1 .. %d", who, M, h->max_rows);
+    RPN_REQUIRE(h->kept_rows == M && h->kept_pooled == d_pooled,
+                "%s: no kept forward of these %d rows (the kept forward, if any, had %d rows; any later forward, set_layer or adam_step "
+                "replaces or drops it)", who, M, h->kept_rows);
+    RPN_REQUIRE(aligned16(d_pooled) && aligned16(d_grad_pooled), "%s: the pooled features and their gradient must be 16-byte aligned", who);
+    const int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    const hipStream_t s = as_stream(stream);
+    const int K1 = h->k1, H1 = h->h1, H2 = h->h2, NP = h->npad;
+    float *w = h->w, *g = h->g;
+    // the pair: dz = [grad_logits | grad_deltas | 0]; dWp = a2^T dz, dbp = sum dz, d2 = (dz Wp^T) [a2 > 0]
+    hipError_t e = launch_pack_pair_grad(d_grad_logits, d_grad_deltas, M, h->c, NP, h->dz, s);
+    if (e == hipSuccess) e = launch_conv1x1_wgrad(h->a2, h->dz, M, H2, NP, h->part, g + h->off[4], s);
+    if (e == hipSuccess) e = launch_colsum(h->dz, M, NP, h->part, g + h->off[5], s);
+    if (e == hipSuccess) e = launch_conv1x1_dgrad(h->dz, w + h->off[4], nullptr, M, H2, NP, h->d2, s);
+    if (e == hipSuccess) e = launch_relu_mask(h->d2, h->a2, (long long)M * H2, s);
+    // fc2: dW2 = a1^T d2, db2 = sum d2, d1 = (d2 W2^T) [a1 > 0]
+    if (e == hipSuccess) e = launch_conv1x1_wgrad(h->a1, h->d2, M, H1, H2, h->part, g + h->off[2], s);
+    if (e == hipSuccess) e = launch_colsum(h->d2, M, H2, h->part, g + h->off[3], s);
+    if (e == hipSuccess) e = launch_conv1x1_dgrad(h->d2, w + h->off[2], nullptr, M, H1, H2, h->d1, s);
+    if (e == hipSuccess) e = launch_relu_mask(h->d1, h->a1, (long long)M * H1, s);
+    // fc1: dW1 = pooled^T d1, db1 = sum d1, grad_pooled = d1 W1^T when asked for
+    if (e == hipSuccess) e = launch_conv1x1_wgrad(d_pooled, h->d1, M, K1, H1, h->part, g + h->off[0], s);
+    if (e == hipSuccess) e = launch_colsum(h->d1, M, H1, h->part, g + h->off[1], s);
+    if (e == hipSuccess && d_grad_pooled) e = launch_conv1x1_dgrad(h->d1, w + h->off[0], nullptr, M, K1, H1, d_grad_pooled, s);
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_adam_step(rpn_det_head *h, float lr, float beta_1, float beta_2, float epsilon, void *stream)
+{
+    const char *who = "rpn_det_head_adam_step";
+    RPN_REQUIRE(h, "%s: null head", who);
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
+    RPN_REQUIRE(beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f && epsilon > 0.0f, "%s: beta_1 = %g, beta_2 = %g, epsilon = %g",
+                who, (double)beta_1, (double)beta_2, (double)epsilon);
+    RPN_REQUIRE(h->loaded == 15u, "%s: set_layer has not been called for every layer (fc1, fc2, cls, reg)", who);
+    const int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    h->kept_rows = 0;            // a kept forward was made with the weights this step changes
+    const hipError_t e = launch_adam(h->w, h->g, h->m, h->v, (long long)h->n, h->t + 1, lr, beta_1, beta_2, epsilon, as_stream(stream));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    h->t += 1;
+    return RPN_OK;
+}
+
+extern "C" int rpn_fc_forward(const float *d_a, const float *d_w, const float *d_bias, int M, int K, int N, int ldw, int relu,
+                              float *d_out, void *stream)
+{
+    const char *who = "rpn_fc_forward";
+    RPN_REQUIRE(d_a && d_w && d_out, "%s: null pointer", who);
+    RPN_REQUIRE(M >= 1 && M <= kFcMaxRows && N >= 1, "%s: M = %d (1 .. %lld), N = %d", who, M, kFcMaxRows, N);
+    RPN_REQUIRE(K >= 4 && K % 4 == 0, "%s: K = %d must be a positive multiple of 4", who, K);
+    RPN_REQUIRE(ldw >= N && ldw % 4 == 0, "%s: ldw = %d must be a multiple of 4 and >= N = %d", who, ldw, N);
+    RPN_REQUIRE(relu == 0 || relu == 1, "%s: relu must be 0 or 1", who);
+    RPN_REQUIRE(aligned16(d_a) && aligned16(d_w), "%s: a and w must be 16-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_fc_forward(d_a, d_w, d_bias, M, K, N, ldw, relu, N, d_out, nullptr, as_stream(stream));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}

@@ -1,0 +1,1 @@
+from .detection_head import DetectionHead  # noqa: F401

@@ -1,0 +1,217 @@
+"""The detection head of a Faster R-CNN second stage on MI355X: two fully-connected ReLU layers on the RoI features and the
+cls | reg output pair, trained on the device (``rpn_det_head_*``; contract in ``include/rpn_hip.h``).
+
+This module has NO counterpart in the reference, which stops at the proposals.  The architecture is this project's choice (the
+Fast R-CNN head), as the thresholds of ``calculate_roi_targets`` are:
+
+    pooled (B,R,ph,pw,Cf) --Flatten (NHWC: index (i*pw + j)*Cf + c)--> x (B*R, ph*pw*Cf)
+    fc1: h1 = relu(x  W1 + b1)     fc2: h2 = relu(h1 W2 + b2)
+    cls: logits = h2 Wc + bc  -> (B,R,C)  LOGITS         reg: deltas = h2 Wr + br  -> (B,R,4C)  class-specific
+
+Kernels are Keras ``Dense`` kernels, (in, out).  There is no dropout: every training entry point of this library gives the same
+bits on every run, and so does this one.  Exact float32; a RoI's outputs do not depend on the batch it is part of.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+from ..utils import roi_utils
+
+LAYERS = ("fc1", "fc2", "cls", "reg")
+
+
+class _HeadFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pooled, token, head):
+        # token: the head's stand-in for its parameters in the torch graph (they live inside the object, not in torch), so that a
+        # trainable head's outputs require grad even when `pooled` does not
+        ctx.head = head
+        ctx.save_for_backward(pooled)
+        out = head._forward(pooled, keep=True)
+        ctx.serial = head._serial                # the head keeps ONE forward's activations: this one's, until its next call
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_logits, grad_deltas):
+        pooled, = ctx.saved_tensors
+        head = ctx.head
+        if ctx.serial != head._serial:
+            raise ValueError("DetectionHead backward: the head has been called, given weights or stepped since this forward (call %d, now "
+                             "%d); it keeps the activations of its most recent call only" % (ctx.serial, head._serial))
+        B, R = int(pooled.shape[0]), int(pooled.shape[1])
+        zeros = lambda n: torch.zeros((B, R, n), dtype=torch.float32, device="cuda")
+        gl = grad_logits.contiguous() if grad_logits is not None else zeros(head.total_labels)
+        gd = grad_deltas.contiguous() if grad_deltas is not None else zeros(4 * head.total_labels)
+        want = ctx.needs_input_grad[0]
+        gp = torch.empty_like(pooled) if want else None
+        st = L.lib().rpn_det_head_backward(head._h, L.ptr(pooled), B * R, L.ptr(gl), L.ptr(gd), L.ptr(gp), L.stream_ptr())
+        L.check(st, "DetectionHead backward")
+        return gp, None, None
+
+
+class DetectionHead(object):
+    """``head(pooled) -> (cls_logits (B,R,C), reg_pred (B,R,4C))`` on torch CUDA tensors; ``pooled`` (B,R,ph,pw,Cf) is what
+    ``roi_utils.roi_pooling`` returns, B*R <= ``max_rois``.
+
+    With grad mode on, a call on a trainable head -- or on a ``pooled`` that requires grad -- is a ``torch.autograd.Function``:
+    its backward runs ``rpn_det_head_backward``, leaves the eight parameter gradients inside the object (``get_gradients()``;
+    ``apply_gradients()`` is one Adam launch over all of them) and returns the gradient with respect to ``pooled``, which flows
+    on through ``roi_pooling`` into the feature map.  The head keeps the activations of ONE forward, so a backward must belong
+    to the head's most recent call: after any other call of the head (kept or not: a second batch, a ``detect``), a
+    ``set_weights`` or an ``apply_gradients`` the backward of an earlier call raises ``ValueError`` instead of computing from
+    another call's activations.  Each backward REPLACES the stored parameter gradients; they do not accumulate over calls, so
+    it is one forward, one backward, one ``apply_gradients``.  Under ``torch.no_grad()`` nothing is kept.  ``trainable=False`` is the inference head: weights and the two hidden activations only.
+
+    Initial weights are Keras' ``Dense`` defaults, Glorot-uniform kernels and zero biases, drawn from ``seed``."""
+
+    def __init__(self, total_labels, pooling_size=(7, 7), channels=512, hidden=(4096, 4096), max_rois=8 * 300, trainable=True,
+                 seed=0):
+        self.total_labels = int(total_labels)
+        self.pooling_size = tuple(int(v) for v in pooling_size)
+        self.channels, self.hidden = int(channels), tuple(int(v) for v in hidden)
+        self.max_rois, self.trainable = int(max_rois), bool(trainable)
+        if len(self.pooling_size) != 2 or len(self.hidden) != 2:
+            raise ValueError("pooling_size and hidden must have two entries each, got %r and %r" % (pooling_size, hidden))
+        ph, pw = self.pooling_size
+        h = L.vp(0)
+        L.check(L.lib().rpn_det_head_create(ph, pw, self.channels, self.hidden[0], self.hidden[1], self.total_labels, self.max_rois,
+                                            int(self.trainable), ctypes.byref(h)), "rpn_det_head_create")
+        self._h = h
+        self.features = ph * pw * self.channels
+        C = self.total_labels
+        self.shapes = {"fc1": (self.features, self.hidden[0]), "fc2": self.hidden, "cls": (self.hidden[1], C),
+                       "reg": (self.hidden[1], 4 * C)}
+        self._opt = None
+        self._token = None
+        self._serial = 0                         # counts what invalidates a kept forward: calls, set_weights, apply_gradients
+        self.compile()
+        if torch.cuda.is_available():          # (without a device the object still answers shape and memory questions)
+            self.set_weights(self.initial_weights(seed))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                L.lib().rpn_det_head_destroy(h)
+            except Exception:
+                pass
+
+    # ---- weights ------------------------------------------------------------------------
+    def initial_weights(self, seed=0):
+        """Keras ``Dense`` defaults: kernel ~ U(-l, l), l = sqrt(6 / (fan_in + fan_out)); bias 0."""
+        rng = np.random.RandomState(seed)
+        out = {}
+        for name in LAYERS:
+            fan_in, fan_out = self.shapes[name]
+            limit = np.sqrt(6.0 / (fan_in + fan_out))
+            out[name] = {"kernel": rng.uniform(-limit, limit, size=(fan_in, fan_out)).astype(np.float32),
+                         "bias": np.zeros((fan_out,), np.float32)}
+        return out
+
+    def memory_bytes(self):
+        """(weights -- with gradients and Adam's moments when trainable --, workspace) bytes of device memory the head holds"""
+        w, ws = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        L.check(L.lib().rpn_det_head_memory_bytes(self._h, ctypes.byref(w), ctypes.byref(ws)), "rpn_det_head_memory_bytes")
+        return int(w.value), int(ws.value)
+
+    def set_weights(self, weights, partial=False):
+        """weights: {layer: {"kernel": (in, out), "bias": (out,)}}, layers "fc1", "fc2", "cls", "reg".  ``partial``: layers absent
+        from ``weights`` are left as they are.  Returns the names of the layers set."""
+        done = []
+        for name in LAYERS:
+            if name not in weights:
+                if partial:
+                    continue
+                raise KeyError("weights for layer %r are missing" % name)
+            kernel = np.ascontiguousarray(weights[name]["kernel"], dtype=np.float32)
+            bias = np.ascontiguousarray(weights[name]["bias"], dtype=np.float32)
+            if tuple(kernel.shape) != tuple(self.shapes[name]) or tuple(bias.shape) != (self.shapes[name][1],):
+                raise ValueError("layer %r: kernel %s / bias %s, expected %s / (%d,)" % (name, kernel.shape, bias.shape,
+                                                                                         tuple(self.shapes[name]), self.shapes[name][1]))
+            self._serial += 1
+            L.check(L.lib().rpn_det_head_set_layer(self._h, name.encode(), kernel.ctypes.data_as(L.c_float_p),
+                                                   bias.ctypes.data_as(L.c_float_p)), "rpn_det_head_set_layer(%s)" % name)
+            done.append(name)
+        return done
+
+    def _get(self, fn, what):
+        out = {}
+        for name in LAYERS:
+            kernel = np.empty(self.shapes[name], dtype=np.float32)
+            bias = np.empty((self.shapes[name][1],), dtype=np.float32)
+            L.check(fn(self._h, name.encode(), kernel.ctypes.data_as(L.c_float_p), bias.ctypes.data_as(L.c_float_p), L.stream_ptr()),
+                    "%s(%s)" % (what, name))
+            out[name] = {"kernel": kernel, "bias": bias}
+        return out
+
+    def get_weights(self):
+        """{layer: {"kernel", "bias"}} as numpy arrays (synchronises the current stream)"""
+        return self._get(L.lib().rpn_det_head_get_layer, "rpn_det_head_get_layer")
+
+    def get_gradients(self):
+        """{layer: {"kernel", "bias"}}: the parameter gradients the last backward left in the head"""
+        return self._get(L.lib().rpn_det_head_get_gradient, "rpn_det_head_get_gradient")
+
+    def save_weights(self, path):
+        """a flat ``.npz`` with keys ``<layer>/<param>``, the form ``RPNModel.save_weights`` writes"""
+        np.savez(path, **{"%s/%s" % (layer, p): v for layer, d in self.get_weights().items() for p, v in d.items()})
+
+    def load_weights(self, path, by_name=True):
+        data = np.load(path)
+        weights = {}
+        for key in data.files:
+            layer, param = key.rsplit("/", 1)
+            if layer in LAYERS:
+                weights.setdefault(layer, {})[param] = data[key]
+        return self.set_weights(weights, partial=bool(by_name))
+
+    # ---- forward / backward -------------------------------------------------------------
+    def _forward(self, pooled, keep):
+        B, R = int(pooled.shape[0]), int(pooled.shape[1])
+        C = self.total_labels
+        logits = torch.empty((B, R, C), dtype=torch.float32, device="cuda")
+        deltas = torch.empty((B, R, 4 * C), dtype=torch.float32, device="cuda")
+        self._serial += 1
+        st = L.lib().rpn_det_head_forward(self._h, L.ptr(pooled), B * R, int(keep), L.ptr(logits), L.ptr(deltas), L.stream_ptr())
+        L.check(st, "DetectionHead forward")
+        return logits, deltas
+
+    def __call__(self, pooled):
+        if not isinstance(pooled, torch.Tensor):
+            raise TypeError("pooled must be a torch tensor (B, R, ph, pw, C)")
+        expect = self.pooling_size + (self.channels,)
+        if pooled.dim() != 5 or tuple(int(v) for v in pooled.shape[2:]) != expect:
+            raise ValueError("pooled must be (B, R, %d, %d, %d), got %s" % (expect + (tuple(pooled.shape),)))
+        if int(pooled.shape[0]) * int(pooled.shape[1]) > self.max_rois:
+            raise ValueError("%d x %d RoIs, the head was made for at most %d" % (int(pooled.shape[0]), int(pooled.shape[1]), self.max_rois))
+        grad = torch.is_grad_enabled() and (self.trainable or pooled.requires_grad)
+        if grad and not self.trainable:
+            raise RuntimeError("a gradient through DetectionHead needs trainable=True (the inference head keeps no activations)")
+        x = L.to_device(pooled)[0]
+        if grad:
+            if self._token is None:
+                self._token = torch.zeros((), dtype=torch.float32, device="cuda", requires_grad=True)
+            return _HeadFunction.apply(x, self._token, self)
+        return self._forward(x.detach(), keep=False)
+
+    # ---- optimiser ----------------------------------------------------------------------
+    def compile(self, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+        """Adam's parameters (Keras' defaults but for the learning rate); the moments live in the head from its creation."""
+        self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
+
+    def apply_gradients(self):
+        """one Adam step (one launch) from the gradients the last backward left"""
+        self._serial += 1
+        L.check(L.lib().rpn_det_head_adam_step(self._h, *(self._opt + (L.stream_ptr(),))), "rpn_det_head_adam_step")
+
+    def train_steps(self):
+        return int(L.lib().rpn_det_head_steps(self._h))
+
+    # ---- inference ----------------------------------------------------------------------
+    def detect(self, rois, pooled, variances, valid=None, **nms_kwargs):
+        """``head(pooled)`` then ``roi_utils.roi_detections``: (boxes (B,M,4), scores (B,M), classes (B,M), valid_detections (B,))"""
+        with torch.no_grad():
+            logits, deltas = self(pooled)
+        return roi_utils.roi_detections(rois, deltas, logits, variances, valid=valid, **nms_kwargs)

@@ -212,6 +212,14 @@ class Proposer(object):
         pooled = self.feature_extractor.roi_pool(ob, (ph, pw), valid=ov, out=bufs[(ph, pw)][:B])
         return ob, osc, ov, pooled
 
+    def detect(self, imgs, head, **nms_kwargs):
+        """imgs -> (boxes (B,M,4) clipped to [0, 1], scores (B,M), classes (B,M), valid_detections (B,) int32), M =
+        ``max_total_size`` (300 unless given): ``propose_features`` at the head's pooling size, then ``head.detect`` (a
+        ``models.DetectionHead``: its layers, ``roi_utils.roi_detections``) with this model's variances.  Everything on the current
+        stream, no host synchronisation in between.  ``nms_kwargs`` go to ``roi_detections``."""
+        rois, _scores, valid, pooled = self.propose_features(imgs, pooling_size=head.pooling_size)
+        return head.detect(rois, pooled, self.hyper_params["variances"], valid=valid, **nms_kwargs)
+
     def propose_async(self, imgs):
         """Pipelined form (needs ``overlap_nms=True``): enqueues the conv stack on the current stream and decode+NMS
         on the side stream and returns the output tensors WITHOUT ordering the current stream behind the NMS, so that
