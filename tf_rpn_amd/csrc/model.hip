@@ -25,6 +25,24 @@ constexpr float kBnEps = 1e-3f;
 
 enum OpKind { OP_CONV = 0, OP_DWCONV = 1, OP_POOL = 2, OP_HEAD = 3, OP_TOSPLIT = 4, OP_IRBLOCK = 5, OP_VGGB1 = 6 };
 
+// One value per combination of launcher and weight format that a forward can reach.  decide_routes picks it, once, when the graph
+// is complete; the arena and weight plans, rpn_model_set_layer, the forward and rpn_model_op_info only switch on it.
+enum Route {
+    RT_NONE = 0,
+    RT_TOSPLIT,                        // float32 NHWC -> SPLIT16 copy
+    RT_CIN3, RT_CIN3_MFMA,             // first layer (Cin = 3, 3x3): [27][Cout] floats / one-MFMA-step split records
+    RT_SPLIT, RT_SPLIT16,              // x3-split conv on the 32x32x16 / 16x16x32 MFMA ("split" / "split32" records)
+    RT_WINO,                           // float32 Winograd (transformed weights)
+    RT_PW_X3,                          // f16x3 pointwise conv + ReLU6 writing SPLIT16 (fragment-major hi / lo float16 image)
+    RT_F32,                            // float32 implicit GEMM (packed_shape matrix)
+    RT_HEAD_SPLITK, RT_HEAD_F32,       // fused rpn_reg | rpn_cls: split-K head kernel / implicit GEMM (Op::head_frag: + fragment-ordered copy)
+    RT_VGGB1,                          // VGG16 block 1 in one launch
+    RT_IR, RT_IR_X3, RT_IR_HRX3,       // fused MobileNetV2 block: float32 / f16x3 / f16x3 high-resolution form
+    RT_DW,                             // depthwise 3x3
+    RT_POOL_F32, RT_POOL_SPLIT,        // 2 x 2 max-pool
+    RT_FUSED                           // runs inside the previous op (a pool in a conv's epilogue): launches nothing
+};
+
 struct Tensor {
     std::string name;
     int H = 0, W = 0, C = 0;
@@ -55,14 +73,14 @@ struct Op {
     PackedShape ps{};
     size_t w_off = 0, b_off = 0;       // floats into the weight blob
     std::vector<int> params;
-    bool cin3 = false;                 // first layer (Cin = 3, 3x3): direct vector-ALU kernel ...
-    bool cin3_mfma = false;            // ... or, in the split-precision modes, the one-step MFMA kernel
-    bool split = false;                // runs on the x3-split 16-bit MFMA kernel (SPLIT16 input)
-    bool k16 = false;                  // split conv on the 16x16x32-MFMA kernel ("split32" weight packing)
+    Route route = RT_NONE;             // the launcher and weight format of this op (decide_routes)
+    bool pools_next = false;           // this conv also does the next op's 2 x 2 max-pool, in its epilogue (that op: RT_FUSED)
+    bool ktree = false;                // split conv in front of the slab-adding head: walks K as a fixed tree (conv_kernels.h) ...
+    bool ksplit = false;               // ... and may spread the tree over workgroups at small batches (its tensor has the slabs)
+    bool head_frag = false;            // the head keeps a fragment-ordered copy of its matrix (rpn_head_kernel can take this head)
     bool out_f32 = false;              // split conv writing float32 NHWC (feeds the float32 head)
     bool f32_out_split = false;        // float32 implicit-GEMM conv writing SPLIT16 directly (its consumer is a split conv)
-    bool wino = false;                 // precision F32W: 3x3 stride-1 'same' conv as float32 Winograd (conv_wino_kernels.hip)
-    int wino_f = 2;                    // ... F(2x2, 3x3) or F(4x4, 3x3): wino_variant at the handle's max_batch
+    int wino_f = 2;                    // RT_WINO: F(2x2, 3x3) or F(4x4, 3x3): wino_variant at the handle's max_batch
     float out_scale = 1.0f;            // 2^-shift of the pre-scaled split weights
     // OP_IRBLOCK (one fused MobileNetV2 block; Cin / Cout = block input / output channels, stride = the depthwise's):
     int cexp = 0;                      // expanded channels
@@ -70,10 +88,8 @@ struct Op {
     bool ir_res = false;               // + block input
     int ir_pad = 0;                    // top/left padding of the depthwise (stem: of Conv1)
     size_t ir_off[6] = {0, 0, 0, 0, 0, 0};   // we, be, wd, bd, wp, bp (floats into the weight blob)
-    bool ir_x3 = false;                // F16X3 only: the block's two GEMMs on the 16-bit MFMA (hi + lo float16 operands)
-    bool ir_hrx3 = false;              // ... the high-resolution form (blocks 1-3: ir_block_hrx3_kernel; implies ir_x3)
-    float ir_scale[2] = {1.0f, 1.0f};  // ... 2^-shift of the pre-scaled expand / projection weights
-    int ir_ce = 0;                     // ... chunk size chosen for this handle (ir_hrx3_chunk_for; 0: the kernel family's default)
+    float ir_scale[2] = {1.0f, 1.0f};  // RT_IR_X3 / RT_IR_HRX3: 2^-shift of the pre-scaled expand / projection weights
+    int ir_ce = 0;                     // RT_IR_HRX3: chunk size chosen for this handle (ir_hrx3_chunk_for; 0: the kernel family's default)
     // OP_VGGB1 (VGG16 block 1 in one launch) reuses ir_off[0..3] = w1, b1, w2, b2 and ir_scale[0..1] = the two 2^-shift
 };
 
@@ -135,11 +151,11 @@ static bool use_mfma16(int Cin, int Cout, int H, int W, int B)
     return Cin >= 128;
 }
 
-// RPN_HEAD_SPLITK=0: the head through the generic float32 implicit GEMM (one 128 x 32 tile walking K in 32 steps)
-static bool head_splitk()
+// The first-layer kernels (Cin = 3, 3x3, stride 1 or 2): shared by decide_routes and the single-layer entry rpn_conv2d
+static bool cin3_eligible(int Cin, int R, int S, int stride, int Cout, int act)
 {
-    static const int on = RPN_KNOB("RPN_HEAD_SPLITK", 1);
-    return on != 0;
+    return Cin == 3 && R == 3 && S == 3 && (stride == 1 || stride == 2) && Cout % 16 == 0 && Cout <= 256 && 256 % (Cout / 16) == 0 &&
+           act != ACT_SIGMOID;
 }
 
 static int add_tensor(rpn_model *m, const std::string &name, int H, int W, int C, bool external = false)
@@ -161,47 +177,25 @@ static int add_param(rpn_model *m, int op, const std::string &name, const std::s
     return (int)m->params.size() - 1;
 }
 
-// F16X3 only: a pointwise conv + ReLU6 whose output goes to a split conv as SPLIT16 (MobileNetV2: block_13_expand in front
-// of rpn_conv) runs on the 16-bit MFMA (pw_x3_kernel) instead of the float32 implicit GEMM.  Decided where it is used: the
-// producer only learns that its output is SPLIT16 when its consumer is added.
-static bool is_pw_x3(const rpn_model *m, const Op &op)
-{
-    static const int knob = RPN_KNOB("RPN_MN_X3", 1);      // read ONCE per process: weight packing (set_layer), kernel choice
-                                                           // (forward) and op_info must agree whatever happens to the environment
-    return op.kind == OP_CONV && op.f32_out_split && m->f16 && op.R == 1 && op.S == 1 && op.stride == 1 && op.act == ACT_RELU6 &&
-           op.residual < 0 && !op.ps.generic && pw_x3_supported(op.Cin, op.Cout) && op.ps.floats() == (size_t)op.Cin * op.Cout &&
-           knob != 0;
-}
-
-// Float32 graph: a float32 implicit-GEMM conv directly followed by its 2 x 2 max-pool (VGG16 block*_pool) runs as ONE kernel,
-// the pool inside the conv's epilogue (ConvArgs::pool; same bits as the separate pool kernel), unless every activation must be
-// kept.  True for op i = the conv; op i + 1 is then the pool that does not launch.
-static bool f32_pool_fused(const rpn_model *m, size_t i)
-{
-    if (m->keep_all || i + 1 >= m->ops.size()) return false;
-    const Op &op = m->ops[i], &nx = m->ops[i + 1];
-    // the un-pooled tensor is never written when fused: the pool must be its ONLY reader (no residual, tap or returned feature map)
-    if (op.out == m->feat_tensor) return false;
-    for (size_t j = 0; j < m->ops.size(); ++j)
-        if (j != i + 1 && (m->ops[j].in == op.out || m->ops[j].residual == op.out)) return false;
-    return op.kind == OP_CONV && !op.split && !op.cin3 && !op.f32_out_split && op.residual < 0 && op.act != ACT_SIGMOID &&
-           nx.kind == OP_POOL && !nx.split && nx.in == op.out && (RPN_LAB_KNOB("RPN_F32_POOLFUSE", 1) != 0);
-}
-
-// dense conv op; returns the output tensor id
+// dense conv op; returns the output tensor id.  The builders fix the graph and the FORMAT of every tensor (a conv reads SPLIT16
+// exactly when it will run on a split kernel); which kernel runs each op is decide_routes' business.
+// first_out_split: the first layer (block1_conv1, on its Cin = 3 kernels) writes SPLIT16 for the split conv behind it.
 static int add_conv(rpn_model *m, const std::string &name, const std::string &bn, int in, int Cout, int R,
                     int stride, int pad_t, int pad_l, int OH, int OW, int act, int residual = -1,
-                    bool force_f32_out = false, bool cin3_out_split = false)
+                    bool force_f32_out = false, bool first_out_split = false)
 {
     const bool split = m->use_split && R == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && residual < 0 &&
                        act != ACT_SIGMOID &&
                        m->tensors[in].C % 16 == 0 && Cout % 16 == 0 && !m->tensors[in].external;
-    if (split && !m->tensors[in].split_fmt && !m->keep_all && !m->ops.empty() && m->ops.back().out == in &&
-        m->ops.back().kind == OP_CONV && !m->ops.back().split && !m->ops.back().cin3 && m->ops.back().residual < 0 &&
-        m->ops.back().Cout % 32 == 0 && m->ops.back().act != ACT_SIGMOID) {
-        // the float32 producer (MobileNetV2: block_13_expand) writes SPLIT16 from its own epilogue: no conversion pass
-        m->ops.back().f32_out_split = true;
-        m->tensors[in].split_fmt = true;
+    if (split && !m->tensors[in].split_fmt && !m->keep_all && !m->ops.empty() && m->ops.back().out == in) {
+        // the float32 producer (MobileNetV2: block_13_expand) writes SPLIT16 from its own epilogue: no conversion pass.  (Not the
+        // first layer: its kernels take their output format from first_out_split.)
+        Op &pr = m->ops.back();
+        if (pr.kind == OP_CONV && !m->tensors[pr.in].split_fmt && !m->tensors[pr.in].external && pr.residual < 0 && pr.Cout % 32 == 0 &&
+            pr.act != ACT_SIGMOID) {
+            pr.f32_out_split = true;
+            m->tensors[in].split_fmt = true;
+        }
     }
     if (split && !m->tensors[in].split_fmt) {          // float32 producer -> SPLIT16 copy for the split kernel
         const Tensor tsrc = m->tensors[in];
@@ -215,28 +209,13 @@ static int add_conv(rpn_model *m, const std::string &name, const std::string &bn
     }
     const Tensor ti = m->tensors[in];
     Op op;
-    op.split = split;
-    op.cin3 = ti.C == 3 && R == 3 && (stride == 1 || stride == 2) && Cout % 16 == 0 && Cout <= 256 &&
-              256 % (Cout / 16) == 0 && residual < 0 && act != ACT_SIGMOID;
-    // f16x3 only: with bfloat16 halves the first layer's 2^-16 product error, carried through 40 MobileNetV2 layers,
-    // measured 1.25e-4 on the objectness (bound 1e-4); with float16 halves it is indistinguishable from exact f32
-    op.cin3_mfma = op.cin3 && m->use_split && m->f16 && (Cout == 32 || Cout == 64) &&
-                   (RPN_LAB_KNOB("RPN_CIN3_MFMA", 1) != 0);
     op.out_f32 = split && force_f32_out;
-    op.wino = m->wino && R == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && OH == ti.H && OW == ti.W && residual < 0 &&
-              act != ACT_SIGMOID && !op.cin3 && !ti.external && wino_supported(ti.C, Cout);
-    if (op.wino) {
-        op.wino_f = wino_variant(m->max_batch, ti.H, ti.W, ti.C, Cout);
-        // a layer the Winograd launcher would refuse (32-bit buffer offsets, ticket block) stays on the direct float32 kernel
-        op.wino = wino_launchable(m->max_batch, ti.H, ti.W, ti.C, Cout, op.wino_f);
-    }
     op.kind = OP_CONV; op.name = name; op.in = in; op.residual = residual;
     op.Cin = ti.C; op.Cout = Cout; op.R = R; op.S = R; op.stride = stride; op.pad_t = pad_t; op.pad_l = pad_l;
     op.H = ti.H; op.W = ti.W; op.OH = OH; op.OW = OW; op.act = act;
     op.ps = packed_shape(R, R, ti.C, Cout);
-    op.k16 = split && use_mfma16(ti.C, Cout, ti.H, ti.W, m->max_batch);
     op.out = add_tensor(m, name, OH, OW, Cout);
-    m->tensors[op.out].split_fmt = (split && !force_f32_out) || (op.cin3 && cin3_out_split);
+    m->tensors[op.out].split_fmt = (split && !force_f32_out) || (ti.external && first_out_split);
     m->ops.push_back(op);
     const int oi = (int)m->ops.size() - 1;
     add_param(m, oi, name, bn, bn.empty() ? 0 : 1, R, R, ti.C, Cout);
@@ -267,7 +246,6 @@ static int add_pool(rpn_model *m, const std::string &name, int in)
     op.kind = OP_POOL; op.name = name; op.in = in;
     op.Cin = op.Cout = ti.C; op.H = ti.H; op.W = ti.W; op.OH = ti.H / 2; op.OW = ti.W / 2;   // 'valid' floors
     op.out = add_tensor(m, name, op.OH, op.OW, ti.C);
-    op.split = ti.split_fmt;
     m->tensors[op.out].split_fmt = ti.split_fmt;
     m->ops.push_back(op);
     return op.out;
@@ -278,18 +256,6 @@ static void add_head(rpn_model *m, int feat)
 {
     const Tensor tf = m->tensors[feat];
     const int x = add_conv(m, "rpn_conv", "", feat, 512, 3, 1, 1, 1, tf.H, tf.W, ACT_RELU, -1, true);
-    {   // split-K of rpn_conv at small batches (its partial-sum slabs are added by the head): room for the largest S * B
-        const Op &cv = m->ops.back();
-        if (cv.split && cv.k16 && cv.out_f32 && !m->keep_all && rpn_head_supported(512, 5 * m->K) && head_splitk() &&
-            conv3x3_split16_ktree_ok(m->max_batch, cv.H, cv.W, cv.Cin, cv.Cout, split_cout_pad(cv.Cout))) {
-            int cap = m->max_batch;
-            for (int b = 1; b <= m->max_batch; ++b) {
-                const int sk = conv3x3_split16_ksplit(b, cv.H, cv.W, cv.Cin, cv.Cout, split_cout_pad(cv.Cout));
-                if (sk * b > cap) cap = sk * b;
-            }
-            m->tensors[x].slabs = (cap + m->max_batch - 1) / m->max_batch;
-        }
-    }
     Op op;
     op.kind = OP_HEAD; op.name = "rpn_head"; op.in = x;
     op.Cin = 512; op.Cout = 5 * m->K; op.R = op.S = 1; op.stride = 1;
@@ -359,15 +325,6 @@ static int add_irblock(rpn_model *m, const std::string &name, int in, int cexp, 
     op.Cin = ti.C; op.Cout = cout; op.cexp = cexp; op.stride = stride; op.ir_pad = pad; op.ir_res = res; op.ir_stem = stem;
     op.R = op.S = 3;
     op.H = ti.H; op.W = ti.W; op.OH = OH; op.OW = OW; op.act = ACT_LINEAR;
-    op.ir_x3 = m->f16 && !stem && ir_block_x3_supported(ti.C, cexp, cout, stride, res) &&
-               (RPN_KNOB("RPN_MN_X3", 1) != 0);
-    op.ir_hrx3 = m->f16 && !stem && ir_block_hrx3_supported(ti.C, cexp, cout, stride, res) &&
-                 ir_block_hrx3_preferred(ti.C, stride, (long long)((OW + 7) / 8) * ((OH + 3) / 4) * m->max_batch) &&
-                 (RPN_KNOB("RPN_MN_X3", 1) != 0) && (RPN_LAB_KNOB("RPN_MN_HRX3", 1) != 0);
-    if (op.ir_hrx3) {
-        op.ir_x3 = true;
-        op.ir_ce = ir_hrx3_chunk_for(ti.C, stride, (long long)((OW + 7) / 8) * ((OH + 3) / 4) * m->max_batch);
-    }
     op.out = add_tensor(m, name, OH, OW, cout);
     m->ops.push_back(op);
     const int oi = (int)m->ops.size() - 1;
@@ -466,6 +423,95 @@ static void build_mobilenet_v2(rpn_model *m)
     add_head(m, t);
 }
 
+// Which kernel runs each op, and in which weight format: decided HERE and nowhere else, when the graph is complete (a pointwise conv
+// learns its output format from its consumer, a fused float32 pool must be its conv's only reader) and before the arena and the
+// weights are planned; everything else switches on Op::route and reads the facts beside it.  The environment knobs are read once
+// per process: weight packing, launches and rpn_model_op_info agree whatever happens to the environment afterwards.
+static void decide_routes(rpn_model *m)
+{
+    static const int head_splitk = RPN_KNOB("RPN_HEAD_SPLITK", 1);   // 0: the head through the generic float32 implicit GEMM
+    static const int mn_x3 = RPN_KNOB("RPN_MN_X3", 1);               // 0: MobileNetV2 under f16x3 on the float32 MFMA
+    static const int mn_hrx3 = RPN_LAB_KNOB("RPN_MN_HRX3", 1);
+    static const int cin3_mfma = RPN_LAB_KNOB("RPN_CIN3_MFMA", 1);
+    static const int f32_poolfuse = RPN_LAB_KNOB("RPN_F32_POOLFUSE", 1);
+    const size_t n = m->ops.size();
+    auto split_in = [&](const Op &o) { return m->tensors[o.in].split_fmt; };
+    for (size_t i = 0; i < n; ++i) {
+        Op &op = m->ops[i];
+        Op *nx = i + 1 < n ? &m->ops[i + 1] : nullptr;
+        const bool pool_next = nx && nx->kind == OP_POOL && nx->in == op.out;
+        switch (op.kind) {
+        case OP_TOSPLIT: op.route = RT_TOSPLIT; break;
+        case OP_DWCONV: op.route = RT_DW; break;
+        case OP_VGGB1: op.route = RT_VGGB1; break;
+        case OP_POOL: op.route = i > 0 && m->ops[i - 1].pools_next ? RT_FUSED : (split_in(op) ? RT_POOL_SPLIT : RT_POOL_F32); break;
+        case OP_HEAD:
+            op.head_frag = rpn_head_supported(op.Cin, op.Cout);
+            op.route = op.head_frag && head_splitk != 0 ? RT_HEAD_SPLITK : RT_HEAD_F32;
+            break;
+        case OP_IRBLOCK: {
+            // F16X3 only: the block's two GEMMs on the 16-bit MFMA (hi + lo float16 operands); blocks 1-3 in the high-resolution form
+            const long long tiles = (long long)((op.OW + 7) / 8) * ((op.OH + 3) / 4) * m->max_batch;
+            const bool x3 = m->f16 && !op.ir_stem && mn_x3 != 0;
+            const bool hr = x3 && mn_hrx3 != 0 && ir_block_hrx3_supported(op.Cin, op.cexp, op.Cout, op.stride, op.ir_res) &&
+                            ir_block_hrx3_preferred(op.Cin, op.stride, tiles);
+            op.route = hr ? RT_IR_HRX3 : (x3 && ir_block_x3_supported(op.Cin, op.cexp, op.Cout, op.stride, op.ir_res) ? RT_IR_X3 : RT_IR);
+            if (hr) op.ir_ce = ir_hrx3_chunk_for(op.Cin, op.stride, tiles);
+            break;
+        }
+        case OP_CONV: {
+            const bool plain = op.residual < 0 && op.act != ACT_SIGMOID;
+            if (cin3_eligible(op.Cin, op.R, op.S, op.stride, op.Cout, op.act) && op.residual < 0) {
+                // f16x3 only: with bfloat16 halves the first layer's 2^-16 product error, carried through 40 MobileNetV2 layers,
+                // measured 1.25e-4 on the objectness (bound 1e-4); with float16 halves it is indistinguishable from exact f32
+                op.route = m->use_split && m->f16 && (op.Cout == 32 || op.Cout == 64) && cin3_mfma != 0 ? RT_CIN3_MFMA : RT_CIN3;
+            } else if (split_in(op)) {
+                op.route = use_mfma16(op.Cin, op.Cout, op.H, op.W, m->max_batch) ? RT_SPLIT16 : RT_SPLIT;
+                // directly followed by its 2 x 2 max-pool: ONE kernel, the pool in the epilogue (the un-pooled activation never
+                // reaches HBM), unless every activation must be kept
+                op.pools_next = !op.out_f32 && !m->keep_all && pool_next;
+                // rpn_conv in front of the slab-adding head: a K TREE at every batch size of this model, or at none; at small
+                // batches split over workgroups, raw partial sums into slabs that the head adds: room for the largest S * B
+                const int cpad = split_cout_pad(op.Cout);
+                op.ktree = op.route == RT_SPLIT16 && op.out_f32 && nx && nx->kind == OP_HEAD && nx->in == op.out &&
+                           rpn_head_supported(nx->Cin, nx->Cout) && head_splitk != 0 &&
+                           conv3x3_split16_ktree_ok(m->max_batch, op.H, op.W, op.Cin, op.Cout, cpad);
+                op.ksplit = op.ktree && !m->keep_all;   // (every activation kept: the tree inside one workgroup's tile loop)
+                if (op.ksplit) {
+                    int cap = m->max_batch;
+                    for (int b = 1; b <= m->max_batch; ++b)
+                        cap = std::max(cap, b * conv3x3_split16_ksplit(b, op.H, op.W, op.Cin, op.Cout, cpad));
+                    m->tensors[op.out].slabs = (cap + m->max_batch - 1) / m->max_batch;
+                }
+            } else if (m->wino && op.R == 3 && op.stride == 1 && op.pad_t == 1 && op.pad_l == 1 && op.OH == op.H && op.OW == op.W &&
+                       plain && !m->tensors[op.in].external && wino_supported(op.Cin, op.Cout) &&
+                       // a layer the Winograd launcher would refuse (32-bit buffer offsets, ticket block) stays on the direct kernel
+                       wino_launchable(m->max_batch, op.H, op.W, op.Cin, op.Cout, wino_variant(m->max_batch, op.H, op.W, op.Cin, op.Cout))) {
+                op.route = RT_WINO;
+                op.wino_f = wino_variant(m->max_batch, op.H, op.W, op.Cin, op.Cout);
+            } else if (op.f32_out_split && m->f16 && op.R == 1 && op.S == 1 && op.stride == 1 && op.act == ACT_RELU6 && op.residual < 0 &&
+                       !op.ps.generic && pw_x3_supported(op.Cin, op.Cout) && op.ps.floats() == (size_t)op.Cin * op.Cout && mn_x3 != 0) {
+                // a pointwise conv + ReLU6 whose output goes to a split conv as SPLIT16 (MobileNetV2: block_13_expand in front of
+                // rpn_conv) on the 16-bit MFMA (pw_x3_kernel) instead of the float32 implicit GEMM
+                op.route = RT_PW_X3;
+            } else {
+                op.route = RT_F32;
+            }
+            if ((op.route == RT_F32 || op.route == RT_WINO) && !op.f32_out_split && plain && !m->keep_all && pool_next &&
+                !m->tensors[nx->in].split_fmt && op.out != m->feat_tensor && f32_poolfuse != 0) {
+                // float32 graph: conv + block*_pool as ONE kernel (ConvArgs::pool / a Winograd tile's 2 x 2 outputs; same bits as the
+                // separate pool kernel).  The un-pooled tensor is never written: the pool must be its ONLY reader
+                bool only = true;
+                for (size_t j = 0; j < n; ++j)
+                    if (j != i + 1 && (m->ops[j].in == op.out || m->ops[j].residual == op.out)) only = false;
+                op.pools_next = only;
+            }
+            break;
+        }
+        }
+    }
+}
+
 // liveness-based arena plan (first fit); offsets in floats per image
 static void plan_arena(rpn_model *m)
 {
@@ -476,15 +522,10 @@ static void plan_arena(rpn_model *m)
         if (op.in >= 0) m->tensors[op.in].last_use = i;
         if (op.residual >= 0) m->tensors[op.residual].last_use = i;
     }
-    // a split conv fused with its max-pool writes the POOL's output while it still reads its own input:
+    // a conv that also does the next op's max-pool writes the POOL's output while it still reads its own input:
     // the pooled tensor becomes live one op earlier
-    if (!m->keep_all)
-        for (size_t i = 0; i + 1 < m->ops.size(); ++i) {
-            const Op &op = m->ops[i], &nx = m->ops[i + 1];
-            if (op.kind == OP_CONV && op.split && !op.out_f32 && nx.kind == OP_POOL && nx.split && nx.in == op.out)
-                m->tensors[nx.out].def = (int)i;
-            if (f32_pool_fused(m, i)) m->tensors[nx.out].def = (int)i;      // (the float32 graph's fused pools likewise)
-        }
+    for (size_t i = 0; i + 1 < m->ops.size(); ++i)
+        if (m->ops[i].pools_next) m->tensors[m->ops[i + 1].out].def = (int)i;
     size_t top = 0;
     std::vector<int> placed;
     for (int ti = 0; ti < (int)m->tensors.size(); ++ti) {
@@ -520,60 +561,75 @@ static void plan_arena(rpn_model *m)
 static void plan_weights(rpn_model *m)
 {
     size_t off = 0;
+    auto take = [&](size_t floats) {                  // 256-byte granules
+        const size_t at = off;
+        off += (floats + 63) & ~(size_t)63;
+        return at;
+    };
     for (auto &op : m->ops) {
-        if (op.kind == OP_CONV && op.cin3) {
-            op.w_off = off;
-            off += ((size_t)32 * op.Cout + 63) & ~(size_t)63;        // 27 x Cout floats, or Cout x 128 B of split records
-            op.b_off = off;
-            off += ((size_t)op.Cout + 63) & ~(size_t)63;
-        } else if (op.kind == OP_CONV && op.split) {
-            op.w_off = off;
-            off += (split_weight_bytes(op.Cin, op.Cout) / sizeof(float) + 63) & ~(size_t)63;
+        switch (op.route) {
+        case RT_CIN3: case RT_CIN3_MFMA:
+            op.w_off = take((size_t)32 * op.Cout);                       // 27 x Cout floats, or Cout x 128 B of split records
+            op.b_off = take((size_t)op.Cout);
+            break;
+        case RT_SPLIT: case RT_SPLIT16:
+            op.w_off = take(split_weight_bytes(op.Cin, op.Cout) / sizeof(float));
             op.b_off = off;
             off += (size_t)split_cout_pad(op.Cout);
-        } else if (op.kind == OP_CONV && op.wino) {
-            op.w_off = off;
-            off += (wino_weight_floats(op.Cin, op.Cout, op.wino_f) + 63) & ~(size_t)63;
+            break;
+        case RT_WINO:
+            op.w_off = take(wino_weight_floats(op.Cin, op.Cout, op.wino_f));
             op.b_off = off;
             off += (size_t)op.ps.cout_pad;
-        } else if (op.kind == OP_CONV || op.kind == OP_HEAD) {
-            op.w_off = off;
-            off += (op.ps.floats() + 63) & ~(size_t)63;
+            break;
+        case RT_PW_X3: case RT_F32: case RT_HEAD_F32: case RT_HEAD_SPLITK:
+            op.w_off = take(op.ps.floats());
             op.b_off = off;
             off += (size_t)op.ps.cout_pad;
-            if (op.kind == OP_HEAD && rpn_head_supported(op.Cin, op.Cout)) {      // fragment-ordered copy for rpn_head_kernel
+            if (op.head_frag) {                                          // fragment-ordered copy for rpn_head_kernel
                 op.ir_off[0] = off;
                 off += (size_t)512 * 16 * ((op.Cout + 15) / 16);
             }
-        } else if (op.kind == OP_DWCONV) {
-            op.w_off = off;
-            off += ((size_t)9 * op.Cin + 63) & ~(size_t)63;
-            op.b_off = off;
-            off += ((size_t)op.Cin + 63) & ~(size_t)63;
-        } else if (op.kind == OP_VGGB1) {
+            break;
+        case RT_DW:
+            op.w_off = take((size_t)9 * op.Cin);
+            op.b_off = take((size_t)op.Cin);
+            break;
+        case RT_VGGB1: {
             const size_t sizes[4] = {(size_t)32 * 64, 64, split_weight_bytes(64, 64) / sizeof(float), 64};
             op.w_off = off;
-            for (int i = 0; i < 4; ++i) {
-                op.ir_off[i] = off;
-                off += (sizes[i] + 63) & ~(size_t)63;
-            }
-        } else if (op.kind == OP_IRBLOCK) {
+            for (int i = 0; i < 4; ++i) op.ir_off[i] = take(sizes[i]);
+            break;
+        }
+        case RT_IR: case RT_IR_X3: case RT_IR_HRX3: {
             const size_t kp = op.ir_stem ? 28 : (size_t)op.Cin, coutp = ((size_t)op.Cout + 15) / 16 * 16;
             size_t sizes[6] = {kp * op.cexp, (size_t)op.cexp, (size_t)9 * op.cexp, (size_t)op.cexp,
                                (size_t)op.cexp * coutp, coutp};
-            if (op.ir_hrx3) {                                             // zero-padded fragment images: larger than the matrices
+            if (op.route == RT_IR_HRX3) {                                 // zero-padded fragment images: larger than the matrices
                 sizes[0] = ir_hrx3_expand_floats(op.cexp);
                 sizes[4] = ir_hrx3_project_floats(op.Cin, op.cexp, op.Cout, op.stride, op.ir_ce);
             }
-            if (op.ir_x3) sizes[2] = ir_x3_dw_floats(op.cexp);           // depthwise taps + bias as one record per channel
+            if (op.route != RT_IR) sizes[2] = ir_x3_dw_floats(op.cexp);   // depthwise taps + bias as one record per channel
             op.w_off = off;
-            for (int i = 0; i < 6; ++i) {
-                op.ir_off[i] = off;
-                off += (sizes[i] + 63) & ~(size_t)63;
-            }
+            for (int i = 0; i < 6; ++i) op.ir_off[i] = take(sizes[i]);
+            break;
+        }
+        default: break;                                                  // no weights
         }
     }
     m->weight_floats = off;
+}
+
+// The graph of the handle's backbone, its routes, arena and weight blob: at creation and again when keep_activations changes it
+static void build_graph(rpn_model *m)
+{
+    m->tensors.clear(); m->ops.clear(); m->params.clear(); m->flops = 0.0;
+    if (m->backbone == RPN_BACKBONE_VGG16) build_vgg16(m);
+    else build_mobilenet_v2(m);
+    m->F = m->tensors[m->feat_tensor].H;
+    decide_routes(m);
+    plan_arena(m);
+    plan_weights(m);
 }
 
 static int ensure_device(rpn_model *m)
@@ -593,7 +649,7 @@ static int ensure_device(rpn_model *m)
     if (!m->d_wino_ws) {
         size_t need = 0;
         for (const Op &op : m->ops)
-            if (op.kind == OP_CONV && op.wino) need = std::max(need, wino_workspace_bytes(m->max_batch, op.H, op.W, op.Cin, op.Cout, op.wino_f));
+            if (op.route == RT_WINO) need = std::max(need, wino_workspace_bytes(m->max_batch, op.H, op.W, op.Cin, op.Cout, op.wino_f));
         if (need) {
             RPN_HIP_CHECK(hipMalloc(&m->d_wino_ws, need));
             // the tickets must read zero before the first forward, which runs on the CALLER's stream: a non-blocking stream is not
@@ -604,7 +660,7 @@ static int ensure_device(rpn_model *m)
     }
     if (!m->d_ksplit) {
         bool any = false;
-        for (const Op &op : m->ops) any = any || (op.kind == OP_IRBLOCK && op.ir_x3);
+        for (const Op &op : m->ops) any = any || op.route == RT_IR_X3 || op.route == RT_IR_HRX3;
         if (any) {
             RPN_HIP_CHECK(hipMalloc(&m->d_ksplit, ir_block_x3_scratch_floats() * sizeof(float)));
             RPN_HIP_CHECK(hipMemset(m->d_ksplit, 0, ir_block_x3_scratch_floats() * sizeof(float)));
@@ -617,6 +673,42 @@ static float *tensor_ptr(rpn_model *m, int id, const float *d_input)
 {
     if (id == 0) return const_cast<float *>(d_input);
     return m->d_arena + m->tensors[id].offset * (size_t)m->max_batch;
+}
+
+static int param_by_name(const rpn_model *m, const char *name)
+{
+    for (size_t i = 0; i < m->params.size(); ++i)
+        if (m->params[i].name == name) return (int)i;
+    return -1;
+}
+
+static int tensor_by_name(const rpn_model *m, const char *name)
+{
+    for (size_t i = 0; i < m->tensors.size(); ++i)
+        if (m->tensors[i].name == name) return (int)i;
+    return -1;
+}
+
+// BatchNorm folded into a [rows][Cout] matrix: column n times scale[n] (no BatchNorm, scale empty: a copy).  The depthwise taps
+// (3,3,C,1) are the [9][C] case.  ld >= Cout: the row stride of the result, the padding columns zero.
+static std::vector<float> fold_bn(const float *kernel, size_t rows, int Cout, const std::vector<float> &scale, size_t ld = 0)
+{
+    if (ld == 0) ld = (size_t)Cout;
+    std::vector<float> w(rows * ld, 0.0f);
+    for (size_t k = 0; k < rows; ++k)
+        for (int n = 0; n < Cout; ++n) w[k * ld + n] = scale.empty() ? kernel[k * Cout + n] : kernel[k * Cout + n] * scale[n];
+    return w;
+}
+
+static unsigned short *u16(std::vector<float> &v) { return reinterpret_cast<unsigned short *>(v.data()); }
+
+// one layer's packed weights and its nb folded biases into the weight blob
+template <typename T>
+static int upload_layer(rpn_model *m, size_t w_at, const std::vector<T> &w, size_t b_at, const std::vector<float> &shift, size_t nb)
+{
+    RPN_HIP_CHECK(hipMemcpy(m->d_weights + w_at, w.data(), w.size() * sizeof(T), hipMemcpyHostToDevice));
+    RPN_HIP_CHECK(hipMemcpy(m->d_weights + b_at, shift.data(), nb * sizeof(float), hipMemcpyHostToDevice));
+    return RPN_OK;
 }
 
 }  // namespace rpn
@@ -640,11 +732,7 @@ extern "C" int rpn_model_create(int backbone, int img_size, int anchor_count, in
     m->use_split = precision == RPN_PRECISION_BF16X3 || precision == RPN_PRECISION_F16X3;
     m->f16 = precision == RPN_PRECISION_F16X3;
     m->wino = precision == RPN_PRECISION_F32W;
-    if (backbone == RPN_BACKBONE_VGG16) build_vgg16(m);
-    else build_mobilenet_v2(m);
-    m->F = m->tensors[m->feat_tensor].H;
-    plan_arena(m);
-    plan_weights(m);
+    build_graph(m);
     *out = m;
     return RPN_OK;
 }
@@ -705,12 +793,7 @@ extern "C" int rpn_model_keep_activations(rpn_model *m, int keep)
     m->keep_all = keep != 0;
     // the graph itself depends on it (MobileNetV2 blocks are fused into one launch only when their intermediate
     // activations need not exist): rebuild
-    m->tensors.clear(); m->ops.clear(); m->params.clear(); m->flops = 0.0;
-    if (m->backbone == RPN_BACKBONE_VGG16) build_vgg16(m);
-    else build_mobilenet_v2(m);
-    m->F = m->tensors[m->feat_tensor].H;
-    plan_arena(m);
-    plan_weights(m);
+    build_graph(m);
     return RPN_OK;
 }
 
@@ -719,9 +802,7 @@ extern "C" int rpn_model_set_layer(rpn_model *m, const char *name, const float *
                                    const float *bn_var)
 {
     RPN_REQUIRE(m && name && kernel, "rpn_model_set_layer: null argument");
-    int pi = -1;
-    for (int i = 0; i < (int)m->params.size(); ++i)
-        if (m->params[i].name == name) pi = i;
+    const int pi = param_by_name(m, name);
     RPN_REQUIRE(pi >= 0, "rpn_model_set_layer: no layer named '%s'", name);
     Param &p = m->params[pi];
     Op &op = m->ops[p.op];
@@ -745,162 +826,132 @@ extern "C" int rpn_model_set_layer(rpn_model *m, const char *name, const float *
     if (bias)
         for (int n = 0; n < p.Cout; ++n) shift[n] += has_bn ? bias[n] * scale[n] : bias[n];
 
-    if (op.kind == OP_VGGB1) {
+    // Every route only packs: BatchNorm is folded BEFORE a power-of-two pre-scale is chosen (split_weight_shift of the FOLDED weights:
+    // a BatchNorm scale of 30 on top of a shift chosen for the raw kernel would push the float16 hi halves past 65504)
+    const size_t nout = (size_t)p.Cout;
+    int e = RPN_OK;
+    switch (op.route) {
+    case RT_VGGB1: {
         // parameter 0 = block1_conv1 (one-MFMA-step records), 1 = block1_conv2 (split records); no BatchNorm in VGG16
         const bool first = op.params[0] == pi;
-        const size_t count = (size_t)9 * p.Cin * p.Cout;
-        const int wshift = split_weight_shift(kernel, count, m->f16);
+        const int wshift = split_weight_shift(kernel, (size_t)9 * p.Cin * p.Cout, m->f16);
         std::vector<unsigned short> packed(first ? (size_t)64 * 64 : split_weight_bytes(64, 64) / sizeof(unsigned short));
         if (first) pack_weights_cin3_mfma_host(kernel, nullptr, 64, 64, m->f16, wshift, packed.data());
         else pack_weights_split_host(kernel, nullptr, 64, 64, 64, m->f16, wshift, packed.data());
         op.ir_scale[first ? 0 : 1] = ldexpf(1.0f, -wshift);
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.ir_off[first ? 0 : 2], packed.data(), packed.size() * sizeof(unsigned short),
-                                hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.ir_off[first ? 1 : 3], shift.data(), (size_t)64 * sizeof(float),
-                                hipMemcpyHostToDevice));
-    } else if (op.kind == OP_IRBLOCK) {
+        e = upload_layer(m, op.ir_off[first ? 0 : 2], packed, op.ir_off[first ? 1 : 3], shift, 64);
+        break;
+    }
+    case RT_IR: case RT_IR_X3: case RT_IR_HRX3: {
         // role = position among the op's parameters: 0 expand / Conv1, 1 depthwise, 2 project.  Zero padding (the stem's
         // 28th im2col row, projection columns beyond Cout) comes from the memset of the weight blob.
         int role = 0;
         while (role < 3 && op.params[(size_t)role] != pi) ++role;
-        std::vector<float> w;
-        size_t w_at, b_at, nb;
+        RPN_REQUIRE(role < 3, "rpn_model_set_layer: layer '%s' is not a parameter of its block", name);
+        std::vector<float> w, packed;
+        int sh = 0;
         if (role == 0) {                                   // (R,S,Cin,Cexp) row-major == [K][Cexp]
-            const size_t rows = op.ir_stem ? 27 : (size_t)p.Cin;
-            w.resize(rows * p.Cout);
-            for (size_t k = 0; k < rows; ++k)
-                for (int n = 0; n < p.Cout; ++n) w[k * p.Cout + n] = kernel[k * p.Cout + n] * scale[n];
-            if (op.ir_hrx3) {
-                const int sh = split_weight_shift(w.data(), w.size(), true);
-                std::vector<float> packed(ir_hrx3_expand_floats(p.Cout));
-                pack_ir_hrx3_expand(w.data(), p.Cin, p.Cout, op.stride, sh, reinterpret_cast<unsigned short *>(packed.data()), op.ir_ce);
-                w.swap(packed);
-                op.ir_scale[0] = ldexpf(1.0f, -sh);
-            } else if (op.ir_x3) {                         // hi + lo float16 fragments, same byte count
-                const int sh = split_weight_shift(w.data(), w.size(), true);
-                std::vector<float> packed(w.size());
-                pack_ir_x3_expand(w.data(), p.Cin, p.Cout, sh, reinterpret_cast<unsigned short *>(packed.data()));
-                w.swap(packed);
-                op.ir_scale[0] = ldexpf(1.0f, -sh);
+            w = fold_bn(kernel, op.ir_stem ? 27 : (size_t)p.Cin, p.Cout, scale);
+            if (op.route == RT_IR_HRX3) {
+                sh = split_weight_shift(w.data(), w.size(), true);
+                packed.resize(ir_hrx3_expand_floats(p.Cout));
+                pack_ir_hrx3_expand(w.data(), p.Cin, p.Cout, op.stride, sh, u16(packed), op.ir_ce);
+            } else if (op.route == RT_IR_X3) {             // hi + lo float16 fragments, same byte count
+                sh = split_weight_shift(w.data(), w.size(), true);
+                packed.resize(w.size());
+                pack_ir_x3_expand(w.data(), p.Cin, p.Cout, sh, u16(packed));
             }
-            w_at = op.ir_off[0]; b_at = op.ir_off[1]; nb = (size_t)p.Cout;
         } else if (role == 1) {                            // (3,3,C,1) == [9][C]
-            w.resize((size_t)9 * p.Cin);
-            for (int t = 0; t < 9; ++t)
-                for (int c = 0; c < p.Cin; ++c) w[(size_t)t * p.Cin + c] = kernel[(size_t)t * p.Cin + c] * scale[c];
-            if (op.ir_x3) {                                // [channel][9 taps, bias, 0, 0] (both f16x3 block kernels)
-                std::vector<float> packed(ir_x3_dw_floats(p.Cin));
+            w = fold_bn(kernel, 9, p.Cin, scale);
+            if (op.route != RT_IR) {                       // [channel][9 taps, bias, 0, 0] (both f16x3 block kernels)
+                packed.resize(ir_x3_dw_floats(p.Cin));
                 pack_ir_x3_dw(w.data(), shift.data(), p.Cin, packed.data());
-                w.swap(packed);
             }
-            w_at = op.ir_off[2]; b_at = op.ir_off[3]; nb = (size_t)p.Cin;
         } else {                                           // (1,1,Cexp,Cout) -> [Cexp][coutp]
-            const size_t coutp = ((size_t)p.Cout + 15) / 16 * 16;
-            w.assign((size_t)p.Cin * coutp, 0.0f);
-            for (int k = 0; k < p.Cin; ++k)
-                for (int n = 0; n < p.Cout; ++n) w[(size_t)k * coutp + n] = kernel[(size_t)k * p.Cout + n] * scale[n];
-            if (op.ir_hrx3) {
-                const int sh = split_weight_shift(w.data(), w.size(), true);
-                std::vector<float> packed(ir_hrx3_project_floats(op.Cin, p.Cin, p.Cout, op.stride, op.ir_ce));
-                pack_ir_hrx3_project(w.data(), op.Cin, p.Cin, p.Cout, op.stride, sh, reinterpret_cast<unsigned short *>(packed.data()), op.ir_ce);
-                w.swap(packed);
-                op.ir_scale[1] = ldexpf(1.0f, -sh);
-            } else if (op.ir_x3) {                         // (Cout % 16 == 0 for these blocks: coutp == Cout)
-                const int sh = split_weight_shift(w.data(), w.size(), true);
-                std::vector<float> packed(w.size());
-                pack_ir_x3_project(w.data(), p.Cin, p.Cout, sh, reinterpret_cast<unsigned short *>(packed.data()));
-                w.swap(packed);
-                op.ir_scale[1] = ldexpf(1.0f, -sh);
+            w = fold_bn(kernel, (size_t)p.Cin, p.Cout, scale, ((size_t)p.Cout + 15) / 16 * 16);
+            if (op.route == RT_IR_HRX3) {
+                sh = split_weight_shift(w.data(), w.size(), true);
+                packed.resize(ir_hrx3_project_floats(op.Cin, p.Cin, p.Cout, op.stride, op.ir_ce));
+                pack_ir_hrx3_project(w.data(), op.Cin, p.Cin, p.Cout, op.stride, sh, u16(packed), op.ir_ce);
+            } else if (op.route == RT_IR_X3) {             // (Cout % 16 == 0 for these blocks: coutp == Cout)
+                sh = split_weight_shift(w.data(), w.size(), true);
+                packed.resize(w.size());
+                pack_ir_x3_project(w.data(), p.Cin, p.Cout, sh, u16(packed));
             }
-            w_at = op.ir_off[4]; b_at = op.ir_off[5]; nb = (size_t)p.Cout;
         }
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + w_at, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + b_at, shift.data(), nb * sizeof(float), hipMemcpyHostToDevice));
-    } else if (p.kind == 2) {
-        std::vector<float> w((size_t)9 * p.Cin);
-        for (int t = 0; t < 9; ++t)
-            for (int c = 0; c < p.Cin; ++c) w[(size_t)t * p.Cin + c] = kernel[(size_t)t * p.Cin + c] * scale[c];
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float),
-                                hipMemcpyHostToDevice));
-    } else if (op.kind == OP_HEAD) {
+        if (role != 1 && op.route != RT_IR) op.ir_scale[role / 2] = ldexpf(1.0f, -sh);
+        e = upload_layer(m, op.ir_off[2 * role], packed.empty() ? w : packed, op.ir_off[2 * role + 1], shift,
+                         role == 1 ? (size_t)p.Cin : nout);
+        break;
+    }
+    case RT_DW:
+        e = upload_layer(m, op.w_off, fold_bn(kernel, 9, p.Cin, scale), op.b_off, shift, nout);
+        break;
+    case RT_HEAD_SPLITK: case RT_HEAD_F32: {
         // this parameter fills columns [col_off, col_off + Cout) of the fused head matrix
         const PackedShape &ps = op.ps;
         RPN_HIP_CHECK(hipMemcpy2D(m->d_weights + op.w_off + p.col_off, (size_t)ps.cout_pad * sizeof(float), kernel,
                                   (size_t)p.Cout * sizeof(float), (size_t)p.Cout * sizeof(float), (size_t)p.Cin,
                                   hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off + p.col_off, shift.data(), (size_t)p.Cout * sizeof(float),
-                                hipMemcpyHostToDevice));
-        if (rpn_head_supported(op.Cin, op.Cout)) {
+        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off + p.col_off, shift.data(), nout * sizeof(float), hipMemcpyHostToDevice));
+        if (op.head_frag) {
             m->head_host.resize((size_t)512 * ps.cout_pad, 0.0f);
             for (int k = 0; k < 512; ++k)
-                memcpy(&m->head_host[(size_t)k * ps.cout_pad + p.col_off], kernel + (size_t)k * p.Cout, (size_t)p.Cout * sizeof(float));
+                memcpy(&m->head_host[(size_t)k * ps.cout_pad + p.col_off], kernel + (size_t)k * p.Cout, nout * sizeof(float));
             std::vector<float> packed((size_t)512 * 16 * ((op.Cout + 15) / 16));
             pack_head_weights_host(m->head_host.data(), ps.cout_pad, op.Cout, packed.data());
             RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.ir_off[0], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
         }
-    } else if (op.cin3_mfma) {
-        // the power-of-two pre-scale is derived from the FOLDED weights (a BatchNorm scale of 30 on top of a shift
-        // chosen for the raw kernel would push the float16 hi halves past 65504)
-        std::vector<float> folded(kernel, kernel + (size_t)27 * p.Cout);
-        if (has_bn)
-            for (size_t i = 0; i < folded.size(); ++i) folded[i] *= scale[i % (size_t)p.Cout];
+        break;
+    }
+    case RT_CIN3_MFMA: {
+        const std::vector<float> folded = fold_bn(kernel, 27, p.Cout, scale);
         const int wshift = split_weight_shift(folded.data(), folded.size(), m->f16);
-        std::vector<unsigned short> packed((size_t)p.Cout * 64);
+        std::vector<unsigned short> packed(nout * 64);
         pack_weights_cin3_mfma_host(folded.data(), nullptr, p.Cout, p.Cout, m->f16, wshift, packed.data());
         op.out_scale = ldexpf(1.0f, -wshift);
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, packed.data(), packed.size() * sizeof(unsigned short),
-                                hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float),
-                                hipMemcpyHostToDevice));
-    } else if (op.cin3) {
-        std::vector<float> w((size_t)27 * p.Cout);
-        for (int k = 0; k < 27; ++k)
-            for (int n = 0; n < p.Cout; ++n)
-                w[(size_t)k * p.Cout + n] = kernel[(size_t)k * p.Cout + n] * (has_bn ? scale[n] : 1.0f);
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float),
-                                hipMemcpyHostToDevice));
-    } else if (op.split) {
+        e = upload_layer(m, op.w_off, packed, op.b_off, shift, nout);
+        break;
+    }
+    case RT_CIN3:
+        e = upload_layer(m, op.w_off, fold_bn(kernel, 27, p.Cout, scale), op.b_off, shift, nout);
+        break;
+    case RT_SPLIT: case RT_SPLIT16: {
         const int cpad = split_cout_pad(op.Cout);
-        std::vector<float> folded(kernel, kernel + (size_t)9 * p.Cin * p.Cout);       // BatchNorm folded BEFORE the shift
-        if (has_bn)
-            for (size_t i = 0; i < folded.size(); ++i) folded[i] *= scale[i % (size_t)p.Cout];
+        const std::vector<float> folded = fold_bn(kernel, (size_t)9 * p.Cin, p.Cout, scale);
         const int wshift = split_weight_shift(folded.data(), folded.size(), m->f16);
         std::vector<unsigned short> packed(split_weight_bytes(op.Cin, op.Cout) / sizeof(unsigned short));
-        if (op.k16)
-            pack_weights_split32_host(folded.data(), nullptr, p.Cin, p.Cout, cpad, m->f16, wshift, packed.data());
-        else
-            pack_weights_split_host(folded.data(), nullptr, p.Cin, p.Cout, cpad, m->f16, wshift, packed.data());
+        (op.route == RT_SPLIT16 ? pack_weights_split32_host : pack_weights_split_host)(folded.data(), nullptr, p.Cin, p.Cout, cpad, m->f16,
+                                                                                      wshift, packed.data());
         op.out_scale = ldexpf(1.0f, -wshift);
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, packed.data(), packed.size() * sizeof(unsigned short),
-                                hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float),
-                                hipMemcpyHostToDevice));
-    } else if (op.wino) {
+        e = upload_layer(m, op.w_off, packed, op.b_off, shift, nout);
+        break;
+    }
+    case RT_WINO: {
         std::vector<float> packed(wino_weight_floats(p.Cin, p.Cout, op.wino_f));
         pack_weights_wino_host(kernel, has_bn ? scale.data() : nullptr, p.Cin, p.Cout, packed.data(), op.wino_f);
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float), hipMemcpyHostToDevice));
-    } else if (is_pw_x3(m, op)) {
+        e = upload_layer(m, op.w_off, packed, op.b_off, shift, nout);
+        break;
+    }
+    case RT_PW_X3: {
         // [Cin][Cout] with BatchNorm folded, then the power-of-two pre-scale and the fragment-major hi / lo float16 image
-        std::vector<float> w((size_t)p.Cin * p.Cout);
-        for (int k = 0; k < p.Cin; ++k)
-            for (int n = 0; n < p.Cout; ++n) w[(size_t)k * p.Cout + n] = kernel[(size_t)k * p.Cout + n] * (has_bn ? scale[n] : 1.0f);
+        const std::vector<float> w = fold_bn(kernel, (size_t)p.Cin, p.Cout, scale);
         const int sh = split_weight_shift(w.data(), w.size(), true);
         std::vector<float> packed(w.size());
-        pack_ir_x3_expand(w.data(), p.Cin, p.Cout, sh, reinterpret_cast<unsigned short *>(packed.data()));
+        pack_ir_x3_expand(w.data(), p.Cin, p.Cout, sh, u16(packed));
         op.out_scale = ldexpf(1.0f, -sh);
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float), hipMemcpyHostToDevice));
-    } else {
+        e = upload_layer(m, op.w_off, packed, op.b_off, shift, nout);
+        break;
+    }
+    case RT_F32: {
         std::vector<float> packed(op.ps.floats());
         pack_weights_host(op.ps, kernel, has_bn ? scale.data() : nullptr, packed.data());
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.w_off, packed.data(), packed.size() * sizeof(float),
-                                hipMemcpyHostToDevice));
-        RPN_HIP_CHECK(hipMemcpy(m->d_weights + op.b_off, shift.data(), (size_t)p.Cout * sizeof(float),
-                                hipMemcpyHostToDevice));
+        e = upload_layer(m, op.w_off, packed, op.b_off, shift, nout);
+        break;
     }
+    default: break;                                        // (ops without parameters: no Param points at one)
+    }
+    if (e != RPN_OK) return e;
     p.loaded = true;
     return RPN_OK;
 }
@@ -948,132 +999,113 @@ static int run_ops(rpn_model *m, const float *d_imgs, int B, float *d_reg, float
         return (boundary > 0 && marked(boundary - 1)) || (boundary < m->ops.size() && marked(boundary));
     };
     if (evs && want_event(0)) RPN_HIP_CHECK(hipEventRecord(evs[0], s));
-    int op_index = 0;
-    bool skip_next = false;
     int head_slabs = 1;                     // > 1: the head's input is that many partial-sum slabs of a split-K rpn_conv
     size_t head_conv_bias = 0;
-    // split-K factor of op i at this batch size: > 1 only for rpn_conv feeding the slab-adding head, when its output tensor
-    // has room for factor * B images (RPN_KSPLIT=1; conv3x3_split16_ksplit says when it pays)
-    // rpn_conv feeding the slab-adding head runs as a K TREE (conv_kernels.h) at every batch size of this model, or at none
-    auto ktree_for = [&](size_t i) -> bool {
-        const Op &o = m->ops[i];
-        return o.kind == OP_CONV && o.split && o.k16 && o.out_f32 && i + 1 < m->ops.size() && m->ops[i + 1].kind == OP_HEAD &&
-               m->ops[i + 1].in == o.out && rpn_head_supported(512, 5 * m->K) && head_splitk() &&
-               conv3x3_split16_ktree_ok(m->max_batch, o.H, o.W, o.Cin, o.Cout, split_cout_pad(o.Cout));
-    };
-    auto ksplit_for = [&](size_t i) -> int {
-        const Op &o = m->ops[i];
-        if (!ktree_for(i) || m->keep_all) return 1;     // (every activation kept: the tree inside one workgroup's tile loop)
-        const int f = conv3x3_split16_ksplit(B, o.H, o.W, o.Cin, o.Cout, split_cout_pad(o.Cout));
-        return (size_t)f * B <= (size_t)m->tensors[o.out].slabs * m->max_batch ? f : 1;
-    };
     for (size_t oi = 0; oi < n_ops; ++oi) {
         const Op &op = m->ops[oi];
-        const float *x = tensor_ptr(m, op.in, d_imgs);
-        hipError_t e = hipSuccess;
-        // a split conv directly followed by its 2x2 max-pool runs as ONE kernel (pool fused into the
-        // epilogue; the un-pooled activation never reaches HBM) unless every activation must be kept
-        const bool fuse_pool = op.kind == OP_CONV && op.split && !op.out_f32 && !m->keep_all &&
-                               oi + 1 < m->ops.size() && m->ops[oi + 1].kind == OP_POOL &&
-                               m->ops[oi + 1].split && m->ops[oi + 1].in == op.out;
-        if (skip_next) {
-            skip_next = false;                      // the pool already ran inside the previous conv
-        } else if (op.kind == OP_TOSPLIT) {
-            e = launch_f32_to_split(x, (long long)B * op.H * op.W, op.Cin, m->f16, tensor_ptr(m, op.out, d_imgs), s);
-        } else if (op.kind == OP_CONV && op.cin3_mfma) {
-            e = launch_conv_cin3_mfma(x, m->d_weights + op.w_off, m->d_weights + op.b_off, tensor_ptr(m, op.out, d_imgs),
-                                      B, op.H, op.W, op.OH, op.OW, op.Cout, op.stride, op.pad_t, op.pad_l, op.act,
-                                      op.out_scale, m->tensors[op.out].split_fmt ? 1 : 0, m->f16, s);
-        } else if (op.kind == OP_CONV && op.cin3) {
-            e = launch_conv_cin3(x, m->d_weights + op.w_off, m->d_weights + op.b_off, tensor_ptr(m, op.out, d_imgs), B,
-                                 op.H, op.W, op.OH, op.OW, op.Cout, op.stride, op.pad_t, op.pad_l, op.act,
-                                 m->tensors[op.out].split_fmt ? 1 : 0, m->f16, s);
-        } else if (ksplit_for(oi) > 1) {
-            // rpn_conv at a small batch: split-K, raw partial sums; the head adds the slabs (+ this layer's bias, ReLU)
-            head_slabs = ksplit_for(oi);
-            head_conv_bias = op.b_off;
-            e = launch_conv3x3_split16_ksplit(x, m->d_weights + op.w_off, tensor_ptr(m, op.out, d_imgs),
-                                              (long long)B * op.H * op.W * op.Cout, B, op.H, op.W, op.Cin, op.Cout,
-                                              split_cout_pad(op.Cout), op.out_scale, m->f16, head_slabs, s);
-        } else if (ktree_for(oi)) {
-            e = launch_conv3x3_split16(x, m->d_weights + op.w_off, m->d_weights + op.b_off, tensor_ptr(m, op.out, d_imgs), B, op.H,
-                                       op.W, op.Cin, op.Cout, split_cout_pad(op.Cout), op.out_scale, op.act, true, m->f16, false,
-                                       s, true);
-        } else if (op.kind == OP_CONV && op.split) {
-            const int dst = fuse_pool ? m->ops[oi + 1].out : op.out;
-            e = (op.k16 ? launch_conv3x3_split16 : launch_conv3x3_split)(
-                x, m->d_weights + op.w_off, m->d_weights + op.b_off, tensor_ptr(m, dst, d_imgs), B, op.H, op.W, op.Cin,
-                op.Cout, split_cout_pad(op.Cout), op.out_scale, op.act, op.out_f32, m->f16, fuse_pool, s, false);
-            skip_next = fuse_pool;
-        } else if (op.kind == OP_POOL && op.split) {
-            e = launch_maxpool_split(x, B, op.H, op.W, op.Cin, m->f16, tensor_ptr(m, op.out, d_imgs), s);
-        } else if (op.kind == OP_HEAD && rpn_head_supported(op.Cin, op.Cout) && head_splitk()) {
-            e = launch_rpn_head(x, (long long)B * op.H * op.W, m->d_weights + op.ir_off[0], m->d_weights + op.b_off, 4 * m->K,
-                                m->K, d_reg, d_cls, s, head_slabs, (long long)B * op.H * op.W * 512,
-                                head_slabs > 1 ? m->d_weights + head_conv_bias : nullptr);
-            head_slabs = 1;
-        } else if (is_pw_x3(m, op)) {
-            e = launch_pw_x3(x, (long long)B * op.H * op.W, op.Cin, op.Cout, m->d_weights + op.w_off, m->d_weights + op.b_off,
-                             op.out_scale, tensor_ptr(m, op.out, d_imgs), m->d_status, s);
-        } else if (op.kind == OP_CONV && op.wino) {
-            const bool pool = f32_pool_fused(m, oi);                    // + block*_pool: a Winograd tile's 2 x 2 outputs are one window
-            e = launch_conv3x3_wino(x, m->d_weights + op.w_off, m->d_weights + op.b_off,
-                                    tensor_ptr(m, pool ? m->ops[oi + 1].out : op.out, d_imgs), B, op.H, op.W, op.Cin, op.Cout, op.act,
-                                    pool, s, op.wino_f, m->d_wino_ws);
-            skip_next = pool;
-        } else if (op.kind == OP_CONV || op.kind == OP_HEAD) {
+        const float *x = tensor_ptr(m, op.in, d_imgs), *wb = m->d_weights, *w = wb + op.w_off, *bias = wb + op.b_off;
+        // (a conv that also does the next op's pool writes that op's tensor)
+        float *y = op.out >= 0 ? tensor_ptr(m, op.pools_next ? m->ops[oi + 1].out : op.out, d_imgs) : nullptr;
+        auto igemm_args = [&]() {           // the float32 implicit GEMM's arguments, but for the outputs
             ConvArgs a{};
-            a.x = x;
-            a.w = m->d_weights + op.w_off;
-            a.bias = m->d_weights + op.b_off;
+            a.x = x; a.w = w; a.bias = bias;
             a.residual = op.residual >= 0 ? tensor_ptr(m, op.residual, d_imgs) : nullptr;
             a.B = B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.OH = op.OH; a.OW = op.OW; a.Cout = op.Cout;
             a.R = op.R; a.S = op.S; a.stride = op.stride; a.pad_t = op.pad_t; a.pad_l = op.pad_l;
             a.ps = op.ps;
-            if (op.kind == OP_HEAD) {
-                a.out = d_reg; a.ld1 = 4 * m->K; a.act = ACT_LINEAR; a.split = 4 * m->K;
-                a.out2 = d_cls; a.ld2 = m->K; a.act2 = ACT_SIGMOID;
+            return a;
+        };
+        hipError_t e = hipSuccess;
+        switch (op.route) {
+        case RT_FUSED: break;                // the pool already ran inside the previous conv
+        case RT_TOSPLIT: e = launch_f32_to_split(x, (long long)B * op.H * op.W, op.Cin, m->f16, y, s); break;
+        case RT_CIN3_MFMA:
+            e = launch_conv_cin3_mfma(x, w, bias, y, B, op.H, op.W, op.OH, op.OW, op.Cout, op.stride, op.pad_t, op.pad_l, op.act,
+                                      op.out_scale, m->tensors[op.out].split_fmt ? 1 : 0, m->f16, s);
+            break;
+        case RT_CIN3:
+            e = launch_conv_cin3(x, w, bias, y, B, op.H, op.W, op.OH, op.OW, op.Cout, op.stride, op.pad_t, op.pad_l, op.act,
+                                 m->tensors[op.out].split_fmt ? 1 : 0, m->f16, s);
+            break;
+        case RT_SPLIT:
+            e = launch_conv3x3_split(x, w, bias, y, B, op.H, op.W, op.Cin, op.Cout, split_cout_pad(op.Cout), op.out_scale, op.act,
+                                     op.out_f32, m->f16, op.pools_next, s, false);
+            break;
+        case RT_SPLIT16: {
+            // the split-K factor at THIS batch size: > 1 only for rpn_conv feeding the slab-adding head, when its output tensor has
+            // room for factor * B images (conv3x3_split16_ksplit says when it pays)
+            const int cpad = split_cout_pad(op.Cout);
+            const int f = op.ksplit ? conv3x3_split16_ksplit(B, op.H, op.W, op.Cin, op.Cout, cpad) : 1;
+            if (f > 1 && (size_t)f * B <= (size_t)m->tensors[op.out].slabs * m->max_batch) {
+                // raw partial sums; the head adds the slabs (+ this layer's bias, ReLU)
+                head_slabs = f;
+                head_conv_bias = op.b_off;
+                e = launch_conv3x3_split16_ksplit(x, w, y, (long long)B * op.H * op.W * op.Cout, B, op.H, op.W, op.Cin, op.Cout, cpad,
+                                                  op.out_scale, m->f16, f, s);
             } else {
-                const bool pool = f32_pool_fused(m, oi);                // + block*_pool in the epilogue: writes the pool's tensor
-                a.out = tensor_ptr(m, pool ? m->ops[oi + 1].out : op.out, d_imgs); a.ld1 = op.Cout; a.act = op.act; a.split = op.Cout;
-                a.out2 = nullptr; a.ld2 = 0; a.act2 = ACT_LINEAR;
-                a.out_split = op.f32_out_split ? (m->f16 ? 2 : 1) : 0;
-                a.status = op.f32_out_split && m->f16 ? m->d_status : nullptr;
-                a.pool = pool ? 1 : 0;
-                skip_next = pool;
+                e = launch_conv3x3_split16(x, w, bias, y, B, op.H, op.W, op.Cin, op.Cout, cpad, op.out_scale, op.act, op.out_f32, m->f16,
+                                           op.pools_next, s, op.ktree);
             }
+            break;
+        }
+        case RT_POOL_SPLIT: e = launch_maxpool_split(x, B, op.H, op.W, op.Cin, m->f16, y, s); break;
+        case RT_POOL_F32: e = launch_maxpool2x2(x, B, op.H, op.W, op.Cin, y, s); break;
+        case RT_HEAD_SPLITK:
+            e = launch_rpn_head(x, (long long)B * op.H * op.W, wb + op.ir_off[0], bias, 4 * m->K, m->K, d_reg, d_cls, s, head_slabs,
+                                (long long)B * op.H * op.W * 512, head_slabs > 1 ? wb + head_conv_bias : nullptr);
+            head_slabs = 1;
+            break;
+        case RT_PW_X3:
+            e = launch_pw_x3(x, (long long)B * op.H * op.W, op.Cin, op.Cout, w, bias, op.out_scale, y, m->d_status, s);
+            break;
+        case RT_WINO:                        // (+ block*_pool: a Winograd tile's 2 x 2 outputs are one window)
+            e = launch_conv3x3_wino(x, w, bias, y, B, op.H, op.W, op.Cin, op.Cout, op.act, op.pools_next, s, op.wino_f, m->d_wino_ws);
+            break;
+        case RT_HEAD_F32: {
+            ConvArgs a = igemm_args();
+            a.out = d_reg; a.ld1 = 4 * m->K; a.act = ACT_LINEAR; a.split = 4 * m->K;
+            a.out2 = d_cls; a.ld2 = m->K; a.act2 = ACT_SIGMOID;
             e = launch_conv_f32(a, s);
-        } else if (op.kind == OP_VGGB1) {
-            const float *wb = m->d_weights;
-            e = launch_vgg_block1(x, wb + op.ir_off[0], wb + op.ir_off[1], op.ir_scale[0], wb + op.ir_off[2],
-                                  wb + op.ir_off[3], op.ir_scale[1], tensor_ptr(m, op.out, d_imgs), B, op.H, op.W, m->f16, s);
-        } else if (op.kind == OP_IRBLOCK) {
-            const float *wb = m->d_weights;
-            if (op.ir_hrx3)
-                e = launch_ir_block_hrx3(x, B, op.H, op.W, op.Cin, op.cexp, op.Cout, op.stride, op.ir_res, op.ir_pad, op.OH, op.OW,
-                                         wb + op.ir_off[0], wb + op.ir_off[1], wb + op.ir_off[2], wb + op.ir_off[3],
-                                         wb + op.ir_off[4], wb + op.ir_off[5], op.ir_scale[0], op.ir_scale[1],
-                                         tensor_ptr(m, op.out, d_imgs), m->d_status, m->d_ksplit, s, op.ir_ce);
-            else if (op.ir_x3)
-                e = launch_ir_block_x3(x, B, op.H, op.W, op.Cin, op.cexp, op.Cout, op.ir_res, wb + op.ir_off[0],
-                                       wb + op.ir_off[1], wb + op.ir_off[2], wb + op.ir_off[3], wb + op.ir_off[4],
-                                       wb + op.ir_off[5], op.ir_scale[0], op.ir_scale[1], tensor_ptr(m, op.out, d_imgs),
-                                       m->d_status, m->d_ksplit, s);
-            else
-            e = launch_ir_block(x, B, op.H, op.W, op.Cin, op.cexp, op.Cout, op.stride, op.ir_res, op.ir_stem, op.ir_pad,
-                                op.OH, op.OW, wb + op.ir_off[0], wb + op.ir_off[1], wb + op.ir_off[2], wb + op.ir_off[3],
-                                wb + op.ir_off[4], wb + op.ir_off[5], tensor_ptr(m, op.out, d_imgs), s);
-        } else if (op.kind == OP_DWCONV) {
-            e = launch_dwconv3x3(x, B, op.H, op.W, op.Cin, m->d_weights + op.w_off, m->d_weights + op.b_off,
-                                 op.stride, op.pad_t, op.pad_l, op.OH, op.OW, op.act, tensor_ptr(m, op.out, d_imgs), s);
-        } else {
-            e = launch_maxpool2x2(x, B, op.H, op.W, op.Cin, tensor_ptr(m, op.out, d_imgs), s);
+            break;
+        }
+        case RT_F32: {                       // (+ block*_pool in the epilogue)
+            ConvArgs a = igemm_args();
+            a.out = y; a.ld1 = op.Cout; a.act = op.act; a.split = op.Cout;
+            a.out2 = nullptr; a.ld2 = 0; a.act2 = ACT_LINEAR;
+            a.out_split = op.f32_out_split ? (m->f16 ? 2 : 1) : 0;
+            a.status = op.f32_out_split && m->f16 ? m->d_status : nullptr;
+            a.pool = op.pools_next ? 1 : 0;
+            e = launch_conv_f32(a, s);
+            break;
+        }
+        case RT_VGGB1:
+            e = launch_vgg_block1(x, wb + op.ir_off[0], wb + op.ir_off[1], op.ir_scale[0], wb + op.ir_off[2], wb + op.ir_off[3],
+                                  op.ir_scale[1], y, B, op.H, op.W, m->f16, s);
+            break;
+        case RT_IR_HRX3:
+            e = launch_ir_block_hrx3(x, B, op.H, op.W, op.Cin, op.cexp, op.Cout, op.stride, op.ir_res, op.ir_pad, op.OH, op.OW,
+                                     wb + op.ir_off[0], wb + op.ir_off[1], wb + op.ir_off[2], wb + op.ir_off[3], wb + op.ir_off[4],
+                                     wb + op.ir_off[5], op.ir_scale[0], op.ir_scale[1], y, m->d_status, m->d_ksplit, s, op.ir_ce);
+            break;
+        case RT_IR_X3:
+            e = launch_ir_block_x3(x, B, op.H, op.W, op.Cin, op.cexp, op.Cout, op.ir_res, wb + op.ir_off[0], wb + op.ir_off[1],
+                                   wb + op.ir_off[2], wb + op.ir_off[3], wb + op.ir_off[4], wb + op.ir_off[5], op.ir_scale[0],
+                                   op.ir_scale[1], y, m->d_status, m->d_ksplit, s);
+            break;
+        case RT_IR:
+            e = launch_ir_block(x, B, op.H, op.W, op.Cin, op.cexp, op.Cout, op.stride, op.ir_res, op.ir_stem, op.ir_pad, op.OH, op.OW,
+                                wb + op.ir_off[0], wb + op.ir_off[1], wb + op.ir_off[2], wb + op.ir_off[3], wb + op.ir_off[4],
+                                wb + op.ir_off[5], y, s);
+            break;
+        case RT_DW:
+            e = launch_dwconv3x3(x, B, op.H, op.W, op.Cin, w, bias, op.stride, op.pad_t, op.pad_l, op.OH, op.OW, op.act, y, s);
+            break;
+        case RT_NONE: e = hipErrorInvalidValue; break;
         }
         if (e != hipSuccess)
             return fail(RPN_ERR_NO_DEVICE, "rpn_model_forward: layer '%s' failed to launch: %s", op.name.c_str(),
                         hipGetErrorString(e));
-        ++op_index;
-        if (evs && want_event((size_t)op_index)) RPN_HIP_CHECK(hipEventRecord(evs[op_index], s));
+        if (evs && want_event(oi + 1)) RPN_HIP_CHECK(hipEventRecord(evs[oi + 1], s));
         if (op.out == m->feat_tensor) m->feat_written = true;
     }
     return RPN_OK;
@@ -1105,50 +1137,48 @@ void model_train_backbone(const rpn_model *m, int *backbone, int *img_size)
     *backbone = m->backbone; *img_size = m->img_size;
 }
 
-// The backbone of a training step (the head is trained on frozen features): the ops up to the one that writes feat_tensor, at the
-// handle's own precision, then the features as NHWC float32 into d_feat (B, F, F, Cin) -- converted from the split form when the
-// tensor is kept that way, as rpn_model_get_activation does.
-static int features_of(rpn_model *m, int tensor, const float *d_imgs, int B, float *d_feat, hipStream_t s)
+// the number of leading ops that ends with the one writing tensor t
+static size_t ops_through(const rpn_model *m, int t)
 {
-    const int st = ensure_device(m);
-    if (st != RPN_OK) return st;
     size_t n = 0;
     for (size_t i = 0; i < m->ops.size(); ++i)
-        if (m->ops[i].out == tensor) n = i + 1;
-    const int e0 = run_ops(m, d_imgs, B, nullptr, nullptr, s, n);
-    if (e0 != RPN_OK) return e0;
+        if (m->ops[i].out == t) n = i + 1;
+    return n;
+}
+
+// The first `images` images of a tensor at src as NHWC float32 into a caller's buffer -- converted from the split form when the
+// tensor is kept that way.  `who` opens the error message.
+static int tensor_to_f32(rpn_model *m, int tensor, const float *src, int images, float *d_out, hipStream_t s, const char *who)
+{
     const Tensor &t = m->tensors[tensor];
-    const float *src = tensor_ptr(m, tensor, d_imgs);
     if (t.split_fmt) {
-        const hipError_t e = launch_split_to_f32(src, (long long)B * t.H * t.W, t.C, m->f16, d_feat, s);
-        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_head_trainer_step: features: %s", hipGetErrorString(e));
+        const hipError_t e = launch_split_to_f32(src, (long long)images * t.H * t.W, t.C, m->f16, d_out, s);
+        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
         return RPN_OK;
     }
-    RPN_HIP_CHECK(hipMemcpyAsync(d_feat, src, (size_t)B * t.H * t.W * t.C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RPN_HIP_CHECK(hipMemcpyAsync(d_out, src, (size_t)images * t.H * t.W * t.C * sizeof(float), hipMemcpyDeviceToDevice, s));
     return RPN_OK;
 }
 
-int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s)
+// The frozen prefix of a training step: the ops up to the one that writes `tensor`, at the handle's own precision, then the tensor as
+// NHWC float32 into d_feat (B, H, W, C), as rpn_model_get_activation gives it.  Only the layers of those ops need weights in the handle.
+static int features_of(rpn_model *m, int tensor, const float *d_imgs, int B, float *d_feat, hipStream_t s)
 {
+    const size_t n = ops_through(m, tensor);
     for (const Param &p : m->params)
-        if (p.name != "rpn_conv" && p.name != "rpn_reg" && p.name != "rpn_cls")
+        if (p.op >= 0 && (size_t)p.op < n)
             RPN_REQUIRE(p.loaded, "rpn_head_trainer_step: weights of layer '%s' were never set", p.name.c_str());
-    return features_of(m, m->feat_tensor, d_imgs, B, d_feat, s);
+    const int st = ensure_device(m);
+    if (st != RPN_OK) return st;
+    const int e0 = run_ops(m, d_imgs, B, nullptr, nullptr, s, n);
+    if (e0 != RPN_OK) return e0;
+    return tensor_to_f32(m, tensor, tensor_ptr(m, tensor, d_imgs), B, d_feat, s, "rpn_head_trainer_step: features");
 }
 
-static int tensor_by_name(const rpn_model *m, const char *name)
-{
-    for (size_t i = 0; i < m->tensors.size(); ++i)
-        if (m->tensors[i].name == name) return (int)i;
-    return -1;
-}
+// the backbone under a trained head: everything below rpn_conv
+int model_features(rpn_model *m, const float *d_imgs, int B, float *d_feat, hipStream_t s) { return features_of(m, m->feat_tensor, d_imgs, B, d_feat, s); }
 
-bool model_has_layer(const rpn_model *m, const char *name)
-{
-    for (const Param &p : m->params)
-        if (p.name == name) return true;
-    return false;
-}
+bool model_has_layer(const rpn_model *m, const char *name) { return param_by_name(m, name) >= 0; }
 
 int model_tensor_shape(const rpn_model *m, const char *name, int *H, int *W, int *C)
 {
@@ -1158,18 +1188,11 @@ int model_tensor_shape(const rpn_model *m, const char *name, int *H, int *W, int
     return RPN_OK;
 }
 
-// The frozen prefix of a step that trains the layers above tensor `name`: the ops up to the one that writes it, then the tensor
-// as NHWC float32 into d_out.  Only the layers of those ops need weights in the handle.
+// ... and under the layers above tensor `name`
 int model_features_at(rpn_model *m, const char *name, const float *d_imgs, int B, float *d_out, hipStream_t s)
 {
     const int ti = tensor_by_name(m, name);
     if (ti < 0) return fail(RPN_ERR_INVALID, "the model has no tensor named '%s'", name);
-    size_t n = 0;
-    for (size_t i = 0; i < m->ops.size(); ++i)
-        if (m->ops[i].out == ti) n = i + 1;
-    for (const Param &p : m->params)
-        if (p.op >= 0 && (size_t)p.op < n)
-            RPN_REQUIRE(p.loaded, "rpn_head_trainer_step: weights of layer '%s' were never set", p.name.c_str());
     return features_of(m, ti, d_imgs, B, d_out, s);
 }
 
@@ -1228,89 +1251,75 @@ extern "C" int rpn_model_op_info(const rpn_model *m, int i, char *name, int name
     RPN_REQUIRE(m && i >= 0 && i < (int)m->ops.size(), "rpn_model_op_info: bad index %d", i);
     const Op &op = m->ops[i];
     if (name && name_len > 0) snprintf(name, (size_t)name_len, "%s", op.name.c_str());
-    double fl = 0.0, by = 0.0;
-    const char *k = "maxpool2x2";
     const double in_b = 4.0 * op.H * op.W * op.Cin, out_b = 4.0 * op.OH * op.OW * op.Cout;
-    // a 2x2 max-pool that runs inside the epilogue of the split conv in front of it (rpn_model_forward: fuse_pool) is not a
-    // launch: no kernel, no bytes of its own (the conv's row carries the pooled output)
-    const bool pool_fused_away = op.kind == OP_POOL && op.split && !m->keep_all && i > 0 && m->ops[i - 1].kind == OP_CONV &&
-                                 m->ops[i - 1].split && !m->ops[i - 1].out_f32 && !m->ops[i - 1].cin3 && op.in == m->ops[i - 1].out;
-    if (op.kind == OP_TOSPLIT) {
-        by = in_b + out_b;
-        k = "f32_to_split";
-    } else if (pool_fused_away) {
-        k = "fused:maxpool_split";
-    } else if (op.kind == OP_POOL && i > 0 && f32_pool_fused(m, (size_t)i - 1)) {
-        k = "fused:maxpool_f32";                   // runs inside the previous float32 conv's epilogue: no launch, no bytes of its own
-    } else if (op.kind == OP_POOL && op.split) {
-        by = in_b + out_b;
-        k = "maxpool_split";
-    } else if (op.kind == OP_CONV && op.cin3) {
+    double fl = 0.0, by = in_b + out_b;
+    char kname[64];
+    const char *k = kname;
+    const char *prec = m->f16 ? "f16x3" : "bf16x3";
+    switch (op.route) {
+    case RT_NONE: k = "?"; break;
+    case RT_TOSPLIT: k = "f32_to_split"; break;
+    case RT_FUSED:
+        // runs inside the epilogue of the conv in front of it: not a launch, no kernel, no bytes of its own (the conv's row
+        // carries the pooled output)
+        by = 0.0;
+        k = m->tensors[op.in].split_fmt ? "fused:maxpool_split" : "fused:maxpool_f32";
+        break;
+    case RT_POOL_SPLIT: k = "maxpool_split"; break;
+    case RT_POOL_F32: k = "maxpool2x2"; break;
+    case RT_DW: fl = 2.0 * op.OH * op.OW * op.Cin * 9; k = "dwconv3x3"; break;
+    case RT_CIN3: case RT_CIN3_MFMA:
         fl = 2.0 * op.OH * op.OW * op.Cout * 27.0;
-        by = in_b + out_b;
-        k = op.cin3_mfma ? "conv_cin3_mfma"
+        k = op.route == RT_CIN3_MFMA ? "conv_cin3_mfma"
             : conv_cin3_uses_f32_mfma(1, op.H, op.W, op.OH, op.OW, op.Cout, op.stride, op.pad_t, op.pad_l, op.act,
                                       m->tensors[op.out].split_fmt ? 1 : 0) ? "conv_cin3_f32_mfma" : "conv_cin3_direct";
-    } else if (op.kind == OP_CONV && op.split) {
+        break;
+    case RT_SPLIT: case RT_SPLIT16:
         fl = 2.0 * op.OH * op.OW * op.Cout * 9.0 * op.Cin;
-        by = in_b + out_b + 4.0 * 9 * op.Cin * op.Cout;
+        by += 4.0 * 9 * op.Cin * op.Cout;
         // the kernel template that runs this layer (both POOL instantiations under one name)
-        static thread_local char kname[64];
-        const char *prec = m->f16 ? "f16x3" : "bf16x3";
-        if (op.k16) {
-            const bool fused_pool = i + 1 < (int)m->ops.size() && m->ops[i + 1].kind == OP_POOL && m->ops[i + 1].split;
-            const char *v = conv3x3_split16_variant(m->max_batch, op.H, op.W, op.Cin, op.Cout, split_cout_pad(op.Cout), fused_pool);
+        if (op.route == RT_SPLIT16) {
+            const bool pool_behind = i + 1 < (int)m->ops.size() && m->ops[i + 1].kind == OP_POOL;
+            const char *v = conv3x3_split16_variant(m->max_batch, op.H, op.W, op.Cin, op.Cout, split_cout_pad(op.Cout), pool_behind);
             // (rpn_conv as a K tree: the 64-wide persistent kernel whenever one workgroup per tile walks all of K)
-            if (v && v[0] == 'd' && op.out_f32 && i + 1 < (int)m->ops.size() && m->ops[i + 1].kind == OP_HEAD &&
-                rpn_head_supported(512, 5 * m->K) && head_splitk() &&
-                conv3x3_split16_ktree_ok(m->max_batch, op.H, op.W, op.Cin, op.Cout, split_cout_pad(op.Cout)))
-                v = "dma,64";
+            if (v && v[0] == 'd' && op.ktree) v = "dma,64";
             if (v && v[0] == 'd') snprintf(kname, sizeof kname, "conv3x3_split16_dma<%s,%s>", prec, v + 4);
             else snprintf(kname, sizeof kname, "conv3x3_split16<%s,%s>", prec, v ? v + 4 : "?");
         } else {
             snprintf(kname, sizeof kname, "conv3x3_split<%s>", prec);
         }
-        k = kname;
-    } else if (op.kind == OP_CONV || op.kind == OP_HEAD) {
+        break;
+    case RT_HEAD_SPLITK: case RT_HEAD_F32: case RT_PW_X3: case RT_WINO: case RT_F32:
         fl = 2.0 * op.OH * op.OW * op.Cout * op.R * op.S * op.Cin;
-        by = in_b + out_b + 4.0 * op.R * op.S * op.Cin * op.Cout;
-        static thread_local char kname32[64];
-        if (op.kind == OP_HEAD && rpn_head_supported(op.Cin, op.Cout) && head_splitk())
-            snprintf(kname32, sizeof kname32, "rpn_head_splitk<%d>", (op.Cout + 15) / 16);
-        else if (is_pw_x3(m, op))
-            snprintf(kname32, sizeof kname32, "pw_f16x3<%d,%d>", op.Cin, op.Cout);
-        else if (op.kind == OP_CONV && op.wino)
-            snprintf(kname32, sizeof kname32, op.wino_f == 16 ? "conv3x3_wino4_f32<16x16x128>" : op.wino_f == 4 ? "conv3x3_wino4_f32<16x32x64>"
-                                              : (op.wino_f == 8 ? "conv3x3_wino4_f32<16x32x64,k2>" : "conv3x3_wino_f32<16x16x64>"));   // (fl above: the direct conv's flops; 4 x / 2.25 x fewer are executed)
-        else
-        {
+        by += 4.0 * op.R * op.S * op.Cin * op.Cout;
+        if (op.route == RT_HEAD_SPLITK) {
+            snprintf(kname, sizeof kname, "rpn_head_splitk<%d>", (op.Cout + 15) / 16);
+        } else if (op.route == RT_PW_X3) {
+            snprintf(kname, sizeof kname, "pw_f16x3<%d,%d>", op.Cin, op.Cout);
+        } else if (op.route == RT_WINO) {     // (fl above: the direct conv's flops; 4 x / 2.25 x fewer are executed)
+            k = op.wino_f == 16 ? "conv3x3_wino4_f32<16x16x128>" : op.wino_f == 4 ? "conv3x3_wino4_f32<16x32x64>"
+                : (op.wino_f == 8 ? "conv3x3_wino4_f32<16x32x64,k2>" : "conv3x3_wino_f32<16x16x64>");
+        } else {
             const int bn32 = conv_f32_tile_n(m->max_batch, op.OH, op.OW, op.Cout);
-            snprintf(kname32, sizeof kname32, "conv_igemm_f32%s<128x%d%s>", conv_f32_uses_dma(bn32, op.ps.generic) ? "_dma" : "", bn32,
+            snprintf(kname, sizeof kname, "conv_igemm_f32%s<128x%d%s>", conv_f32_uses_dma(bn32, op.ps.generic) ? "_dma" : "", bn32,
                      op.ps.generic ? ",generic" : "");
         }
-        k = kname32;
-    } else if (op.kind == OP_VGGB1) {
+        break;
+    case RT_VGGB1:
         fl = 2.0 * op.H * op.W * 64 * 9.0 * (3 + 64);
-        by = in_b + out_b + 4.0 * 9 * (3 + 64) * 64;
-        static thread_local char kb1[64];
-        snprintf(kb1, sizeof kb1, "vgg_block1<%s>", m->f16 ? "f16x3" : "bf16x3");
-        k = kb1;
-    } else if (op.kind == OP_IRBLOCK) {
+        by += 4.0 * 9 * (3 + 64) * 64;
+        snprintf(kname, sizeof kname, "vgg_block1<%s>", prec);
+        break;
+    case RT_IR: case RT_IR_X3: case RT_IR_HRX3: {
         const int DH = op.ir_stem ? (op.H + op.ir_pad + 1 - 3) / 2 + 1 : op.H, DW = op.ir_stem ? (op.W + op.ir_pad + 1 - 3) / 2 + 1 : op.W;
         const double kin = op.ir_stem ? 27.0 : (double)op.Cin;
         fl = 2.0 * DH * DW * op.cexp * kin + 2.0 * op.OH * op.OW * op.cexp * 9.0 + 2.0 * op.OH * op.OW * (double)op.cexp * op.Cout;
-        by = in_b + out_b + 4.0 * (kin * op.cexp + 10.0 * op.cexp + (double)op.cexp * op.Cout + op.Cout);
-        static thread_local char kir[64];
-        if (op.ir_stem) snprintf(kir, sizeof kir, "ir_block<stem,32,16,s1>");
-        else snprintf(kir, sizeof kir, "ir_block%s<%d,%d,%d,s%d%s>", op.ir_hrx3 ? "_hr_f16x3" : (op.ir_x3 ? "_f16x3" : ""), op.Cin, op.cexp, op.Cout, op.stride,
-                      op.ir_res ? ",res" : "");
-        k = kir;
-    } else if (op.kind == OP_DWCONV) {
-        fl = 2.0 * op.OH * op.OW * op.Cin * 9;
-        by = in_b + out_b;
-        k = "dwconv3x3";
-    } else {
-        by = in_b + out_b;
+        by += 4.0 * (kin * op.cexp + 10.0 * op.cexp + (double)op.cexp * op.Cout + op.Cout);
+        if (op.ir_stem) snprintf(kname, sizeof kname, "ir_block<stem,32,16,s1>");
+        else snprintf(kname, sizeof kname, "ir_block%s<%d,%d,%d,s%d%s>", op.route == RT_IR_HRX3 ? "_hr_f16x3" : (op.route == RT_IR_X3 ? "_f16x3" : ""),
+                      op.Cin, op.cexp, op.Cout, op.stride, op.ir_res ? ",res" : "");
+        break;
+    }
     }
     if (kernel && kernel_len > 0) snprintf(kernel, (size_t)kernel_len, "%s", k);
     if (flops_per_image) *flops_per_image = fl;
@@ -1323,11 +1332,12 @@ extern "C" int rpn_model_op_info(const rpn_model *m, int i, char *name, int name
 extern "C" int rpn_model_op_arith(const rpn_model *m, int i)
 {
     if (!m || i < 0 || i >= (int)m->ops.size()) return -1;
-    const Op &op = m->ops[i];
-    const bool x3 = (op.kind == OP_CONV && (op.split || op.cin3_mfma)) || op.kind == OP_VGGB1 || (op.kind == OP_IRBLOCK && op.ir_x3) ||
-                    is_pw_x3(m, op);
-    if (op.kind == OP_CONV && op.wino) return RPN_PRECISION_F32W;     // float32 MFMA, 1 / 2.25 of the direct conv's multiply-adds
-    return x3 ? (m->f16 ? RPN_PRECISION_F16X3 : RPN_PRECISION_BF16X3) : RPN_PRECISION_F32;
+    switch (m->ops[i].route) {
+    case RT_CIN3_MFMA: case RT_SPLIT: case RT_SPLIT16: case RT_PW_X3: case RT_VGGB1: case RT_IR_X3: case RT_IR_HRX3:
+        return m->f16 ? RPN_PRECISION_F16X3 : RPN_PRECISION_BF16X3;
+    case RT_WINO: return RPN_PRECISION_F32W;      // float32 MFMA, 1 / 2.25 of the direct conv's multiply-adds
+    default: return RPN_PRECISION_F32;
+    }
 }
 
 // mean elapsed milliseconds of every op over the kept forwards (synchronises on their last events);
@@ -1364,10 +1374,8 @@ extern "C" int rpn_model_get_activation(rpn_model *m, const char *name, float *d
                                         int shape[4], void *stream)
 {
     RPN_REQUIRE(m && name, "rpn_model_get_activation: null argument");
-    int ti = -1;
-    for (int i = 1; i < (int)m->tensors.size(); ++i)
-        if (m->tensors[i].name == name) ti = i;
-    RPN_REQUIRE(ti >= 0, "rpn_model_get_activation: no activation named '%s'", name);
+    const int ti = tensor_by_name(m, name);
+    RPN_REQUIRE(ti >= 1, "rpn_model_get_activation: no activation named '%s'", name);      // (tensor 0: the caller's own images)
     const Tensor &t = m->tensors[ti];
     if (shape) {
         shape[0] = m->max_batch; shape[1] = t.H; shape[2] = t.W; shape[3] = t.C;
@@ -1378,16 +1386,7 @@ extern "C" int rpn_model_get_activation(rpn_model *m, const char *name, float *d
     RPN_REQUIRE(m->d_arena, "rpn_model_get_activation: no forward pass has run");
     const size_t bytes = t.floats() * (size_t)m->max_batch * sizeof(float);
     RPN_REQUIRE(out_bytes >= bytes, "rpn_model_get_activation: %zu bytes needed, %zu given", bytes, out_bytes);
-    if (t.split_fmt) {
-        const hipError_t e = launch_split_to_f32(m->d_arena + t.offset * (size_t)m->max_batch,
-                                                 (long long)m->max_batch * t.H * t.W, t.C, m->f16, d_out,
-                                                 as_stream(stream));
-        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_model_get_activation: %s", hipGetErrorString(e));
-        return RPN_OK;
-    }
-    RPN_HIP_CHECK(hipMemcpyAsync(d_out, m->d_arena + t.offset * (size_t)m->max_batch, bytes,
-                                 hipMemcpyDeviceToDevice, as_stream(stream)));
-    return RPN_OK;
+    return tensor_to_f32(m, ti, tensor_ptr(m, ti, nullptr), m->max_batch, d_out, as_stream(stream), "rpn_model_get_activation");
 }
 
 // RoI pooling of the feature tap, read where the last forward left it: float32 NHWC, or the split form of the bf16x3 / f16x3 graphs
@@ -1478,8 +1477,7 @@ extern "C" int rpn_conv2d(const float *d_x, int B, int H, int W, int Cin, const 
         if (e2 != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_conv2d(split): kernel failed: %s", hipGetErrorString(e2));
         return RPN_OK;
     }
-    if (Cin == 3 && R == 3 && S == 3 && (stride == 1 || stride == 2) && Cout % 16 == 0 && Cout <= 256 &&
-        256 % (Cout / 16) == 0 && act != ACT_SIGMOID) {   // first-layer direct kernel
+    if (cin3_eligible(Cin, R, S, stride, Cout, act)) {     // first-layer direct kernel
         const hipError_t e = launch_conv_cin3(d_x, d_w, d_bias, d_out, B, H, W, OH, OW, Cout, stride, pad_t, pad_l, act,
                                               0, false, s);
         if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "rpn_conv2d(cin3): launch failed: %s", hipGetErrorString(e));
