@@ -593,6 +593,67 @@ long long rpn_det_head_steps(const rpn_det_head *h);
 int rpn_fc_forward(const float *d_a, const float *d_w, const float *d_bias, int M, int K, int N, int ldw, int relu, float *d_out,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Evaluation: PASCAL VOC average precision of the detections and the recall of the proposals, accumulated on the device (no
+ * reference counterpart: its training script stops at val_loss).  The rules are VOCdevkit's VOCevaldet; where the devkit is loose
+ * the choice is THIS PROJECT'S and is marked (*).  update / update_proposals enqueue on `stream` and return: no copy to the host,
+ * no stream or device synchronisation.  No floating-point atomics; every float64 sum has an order fixed by the counts alone, so
+ * result gives the same bits on every run.
+ *
+ * create: C classes (0 is background), room for max_images images of M detection rows each; iou_threshold in (0, 1]; top_k (n_k)
+ *   and recall_iou (n_t): HOST arrays, the cut-offs (>= 1) and IoU thresholds (in (0, 1]) of the proposal recall, at most 8 each.
+ *   2 <= C <= 65535, 1 <= M <= 4096, max_images * M <= 2^30.  All device memory -- the records, the two halves of the sort
+ *   workspace, the counters: 24 bytes per record in all -- is ONE allocation owned by the handle, made at creation (without a
+ *   device, where create, memory_bytes and every argument check still work: by the first call that finds one).
+ * update: one batch.  d_boxes (B,M,4) [y1,x1,y2,x2], d_scores (B,M), d_classes (B,M) float32 and d_valid (B,) int32 as
+ *   rpn_combined_nms returns them; d_gt_boxes (B,G,4); d_gt_labels (B,G) int32; d_gt_difficult (B,G) bytes or NULL (all zeros);
+ *   1 <= G <= 2048; M is the handle's.  d_flags (B,M) int32 or NULL: 1 TP / 0 FP / -1 not counted, for every row.
+ *   Live detections: row m of image b counts iff m < valid[b], its class is an integer in [1, C) and its score is finite and > 0.
+ *     Every other row is dropped and never indexes memory.
+ *   Ground truth: a row counts iff its label is >= 1 (0 is background, -1 padding, as rpn_roi_targets).
+ *   Matching, for a live detection of class c: jmax = the gt of label c in the same image of highest IoU -- float32
+ *     generate_iou_map arithmetic, every operation rounded on its own -- the FIRST on ties (*), a NaN never wins, difficult gts
+ *     included; jmax does not depend on which gts are taken.
+ *       no gt of that class, or iou < iou_threshold                          -> FP
+ *       iou >= iou_threshold (>=, as the devkit) and the gt is difficult     -> ignored: in neither count, does not take the gt
+ *       iou >= iou_threshold, not difficult, and FIRST in (score descending, m ascending (*)) order among the detections of the
+ *         image with the same jmax and iou >= iou_threshold                  -> TP;  any later one -> FP
+ *   npos[c] = counted, non-difficult gts of label c (labels >= C are not counted); ndet[c] = TP + FP records.
+ *   Slot of a row = (images before this batch + b) * M + m.  images + B > max_images or a bad size: RPN_ERR_INVALID, nothing
+ *   is enqueued, nothing changes.
+ * result: per class, the TP / FP records ordered by score descending, ties to the lower slot (*) (a stable sort); at rank i
+ *     precision = tp_i / (tp_i + fp_i) on cumulative counts, divided in float64; recall = tp_i / npos.
+ *   d_ap (C,)   all-point (VOC2010+): (sum over TP records t of pmax(t)) / npos, pmax(t) = the maximum precision at any rank >= t's.
+ *   d_ap11 (C,) 11-point (VOC2007): the mean over k = 0..10 of the maximum precision among ranks with 10 tp_i >= k npos, 0 if there
+ *     is none -- compared IN INTEGERS (*): it does not reproduce the np.arange(0, 1.1, 0.1) rounding of the common Python port.
+ *   npos == 0: both NaN (index 0 always); npos > 0 and no records: both 0.  The mean over classes is left to the caller.
+ *   d_npos, d_ndet (C,) int32.  d_recall (n_k,n_t) float64 = hits / n_gt, NaN when n_gt == 0; d_n_gt: one long long.  Any output
+ *   may be NULL (d_ap and d_ap11 together).  Device pointers; result synchronises nothing either.  It may be called any number
+ *   of times, between updates too.
+ * update_proposals: the RPN alone.  d_rois (B,R,4), d_valid (B,) or NULL.  For every counted, non-difficult gt (any label >= 1),
+ *   every cut-off k and threshold t: a hit iff the maximum over r < min(k, valid[b]) of IoU(roi r, gt) is >= t (no RoI: no hit);
+ *   hits[k,t] and n_gt accumulate.  Independent of update's image count.
+ * pr_curve: class c's ranking, c in [1, C): the first min(n, cap) records' score, TP flag and slot; *d_n = n = ndet[c].
+ * reset: counters and the image count to zero, on `stream`.  images: detection images counted so far (a host counter).
+ * d_boxes, d_gt_boxes, d_rois 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct rpn_evaluator rpn_evaluator;
+int rpn_evaluator_create(int C, int max_images, int M, float iou_threshold, const int *top_k, int n_k, const float *recall_iou,
+                         int n_t, rpn_evaluator **out);
+void rpn_evaluator_destroy(rpn_evaluator *e);
+int rpn_evaluator_memory_bytes(const rpn_evaluator *e, size_t *bytes);
+int rpn_evaluator_reset(rpn_evaluator *e, void *stream);
+int rpn_evaluator_images(const rpn_evaluator *e);
+int rpn_evaluator_update(rpn_evaluator *e, const float *d_boxes, const float *d_scores, const float *d_classes,
+                         const int32_t *d_valid, const float *d_gt_boxes, const int32_t *d_gt_labels,
+                         const unsigned char *d_gt_difficult, int B, int G, int32_t *d_flags, void *stream);
+int rpn_evaluator_update_proposals(rpn_evaluator *e, const float *d_rois, const int32_t *d_valid, int R, const float *d_gt_boxes,
+                                   const int32_t *d_gt_labels, const unsigned char *d_gt_difficult, int B, int G, void *stream);
+int rpn_evaluator_result(rpn_evaluator *e, double *d_ap, double *d_ap11, int32_t *d_npos, int32_t *d_ndet, double *d_recall,
+                         long long *d_n_gt, void *stream);
+int rpn_evaluator_pr_curve(rpn_evaluator *e, int c, float *d_scores, int32_t *d_tp, int32_t *d_slots, int cap, int32_t *d_n,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,16 @@ _SIGNATURES = {
     "rpn_det_head_adam_step": (ctypes.c_int, [vp] + [ctypes.c_float] * 4 + [vp]),
     "rpn_det_head_steps": (ctypes.c_longlong, [vp]),
     "rpn_fc_forward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp]),
+    "rpn_evaluator_create": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, c_int_p, ctypes.c_int, c_float_p, ctypes.c_int,
+                                            ctypes.POINTER(vp)]),
+    "rpn_evaluator_destroy": (None, [vp]),
+    "rpn_evaluator_memory_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_size_t)]),
+    "rpn_evaluator_reset": (ctypes.c_int, [vp, vp]),
+    "rpn_evaluator_images": (ctypes.c_int, [vp]),
+    "rpn_evaluator_update": (ctypes.c_int, [vp] * 8 + [ctypes.c_int] * 2 + [vp, vp]),
+    "rpn_evaluator_update_proposals": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
+    "rpn_evaluator_result": (ctypes.c_int, [vp] * 8),
+    "rpn_evaluator_pr_curve": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, vp]),
 }
 
 _lib = None
