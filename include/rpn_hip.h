@@ -577,9 +577,45 @@ int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const flo
  * rpn_fc_forward: the forward product on its own, d_out (M, N) = act(d_a (M, K) d_w (K, N; leading dimension ldw) + d_bias (N) or
  *   NULL), relu = 1: max(., 0).  K % 4 == 0, ldw % 4 == 0, ldw >= N (N itself is free: pad the rows of d_w); M free.
  * d_pooled, d_grad_pooled, d_a, d_w 16-byte aligned.
+ *
+ * The inference head in split float16 (RPN_PRECISION_F16X3; rpn_det_head_create_ex, rpn_fc_forward_x3).  For one layer
+ * out = act(x W + b), on v_mfma_f32_16x16x32_f16:
+ *   Input split: every float32 input x enters as hi = f16(x), lo = f16(x - hi), both round-to-nearest-even and unscaled (float16
+ *     subnormals are kept), whether x is a pooled feature or a hidden activation: h1 and h2 travel as float32 and are split by the
+ *     layer that reads them.
+ *   Weight split: every weight w enters as the same split of w * 2^s, ONE s per layer (fc1, fc2, cls, reg each have their own):
+ *     s = 12 - e clamped to [-100, 24] where max|w| = m 2^e, m in [0.5, 1), over that layer's kernel (0 for an all-zero kernel) --
+ *     the rule of the split convolutions.  The epilogue multiplies the accumulator by 2^-s (exact) before the bias.
+ *   Product: hi*hi + hi*lo + lo*hi with float32 accumulation inside the MFMA; lo*lo is dropped.  Then + bias and max(., 0), float32.
+ *   Order: K is walked in steps of 32 from 0; in each step the accumulator takes lo*hi, hi*lo, hi*hi in that order.  Nothing depends
+ *     on M, there is no split of K and no floating-point atomic: a row's result depends on that row, the weights and the bias only,
+ *     the same bits at M = 1 and M = 2400, beside any other rows, on every run.  K tails inside a step of 32 enter as zeros.
+ *   Range: an input with |x| > 65504 or a non-finite one (pooled features, h1, h2) raises RPN_STATUS_F16_RANGE in a device word the
+ *     head owns (rpn_det_head_status: sticky, never read back by a forward; exactly 65504 does not raise it).  The outputs of such a
+ *     forward are invalid: use the float32 head for such features.  A float32 head always reports 0.
+ *   Sizes: K % 4 == 0, N and M free, as for the float32 product.
+ *   Memory: an F16X3 head keeps its float32 weights (get_layer round-trips bit for bit) AND their packed split image, written on the
+ *     device by set_layer from the float32 copy: one 128-byte record of hi and lo halves per column and 32 rows of K, the same
+ *     bytes per weight as float32.  The image mirrors the float32 layout, so memory_bytes reports weights as TWICE the float32
+ *     head's when every layer's K is a multiple of 32 (0.96 GB at 25 088 x 4096) and the rows up to the next multiple of 32 more
+ *     otherwise; the workspace is the same.
+ *   rpn_det_head_create_ex: `precision` RPN_PRECISION_F32 (= rpn_det_head_create) or RPN_PRECISION_F16X3.  F16X3 with trainable = 1,
+ *     BF16X3 and F32W are RPN_ERR_UNSUPPORTED: training stays exact float32.  backward, adam_step and get_gradient fail on an F16X3
+ *     head as on any trainable = 0 head.
+ *   rpn_det_head_forward_layer: ONE hidden layer of the head, "fc1" or "fc2", at the head's precision on the caller's buffers,
+ *     d_out (M, H) = relu(d_in (M, K) W + b) -- what a forward launches for that layer (a timing / test hook).
+ *   rpn_fc_forward_x3: the split product on its own.  d_w is the float32 (K, ldw) matrix ON THE DEVICE; s is taken over its columns
+ *     [0, N).  A test entry like rpn_conv2d: every call finds max|w|, allocates, packs and synchronises.  d_status: a device word
+ *     that receives RPN_STATUS_F16_RANGE, or NULL.
  * ---------------------------------------------------------------------------------- */
 typedef struct rpn_det_head rpn_det_head;
 int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, rpn_det_head **out);
+int rpn_det_head_create_ex(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, int precision,
+                           rpn_det_head **out);
+int rpn_det_head_status(rpn_det_head *h, unsigned *flags, int reset, void *stream);
+int rpn_det_head_forward_layer(rpn_det_head *h, const char *name, const float *d_in, int M, float *d_out, void *stream);
+int rpn_fc_forward_x3(const float *d_a, const float *d_w, const float *d_bias, int M, int K, int N, int ldw, int relu, float *d_out,
+                      unsigned *d_status, void *stream);
 void rpn_det_head_destroy(rpn_det_head *h);
 int rpn_det_head_memory_bytes(const rpn_det_head *h, size_t *weights, size_t *workspace);
 int rpn_det_head_set_layer(rpn_det_head *h, const char *name, const float *kernel, const float *bias);

@@ -3,15 +3,18 @@ by round (median and minimum over the rounds), at the VGG16 (7 x 7 x 512) and Mo
 widths 4096 and 1024:
 
     head forward     rpn_det_head_forward (keep = 1): fc1, fc2, cls | reg
+    head forward f16x3  the same forward on an inference copy of the head at precision "f16x3" (split float16 on the 16-bit MFMA)
     head backward    rpn_det_head_backward with the gradient of the pooled features
     head adam        rpn_det_head_adam_step (one launch over all eight tensors)
     torch fwd+bwd+adam  the same four layers as torch.nn.Linear, float32, forward + backward (to the input) + torch.optim.Adam
     fc1 rpn_fc_forward  the first layer alone on the new GEMM (bias, no activation), with its TFLOP/s
+    fc1 f16x3 (packed)  the first layer of the f16x3 head on its packed weights (rpn_det_head_forward_layer: bias and ReLU), events
+                        around that one launch -- not the re-packing test entry rpn_fc_forward_x3
     fc1 torch.addmm     the same product through torch
     fc1 rpn_conv2d      the same product as a 1 x 1 conv on an (M, 1, 1, K) tensor: the library's way before rpn_fc_forward existed
                         (a single-layer test entry: every call allocates, packs the kernel for its tiles and synchronises)
 
-Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
+Also reports max |f16x3 - f32| of the logits and deltas on the benchmark's inputs.  Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
     python scripts/det_head_bench.py [--rounds 5] [--iters 3] [--json PATH]
 """
 import argparse
@@ -101,7 +104,25 @@ def bench_config(lib, channels, hidden, rounds, iters):
         L.check(lib.rpn_conv2d(L.ptr(x2), M, 1, 1, K1, L.ptr(w1), L.ptr(b1), 1, 1, hidden, 1, 0, 0, 1, 1, 0, 0, L.ptr(out), stream),
                 "rpn_conv2d")
 
-    variants = {"head forward": fwd, "head backward": bwd, "head adam": adam, "torch fwd+bwd+adam": torch_step, "fc1 rpn_fc_forward": fc_new,
+    # the f16x3 inference head with the same weights
+    head_x3 = head.inference_copy(precision="f16x3")
+    logits_x3, deltas_x3 = torch.empty_like(logits), torch.empty_like(deltas)
+    out_x3 = torch.empty((M, hidden), device="cuda")
+
+    def fwd_x3():
+        L.check(lib.rpn_det_head_forward(head_x3._h, L.ptr(pooled), M, 0, L.ptr(logits_x3), L.ptr(deltas_x3), stream), "forward f16x3")
+
+    def fc_x3():
+        L.check(lib.rpn_det_head_forward_layer(head_x3._h, b"fc1", L.ptr(x2), M, L.ptr(out_x3), stream), "forward_layer f16x3")
+
+    fwd()
+    fwd_x3()
+    torch.cuda.synchronize()
+    diff = {"logits": float((logits_x3 - logits).abs().max()), "deltas": float((deltas_x3 - deltas).abs().max()),
+            "max_abs_logits": float(logits.abs().max()), "max_abs_deltas": float(deltas.abs().max()),
+            "f16_range": head_x3.status()["f16_range"]}
+
+    variants = {"head forward f16x3": fwd_x3, "fc1 f16x3 (packed)": fc_x3, "head forward": fwd, "head backward": bwd, "head adam": adam, "torch fwd+bwd+adam": torch_step, "fc1 rpn_fc_forward": fc_new,
                 "fc1 torch.addmm": fc_torch}
     fwd()                                                       # the backward needs a kept forward; every timed backward reuses the last one
     conv_note = None
@@ -113,13 +134,18 @@ def bench_config(lib, channels, hidden, rounds, iters):
         variants["fc1 rpn_conv2d"] = fc_conv
     except (ValueError, RuntimeError) as e:
         conv_note = "rpn_conv2d refuses this shape: %s" % e
-    order = ["head forward", "head backward", "head adam", "torch fwd+bwd+adam", "fc1 rpn_fc_forward", "fc1 torch.addmm", "fc1 rpn_conv2d"]
+    order = ["head forward", "head forward f16x3", "head backward", "head adam", "torch fwd+bwd+adam", "fc1 rpn_fc_forward",
+             "fc1 f16x3 (packed)", "fc1 torch.addmm", "fc1 rpn_conv2d"]
     variants = {n: variants[n] for n in order if n in variants}
     res = time_variants(variants, rounds, iters)
     flop1 = 2.0 * M * K1 * hidden
     tf = {n: flop1 / (res[n][0] * 1e-6) / 1e12 for n in res if n.startswith("fc1")}
     w_bytes, ws_bytes = head.memory_bytes()
-    return dict(us_median_min=res, fc1_tflops=tf, conv_note=conv_note, weights_bytes=w_bytes, workspace_bytes=ws_bytes)
+    x3_bytes = head_x3.memory_bytes()
+    return dict(us_median_min=res, fc1_tflops=tf, conv_note=conv_note, weights_bytes=w_bytes, workspace_bytes=ws_bytes,
+                f16x3_weights_bytes=x3_bytes[0], f16x3_workspace_bytes=x3_bytes[1], f16x3_minus_f32=diff,
+                f16x3_forward_speedup=res["head forward"][0] / res["head forward f16x3"][0],
+                f16x3_fc1_speedup=res["fc1 rpn_fc_forward"][0] / res["fc1 f16x3 (packed)"][0])
 
 
 def main():
@@ -142,6 +168,11 @@ def main():
             tf = row["fc1_tflops"].get(name)
             print("%-32s %-20s %12.1f %12.1f %10s" % (label, name, v[0], v[1], "%.1f" % tf if tf else ""))
         print("%-32s %s" % (label, row["conv_note"]))
+        d = row["f16x3_minus_f32"]
+        print("%-32s f16x3 / f32: head forward %.2fx, fc1 %.2fx; max |f16x3 - f32| logits %.3e (max |logit| %.3e), deltas %.3e (max "
+              "|delta| %.3e); range flag %s; f16x3 head weights %.0f MB" % (label, row["f16x3_forward_speedup"], row["f16x3_fc1_speedup"],
+                                                                          d["logits"], d["max_abs_logits"], d["deltas"], d["max_abs_deltas"],
+                                                                          d["f16_range"], row["f16x3_weights_bytes"] / 1e6))
     print("float32 matrix peak %.1f TFLOP/s; untuned LDS-tiled f32 MFMA GEMM (4096^3) %.1f TFLOP/s" % (PEAK_TF, GUIDE_TF))
     line = json.dumps({"B": B, "R": R, "C": C, "rounds": args.rounds, "iters": args.iters, "peak_tflops": PEAK_TF, "guide_tflops": GUIDE_TF,
                        "results": results})

@@ -135,6 +135,10 @@ _SIGNATURES = {
     "rpn_det_head_adam_step": (ctypes.c_int, [vp] + [ctypes.c_float] * 4 + [vp]),
     "rpn_det_head_steps": (ctypes.c_longlong, [vp]),
     "rpn_fc_forward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp]),
+    "rpn_det_head_create_ex": (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(vp)]),
+    "rpn_det_head_status": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_int, vp]),
+    "rpn_det_head_forward_layer": (ctypes.c_int, [vp, ctypes.c_char_p, vp, ctypes.c_int, vp, vp]),
+    "rpn_fc_forward_x3": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
     "rpn_evaluator_create": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, c_int_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                             ctypes.POINTER(vp)]),
     "rpn_evaluator_destroy": (None, [vp]),

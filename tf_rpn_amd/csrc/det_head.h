@@ -1,7 +1,9 @@
 // det_head.h -- host-side interface of the detection head's own kernels (det_head_kernels.hip; internal to librpn_hip.so): the
 // fully-connected forward GEMM on the float32 MFMA and the two small element-wise kernels of the head's backward.  The weight and
 // input gradients run on train_mnv2.h's launch_conv1x1_wgrad / launch_conv1x1_dgrad, the bias gradients on train_head.h's
-// launch_colsum and the update on train_head.h's launch_adam.  Every kernel is float32, writes each output once and uses no atomics.
+// launch_colsum and the update on train_head.h's launch_adam.  Those kernels are float32, write each output once and use no atomics.
+// The inference head's split-float16 forward (det_head_x3_kernels.hip) is declared below them: no floating-point atomics either
+// (its range flag is an atomicOr on a status word, the test entry's max|w| an integer atomicMax).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +18,24 @@ namespace rpn {
 // it: a row's bits depend on that row of a, on w and on bias alone.
 hipError_t launch_fc_forward(const float *a, const float *w, const float *bias, int M, int K, int N, int ldw, int relu, int split,
                              float *out0, float *out1, hipStream_t s);
+
+// ---- the same product in split float16 (det_head_x3_kernels.hip; arithmetic contract in include/rpn_hip.h) ----------------------------
+// Packed image of a (K, ld) float32 matrix times 2^shift: [ceil(K / 32)][ld][8 pieces of 16 bytes] -- for column n and 32 rows of K
+// the logical pieces are hi k 0-7, hi k 8-15, hi k 16-23, hi k 24-31, lo k 0-7, ..., lo k 24-31 (float16), piece p stored at slot
+// p ^ (n / 2 % 8): the kernel's LDS image, copied as it is.  Rows beyond K are zeros.  The same bytes per weight as float32.
+inline size_t fc_x3_packed_bytes(int K, int ld) { return (size_t)((K + 31) / 32) * (size_t)ld * 128; }
+
+// packs columns [c0, c0 + ncols) of w (K, ld; float32 on the device) into `packed`; the other columns of the image are left alone
+hipError_t launch_fc_pack_x3(const float *w, int K, int ld, int c0, int ncols, int shift, void *packed, hipStream_t s);
+
+// *out_bits = max over rows < K, columns < N of the bits of |w| (non-negative floats order as their bits; NaNs are skipped);
+// *out_bits must be zero before the call
+hipError_t launch_fc_absmax(const float *w, int K, int N, int ld, unsigned *out_bits, hipStream_t s);
+
+// out = act(scale * (a . packed) + bias), `scale` = scale0 for columns < split and scale1 for the others (2^-shift of the packing);
+// the rest as launch_fc_forward, ld % 4 == 0 being the image's column count.  status: the float16 range flag, or null.
+hipError_t launch_fc_forward_x3(const float *a, const void *packed, const float *bias, int M, int K, int N, int ld, int relu, int split,
+                                float scale0, float scale1, float *out0, float *out1, unsigned *status, hipStream_t s);
 
 // dz (M, npad) = [grad_logits (M, C) | grad_deltas (M, 4 C) | zeros]: the gradient of the padded cls | reg product
 hipError_t launch_pack_pair_grad(const float *grad_logits, const float *grad_deltas, int M, int C, int npad, float *dz, hipStream_t s);

@@ -1,10 +1,12 @@
 // det_head_kernels.hip -- the detection head: two fully-connected ReLU layers on the flattened RoI features and the cls | reg output
 // pair (rpn_det_head_*, rpn_fc_forward; contract in include/rpn_hip.h).  New here: the forward GEMM (fc_forward_f32_kernel) and two
-// small element-wise kernels.  The backward reuses the 1x1-conv backward GEMMs (train_mnv2.h), the column sums and Adam
+// small element-wise kernels; the split-float16 forward of the inference head (RPN_PRECISION_F16X3) has its kernels in
+// det_head_x3_kernels.hip and its host side here.  The backward reuses the 1x1-conv backward GEMMs (train_mnv2.h), the column sums and Adam
 // (train_head.h) unchanged; after each input-gradient GEMM one in-place pass applies the ReLU mask (launch_relu_mask).
 #include <cstdint>
 #include <cstring>
 
+#include "conv_kernels.h"
 #include "det_head.h"
 #include "rpn_common.h"
 #include "train_common.h"
@@ -189,6 +191,14 @@ struct rpn_det_head {
     int kept_rows = 0;           // rows of the forward whose activations the backward may read; 0: none
     const float *kept_pooled = nullptr;   // ... and that forward's input: the backward must be handed the same tensor
     long long t = 0;
+    // RPN_PRECISION_F16X3 (inference heads only): beside w, the packed split image of the three weight matrices.  It mirrors w's layout
+    // -- W1 | (b1) | W2 | (b2) | Wp | (bp), every matrix with its rows rounded up to 32 and the bias slots unused -- so that it is as
+    // large as w when every K is a multiple of 32.  shift[i]: layer i's power-of-two pre-scale; status: the float16 range flag.
+    int precision = RPN_PRECISION_F32;
+    unsigned char *wx = nullptr;
+    unsigned *status = nullptr;
+    size_t xoff[3] = {0, 0, 0}, xbytes = 0;   // byte offsets of W1, W2, Wp in wx; its size
+    int shift[4] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -235,6 +245,9 @@ void head_free(rpn_det_head *h)
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
+    if (h->wx) (void)hipFree(h->wx);
+    if (h->status) (void)hipFree(h->status);
+    h->wx = nullptr, h->status = nullptr;
     h->loaded = 0;               // the weights went with the buffers
     h->kept_rows = 0;
 }
@@ -260,6 +273,16 @@ int head_ensure_device(rpn_det_head *h)
                         hipGetErrorString(e));
         }
     }
+    if (h->precision == RPN_PRECISION_F16X3) {
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->wx), h->xbytes);
+        if (e == hipSuccess) e = hipMemset(h->wx, 0, h->xbytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->status), sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemset(h->status, 0, sizeof(unsigned));
+        if (e != hipSuccess) {
+            head_free(h);
+            return fail(RPN_ERR_NO_DEVICE, "rpn_det_head: device allocation of %zu bytes failed: %s", h->xbytes, hipGetErrorString(e));
+        }
+    }
     return RPN_OK;
 }
 
@@ -280,11 +303,40 @@ int head_copy_layer(rpn_det_head *h, float *base, const char *name, float *kerne
     return RPN_OK;
 }
 
+// F16X3: layer i's pre-scale from the host kernel, then its columns of the packed image from the float32 copy on the device
+int head_pack_layer(rpn_det_head *h, int i, const float *kernel)
+{
+    const LayerView lv = layer_view(h, i);
+    const int mat = i < 2 ? i : 2;                               // cls and reg share the pair's matrix: columns [0, C) and [C, 5 C)
+    h->shift[i] = split_weight_shift(kernel, (size_t)lv.rows * lv.cols, true);
+    RPN_HIP_CHECK(launch_fc_pack_x3(h->w + h->off[2 * mat], lv.rows, lv.ld, i == 3 ? h->c : 0, lv.cols, h->shift[i], h->wx + h->xoff[mat],
+                                    nullptr));
+    RPN_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return RPN_OK;
+}
+
+// one product of the head at its precision: layer 0 (fc1), 1 (fc2) or 2 (the cls | reg pair; out0 / out1)
+hipError_t head_launch_layer(rpn_det_head *h, int mat, const float *in, int M, float *out0, float *out1, hipStream_t s)
+{
+    const int K = mat == 0 ? h->k1 : mat == 1 ? h->h1 : h->h2, N = mat == 0 ? h->h1 : mat == 1 ? h->h2 : 5 * h->c;
+    const int ld = mat == 2 ? h->npad : N, relu = mat == 2 ? 0 : 1, split = mat == 2 ? h->c : N;
+    const float *w = h->w + h->off[2 * mat], *b = h->w + h->off[2 * mat + 1];
+    if (h->precision != RPN_PRECISION_F16X3) return launch_fc_forward(in, w, b, M, K, N, ld, relu, split, out0, out1, s);
+    return launch_fc_forward_x3(in, h->wx + h->xoff[mat], b, M, K, N, ld, relu, split, ldexpf(1.0f, -h->shift[mat]),
+                                ldexpf(1.0f, -h->shift[mat == 2 ? 3 : mat]), out0, out1, h->status, s);
+}
+
 }  // namespace
 
 extern "C" int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, rpn_det_head **out)
 {
-    const char *who = "rpn_det_head_create";
+    return rpn_det_head_create_ex(ph, pw, Cf, H1, H2, C, max_rows, trainable, RPN_PRECISION_F32, out);
+}
+
+extern "C" int rpn_det_head_create_ex(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, int precision,
+                                      rpn_det_head **out)
+{
+    const char *who = "rpn_det_head_create_ex";
     RPN_REQUIRE(out, "%s: null out", who);
     *out = nullptr;
     RPN_REQUIRE(ph >= 1 && pw >= 1, "%s: pooling size %d x %d", who, ph, pw);
@@ -299,7 +351,14 @@ extern "C" int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C
                 "%s: %d x %d x %d = %lld features, H1 = %d, H2 = %d: a layer's input may be at most %lld wide (one weight-gradient launch)", who,
                 ph, pw, Cf, k1, H1, H2, kHeadMaxWidth);
     RPN_REQUIRE(max_rows <= kHeadMaxRows, "%s: max_rows = %d, at most %lld rows fit one input-gradient launch", who, max_rows, kHeadMaxRows);
+    RPN_REQUIRE(precision == RPN_PRECISION_F32 || precision == RPN_PRECISION_BF16X3 || precision == RPN_PRECISION_F16X3 ||
+                    precision == RPN_PRECISION_F32W, "%s: precision = %d is no rpn_precision value", who, precision);
+    if (precision == RPN_PRECISION_BF16X3 || precision == RPN_PRECISION_F32W)
+        return fail(RPN_ERR_UNSUPPORTED, "%s: the head computes in RPN_PRECISION_F32 or RPN_PRECISION_F16X3, not in precision %d", who, precision);
+    if (precision == RPN_PRECISION_F16X3 && trainable)
+        return fail(RPN_ERR_UNSUPPORTED, "%s: RPN_PRECISION_F16X3 is the inference head's (trainable = 0): training stays exact float32", who);
     rpn_det_head *h = new rpn_det_head();
+    h->precision = precision;
     h->ph = ph, h->pw = pw, h->cf = Cf, h->h1 = H1, h->h2 = H2, h->c = C, h->max_rows = max_rows, h->trainable = trainable;
     h->k1 = (int)k1, h->npad = npad;
     const size_t sizes[6] = {(size_t)k1 * H1, (size_t)H1, (size_t)H1 * H2, (size_t)H2, (size_t)H2 * npad, (size_t)npad};
@@ -307,6 +366,14 @@ extern "C" int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C
     for (int i = 0; i < 6; ++i) {
         h->off[i] = h->n;
         h->n += sizes[i];
+    }
+    if (precision == RPN_PRECISION_F16X3) {
+        const size_t xs[6] = {fc_x3_packed_bytes(h->k1, H1), sizes[1] * sizeof(float), fc_x3_packed_bytes(H1, H2), sizes[3] * sizeof(float),
+                              fc_x3_packed_bytes(H2, npad), sizes[5] * sizeof(float)};
+        for (int i = 0; i < 6; ++i) {
+            if (i % 2 == 0) h->xoff[i / 2] = h->xbytes;
+            h->xbytes += xs[i];
+        }
     }
     const long long R = max_rows;
     h->part_floats = std::max({conv1x1_wgrad_ws_floats(R, h->k1, H1), conv1x1_wgrad_ws_floats(R, H1, H2), conv1x1_wgrad_ws_floats(R, H2, npad),
@@ -325,7 +392,7 @@ extern "C" void rpn_det_head_destroy(rpn_det_head *h)
 extern "C" int rpn_det_head_memory_bytes(const rpn_det_head *h, size_t *weights, size_t *workspace)
 {
     RPN_REQUIRE(h && weights && workspace, "rpn_det_head_memory_bytes: null pointer");
-    *weights = h->n * sizeof(float) * (h->trainable ? 4 : 1);
+    *weights = h->n * sizeof(float) * (h->trainable ? 4 : 1) + h->xbytes;
     *workspace = head_workspace_bytes(h);
     return RPN_OK;
 }
@@ -340,6 +407,7 @@ extern "C" int rpn_det_head_set_layer(rpn_det_head *h, const char *name, const f
     if (st != RPN_OK) return st;
     h->kept_rows = 0;            // a kept forward was made with the weights this call replaces
     st = head_copy_layer(h, h->w, name, const_cast<float *>(kernel), const_cast<float *>(bias), true, nullptr);
+    if (st == RPN_OK && h->precision == RPN_PRECISION_F16X3) st = head_pack_layer(h, i, kernel);
     if (st == RPN_OK) h->loaded |= 1u << i;
     return st;
 }
@@ -381,12 +449,39 @@ extern "C" int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int 
     if (st != RPN_OK) return st;
     const hipStream_t s = as_stream(stream);
     h->kept_rows = 0;                    // the activations of an earlier forward are overwritten from here on
-    hipError_t e = launch_fc_forward(d_pooled, h->w + h->off[0], h->w + h->off[1], M, h->k1, h->h1, h->h1, 1, h->h1, h->a1, nullptr, s);
-    if (e == hipSuccess) e = launch_fc_forward(h->a1, h->w + h->off[2], h->w + h->off[3], M, h->h1, h->h2, h->h2, 1, h->h2, h->a2, nullptr, s);
-    if (e == hipSuccess)
-        e = launch_fc_forward(h->a2, h->w + h->off[4], h->w + h->off[5], M, h->h2, 5 * h->c, h->npad, 0, h->c, d_logits, d_deltas, s);
+    hipError_t e = head_launch_layer(h, 0, d_pooled, M, h->a1, nullptr, s);
+    if (e == hipSuccess) e = head_launch_layer(h, 1, h->a1, M, h->a2, nullptr, s);
+    if (e == hipSuccess) e = head_launch_layer(h, 2, h->a2, M, d_logits, d_deltas, s);
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
     if (keep) h->kept_rows = M, h->kept_pooled = d_pooled;
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_forward_layer(rpn_det_head *h, const char *name, const float *d_in, int M, float *d_out, void *stream)
+{
+    const char *who = "rpn_det_head_forward_layer";
+    RPN_REQUIRE(h && name && d_in && d_out, "%s: null pointer", who);
+    const int i = layer_index(name);
+    RPN_REQUIRE(i == 0 || i == 1, "%s: layer '%s' is not a hidden layer (fc1, fc2)", who, name);
+    RPN_REQUIRE(M >= 1 && M <= kFcMaxRows, "%s: M = %d (1 .. %lld)", who, M, kFcMaxRows);
+    RPN_REQUIRE(aligned16(d_in), "%s: the input must be 16-byte aligned", who);
+    RPN_REQUIRE(h->loaded >> i & 1u, "%s: layer '%s' was never set", who, name);
+    const int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    const hipError_t e = head_launch_layer(h, i, d_in, M, d_out, nullptr, as_stream(stream));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_status(rpn_det_head *h, unsigned *flags, int reset, void *stream)
+{
+    RPN_REQUIRE(h && flags, "rpn_det_head_status: null pointer");
+    *flags = 0;
+    if (!h->status) return RPN_OK;           // a float32 head, or an F16X3 head that has not touched the device yet
+    const hipStream_t s = as_stream(stream);
+    RPN_HIP_CHECK(hipMemcpyAsync(flags, h->status, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (reset) RPN_HIP_CHECK(hipMemsetAsync(h->status, 0, sizeof(unsigned), s));
+    RPN_HIP_CHECK(hipStreamSynchronize(s));
     return RPN_OK;
 }
 
@@ -454,6 +549,40 @@ extern "C" int rpn_fc_forward(const float *d_a, const float *d_w, const float *d
     RPN_REQUIRE(aligned16(d_a) && aligned16(d_w), "%s: a and w must be 16-byte aligned", who);
     RPN_REQUIRE_DEVICE();
     const hipError_t e = launch_fc_forward(d_a, d_w, d_bias, M, K, N, ldw, relu, N, d_out, nullptr, as_stream(stream));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}
+
+extern "C" int rpn_fc_forward_x3(const float *d_a, const float *d_w, const float *d_bias, int M, int K, int N, int ldw, int relu,
+                                 float *d_out, unsigned *d_status, void *stream)
+{
+    const char *who = "rpn_fc_forward_x3";
+    RPN_REQUIRE(d_a && d_w && d_out, "%s: null pointer", who);
+    RPN_REQUIRE(M >= 1 && M <= kFcMaxRows && N >= 1, "%s: M = %d (1 .. %lld), N = %d", who, M, kFcMaxRows, N);
+    RPN_REQUIRE(K >= 4 && K % 4 == 0, "%s: K = %d must be a positive multiple of 4", who, K);
+    RPN_REQUIRE(ldw >= N && ldw % 4 == 0, "%s: ldw = %d must be a multiple of 4 and >= N = %d", who, ldw, N);
+    RPN_REQUIRE(relu == 0 || relu == 1, "%s: relu must be 0 or 1", who);
+    RPN_REQUIRE(aligned16(d_a) && aligned16(d_w), "%s: a and w must be 16-byte aligned", who);
+    RPN_REQUIRE((reinterpret_cast<uintptr_t>(d_status) & 3u) == 0, "%s: the status word must be 4-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const hipStream_t s = as_stream(stream);
+    // a test entry: max|w| over the columns [0, N), the packed image and the product, with a host round trip in between
+    const size_t pbytes = fc_x3_packed_bytes(K, ldw);
+    unsigned char *buf = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&buf), a256(pbytes) + 256);
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: device allocation of %zu bytes failed: %s", who, pbytes, hipGetErrorString(e));
+    unsigned *d_max = reinterpret_cast<unsigned *>(buf + a256(pbytes));
+    float mx = 0.0f;
+    e = hipMemsetAsync(d_max, 0, sizeof(unsigned), s);
+    if (e == hipSuccess) e = launch_fc_absmax(d_w, K, N, ldw, d_max, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&mx, d_max, sizeof(float), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const int shift = split_weight_shift(&mx, 1, true);
+    if (e == hipSuccess) e = launch_fc_pack_x3(d_w, K, ldw, 0, ldw, shift, buf, s);
+    const float scale = ldexpf(1.0f, -shift);
+    if (e == hipSuccess) e = launch_fc_forward_x3(d_a, buf, d_bias, M, K, N, ldw, relu, N, scale, scale, d_out, nullptr, d_status, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(buf);
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
     return RPN_OK;
 }

@@ -10,6 +10,12 @@ Fast R-CNN head), as the thresholds of ``calculate_roi_targets`` are:
 
 Kernels are Keras ``Dense`` kernels, (in, out).  There is no dropout: every training entry point of this library gives the same
 bits on every run, and so does this one.  Exact float32; a RoI's outputs do not depend on the batch it is part of.
+
+``precision="f16x3"`` (inference heads only) runs the three products on the float16 matrix cores with every float32 operand
+carried as hi + lo float16 halves (``hi*hi + hi*lo + lo*hi``, float32 accumulation; the contract is in ``include/rpn_hip.h``):
+the same batch independence and run-to-run bit identity, an error a little above float32's, and twice the weight memory (the
+float32 weights are kept beside their packed image).  Features or activations beyond the float16 range raise a flag
+(``status()``); the outputs of such a forward are invalid and the float32 head is the one to use.
 """
 import ctypes
 
@@ -20,6 +26,7 @@ from .. import _lib as L
 from ..utils import roi_utils
 
 LAYERS = ("fc1", "fc2", "cls", "reg")
+PRECISIONS = ("f32", "f16x3")
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -64,10 +71,19 @@ class DetectionHead(object):
     another call's activations.  Each backward REPLACES the stored parameter gradients; they do not accumulate over calls, so
     it is one forward, one backward, one ``apply_gradients``.  Under ``torch.no_grad()`` nothing is kept.  ``trainable=False`` is the inference head: weights and the two hidden activations only.
 
-    Initial weights are Keras' ``Dense`` defaults, Glorot-uniform kernels and zero biases, drawn from ``seed``."""
+    ``precision``: ``"f32"`` (exact float32, the default) or ``"f16x3"`` (split float16 on the 16-bit matrix cores; needs
+    ``trainable=False``: training stays exact float32).  ``head.precision`` reports it.
+
+    Initial weights are Keras' ``Dense`` defaults, Glorot-uniform kernels and zero biases, drawn from ``seed``; ``seed=None`` sets
+    none (every layer must then be given with ``set_weights`` before the first call)."""
 
     def __init__(self, total_labels, pooling_size=(7, 7), channels=512, hidden=(4096, 4096), max_rois=8 * 300, trainable=True,
-                 seed=0):
+                 seed=0, precision="f32"):
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %r, got %r" % (PRECISIONS, precision))
+        if precision == "f16x3" and trainable:
+            raise ValueError("precision 'f16x3' is the inference head's: pass trainable=False (training stays exact float32)")
+        self.precision = precision
         self.total_labels = int(total_labels)
         self.pooling_size = tuple(int(v) for v in pooling_size)
         self.channels, self.hidden = int(channels), tuple(int(v) for v in hidden)
@@ -76,8 +92,8 @@ class DetectionHead(object):
             raise ValueError("pooling_size and hidden must have two entries each, got %r and %r" % (pooling_size, hidden))
         ph, pw = self.pooling_size
         h = L.vp(0)
-        L.check(L.lib().rpn_det_head_create(ph, pw, self.channels, self.hidden[0], self.hidden[1], self.total_labels, self.max_rois,
-                                            int(self.trainable), ctypes.byref(h)), "rpn_det_head_create")
+        L.check(L.lib().rpn_det_head_create_ex(ph, pw, self.channels, self.hidden[0], self.hidden[1], self.total_labels, self.max_rois,
+                                               int(self.trainable), L.PRECISIONS[precision], ctypes.byref(h)), "rpn_det_head_create")
         self._h = h
         self.features = ph * pw * self.channels
         C = self.total_labels
@@ -87,7 +103,8 @@ class DetectionHead(object):
         self._token = None
         self._serial = 0                         # counts what invalidates a kept forward: calls, set_weights, apply_gradients
         self.compile()
-        if torch.cuda.is_available():          # (without a device the object still answers shape and memory questions)
+        if torch.cuda.is_available() and seed is not None:   # (without a device the object still answers shape and memory questions;
+            # seed=None: the caller sets every layer itself)
             self.set_weights(self.initial_weights(seed))
 
     def __del__(self):
@@ -153,6 +170,25 @@ class DetectionHead(object):
     def get_gradients(self):
         """{layer: {"kernel", "bias"}}: the parameter gradients the last backward left in the head"""
         return self._get(L.lib().rpn_det_head_get_gradient, "rpn_det_head_get_gradient")
+
+    def inference_copy(self, precision="f32"):
+        """a new inference head (``trainable=False``) of the same shape at ``precision`` holding this head's current weights"""
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %r, got %r" % (PRECISIONS, precision))
+        weights = self.get_weights()
+        head = DetectionHead(self.total_labels, pooling_size=self.pooling_size, channels=self.channels, hidden=self.hidden,
+                             max_rois=self.max_rois, trainable=False, seed=None, precision=precision)
+        head.set_weights(weights)
+        return head
+
+    def status(self, reset=False):
+        """Sticky flags raised on the device by the forwards so far -> {"f16_range": bool}.  ``f16_range`` (``precision="f16x3"``
+        only; a float32 head always reports False): a pooled feature or a hidden activation did not fit float16 (|x| > 65504 or
+        non-finite), the outputs of that forward are invalid -- use the float32 head.  Synchronises the current stream."""
+        flags = ctypes.c_uint(0)
+        stream = L.stream_ptr() if torch.cuda.is_available() else None     # (without a device there is no flag either)
+        L.check(L.lib().rpn_det_head_status(self._h, ctypes.byref(flags), 1 if reset else 0, stream), "rpn_det_head_status")
+        return {"f16_range": bool(flags.value & L.STATUS_F16_RANGE)}
 
     def save_weights(self, path):
         """a flat ``.npz`` with keys ``<layer>/<param>``, the form ``RPNModel.save_weights`` writes"""
