@@ -43,7 +43,7 @@ def run(B, H, Cin, Cout, reps=3):
         o = idx[np.argsort(s[idx, 0])]
         for a_, b_ in zip(o[:-1], o[1:]):
             gaps.append(s[b_, 0] - s[a_, 3])
-    gaps = np.array(gaps)
+    gaps = np.array(gaps if gaps else [0])               # (persistent kernel: one workgroup per CU, no successor)
     print("  distinct (xcc,se,sh,cu) keys %d; gap between a workgroup's end and the next start on the same key: median %d [p10 %d p90 %d]" % (
         len(np.unique(key)), np.median(gaps), *np.percentile(gaps, [10, 90])))
     print("  start-time waves (cycles since first start): p25 %d p50 %d p75 %d max %d" % tuple(np.percentile(start, [25, 50, 75, 100])))
@@ -51,3 +51,12 @@ import sys as _s
 cfgs = [tuple(int(v) for v in a.split(',')) for a in _s.argv[1:]] or [(8, 125, 256, 256), (8, 250, 128, 128)]
 for cfg in cfgs:
     run(*cfg)
+# which waves of a workgroup share a SIMD (HW_ID bits 5:4) -- the persistent kernel's workgroups 0..63 of the last launch
+hw = np.zeros(64 * 16, dtype=np.uint32)
+if not hasattr(raw, "rpn_debug_read_wave_hwid"):      # (a stamp build from before the per-wave record)
+    sys.exit(0)
+raw.rpn_debug_read_wave_hwid.argtypes = [ctypes.c_void_p, ctypes.c_int]
+assert raw.rpn_debug_read_wave_hwid(hw.ctypes.data, hw.size) == 0
+simd = ((hw.reshape(64, 16)[:, :8] >> 4) & 3)
+print("SIMD of waves 0..7, workgroup 0: %s; workgroups (of 64) where wave w and w + 4 share a SIMD for every w: %d" % (
+    simd[0].tolist(), int((simd[:, :4] == simd[:, 4:]).all(axis=1).sum())))

@@ -67,7 +67,19 @@ extern "C" int rpn_debug_read_stamps(unsigned long long *out, int n)
 {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rpn_stamps), (size_t)n * 8);
 }
+// HW_ID of every wave of the first 64 workgroups (which waves of a workgroup share a SIMD): [workgroup][wave]
+__device__ unsigned g_rpn_wave_hwid[64 * 16];
+#define RPN_STAMP_WAVE_HWID()                                                                              \
+    do {                                                                                                   \
+        if ((threadIdx.x & 63) == 0 && blockIdx.x < 64)                                                    \
+            g_rpn_wave_hwid[blockIdx.x * 16 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_getreg((31 << 11) | 4); \
+    } while (0)
+extern "C" int rpn_debug_read_wave_hwid(unsigned *out, int n)
+{
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rpn_wave_hwid), (size_t)n * 4);
+}
 #else
+#define RPN_STAMP_WAVE_HWID() ((void)0)
 #define RPN_STAMP_AT(k) ((void)0)
 #define RPN_STAMP_VAL(k, v) ((void)0)
 #endif
@@ -980,7 +992,8 @@ conv3x3_split16_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tiles)
 //   * `buffer_load ... lds` (global -> LDS, no registers, no ds_write): one barrier per TAP and no exposed store phase
 //     (before: 62 KB of ds_write_b128 at ~79 B/clk/CU between the two barriers of every filter row).  The weights of
 //     tap t+3 are DMA'd into a 3-slot ring while tap t computes; the halo tile of the next slice in 6 pieces per wave
-//     during taps 0..5 of the current slice (other halo buffer).
+//     during taps 0..5 of the current slice (other halo buffer).  A wave issues them in the MIDDLE of its interval, behind
+//     MFMAs, not at the head where all eight waves stood in front of their first MFMA together ("Issue sites" in the kernel).
 //   * the MFMA fragments of tap t+1 are read into a second register set during tap t (one read behind each of the 16
 //     chain-head MFMAs), so the matrix pipe does not wait for LDS behind a barrier.
 //   * persistent workgroups (one per CU) walk the tiles of their XCD: the tap stream simply continues into the next
@@ -1131,24 +1144,29 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
     const int w_tap_bytes = a.cout_pad * 128;
 
     // halo DMA: wave-instruction k = j * 8 + wave fills LDS pieces [64k, 64k + 64); piece e = pixel * 8 + physical slot.
-    // The source offset is recomputed at each use (top of an interval, where register pressure is lowest; ~25 VALU
-    // operations against the interval's 48 MFMAs) instead of living in 6 registers through the whole kernel.
+    // The six source offsets of a tile's halo (a_goff) are computed once per tile: in the prologue, and for the next tile at tap 9
+    // of the last slice, at the halo piece's issue site (RPN_DMA_HALO: behind MFMA 4 NJ of half 1; ~25 VALU operations each).
 #define halo_goff(J, IM, Y0, X0) halo_source_offset<NW, A_INSTR, HP * PPP>((J), wave, lane, (IM), (Y0), (X0), a.H, a.W, in_pix_stride)
     const unsigned b_voff = (unsigned)(((B_PER_WAVE * wave) * 64 + lane) * 16);   // this wave's share of a tap's weights
 
-#define RPN_DMA_A(J, GOFF, SOFF, BUF)                                                                             \
+    // (WV: the wave's index -- `wave`, or an opaque copy of it where the LDS address is to be computed at the DMA and not kept
+    // in a scalar register of its own through the kernel: 15 such addresses otherwise)
+#define RPN_DMA_A(J, GOFF, SOFF, BUF, WV)                                                                         \
     {                                                                                                             \
-        const int k0_ = (J) * NW + wave, k_ = k0_ < A_INSTR ? k0_ : k0_ - A_INSTR;   /* surplus: a duplicate */         \
+        const int k0_ = (J) * NW + (WV), k_ = k0_ < A_INSTR ? k0_ : k0_ - A_INSTR;   /* surplus: a duplicate */         \
         u32x4 *dst_ = As + (BUF) * A1_AT + k_ * 64;                                                               \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, RPN_LDS_PTR(dst_), 16, (GOFF), (SOFF), 0, 0);             \
     }
+#define RPN_DMA_B1(SOFF, SLOT, PIECE, WV)    /* piece PIECE (0 | 1) of this wave's share of a tap's weights */      \
+    {                                                                                                             \
+        u32x4 *dst_ = Bs + (SLOT) * BSLOT + (B_PER_WAVE * (WV)) * 64;                                             \
+        /* the instruction offset advances BOTH the global and the LDS address */                                \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, RPN_LDS_PTR(dst_), 16, b_voff, (SOFF), (PIECE) * 1024, 0); \
+    }
 #define RPN_DMA_B(SOFF, SLOT)                                                                                     \
     {                                                                                                             \
-        u32x4 *dst_ = Bs + (SLOT) * BSLOT + (B_PER_WAVE * wave) * 64;                                             \
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, RPN_LDS_PTR(dst_), 16, b_voff, (SOFF), 0, 0);             \
-        /* the instruction offset advances BOTH the global and the LDS address */                                \
-        if constexpr (B_PER_WAVE == 2)                                                                            \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, RPN_LDS_PTR(dst_), 16, b_voff, (SOFF), 1024, 0);      \
+        RPN_DMA_B1(SOFF, SLOT, 0, wave);                                                                          \
+        if constexpr (B_PER_WAVE == 2) RPN_DMA_B1(SOFF, SLOT, 1, wave);                                           \
     }
 
     int a_off[3][2];
@@ -1204,6 +1222,91 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
     RPN_STAMP_AT(0);
     RPN_STAMP_VAL(1, ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) |
                          (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4));       // XCC_ID, HW_ID
+    RPN_STAMP_WAVE_HWID();
+
+    // Issue sites of the tap loop's DMAs.  The pieces of an interval may be issued anywhere between its two barriers: the ring slot
+    // of tap t+3 was last read in interval t-1 and nobody reads the other halo buffer during the slice (hazards above); the counted
+    // wait at the interval's end stays exact as long as every wave issues the interval's pieces in front of it.  At the head of the
+    // interval, where all eight waves issued them at once in front of their first MFMA, they cost ~180 cycles per wave and tap.  Now
+    // the head holds the first fragment read and the first MFMA only:
+    //   weights (1 or 2 pieces) behind the 2 NJ chain-head MFMAs of half 0 (RPN_DMA_WEIGHTS),
+    //   the halo piece (taps 0..5) behind MFMA 4 NJ of half 1 (RPN_DMA_HALO; the 128-wide tile has no fragment read left there).
+    // The scalar address arithmetic sits at the sites, too: each site is a scheduling region of its own (sched_barrier), entered
+    // through a scalar branch on `gt >= 0`, which always holds.  The branch is there for the register allocator: with the 18 taps
+    // in ONE basic block and the sites inside it, hipcc spilled 160-184 VGPRs to scratch (and scratch loads share vmcnt with the
+    // DMAs); cut into blocks at the sites the kernel needs fewer registers than before (224 against 249 at 128 wide).  The LDS
+    // addresses are computed at the site from an opaque copy of the wave's index: hoisted, they held 15 scalar registers.
+    // All of this rests on hipcc not proving `gt >= 0` (gt starts at 3 and only loses total_taps after gaining as many).  A compiler
+    // that folds the branch brings the spills back: tests/test_host.py::test_kernel_register_budgets (no scratch, <= 256 VGPRs, the
+    // SGPR spill budgets) is the guard, and the fix is then another condition the compiler cannot see through.
+#ifdef RPN_EXP_NO_DMA
+#define RPN_TAP_DMA_B1(SOFF, SLOT, PIECE, WV) ((void)(SOFF))
+#define RPN_TAP_DMA_A(J, GOFF, SOFF, BUF, WV) ((void)(GOFF))
+#else
+#define RPN_TAP_DMA_B1 RPN_DMA_B1
+#define RPN_TAP_DMA_A RPN_DMA_A
+#endif
+#define RPN_DMA_WEIGHTS()   /* weights of tap t+3: this tile's, or the first taps of the next tile (or a harmless re-load) */  \
+    {                                                                                                              \
+        int wv_ = wave;                                                                                            \
+        asm volatile("" : "+s"(wv_));                                                                              \
+        if (gt >= 0) {                                                                                             \
+            int tap_ = gt, nb_ = n0;                                                                               \
+            if (gt >= total_taps) {                                                                                \
+                if (nxt >= 0) { tap_ = gt - total_taps; nb_ = nn0; }                                               \
+                else tap_ = total_taps - 1;                                                                        \
+            }                                                                                                      \
+            const int soff_ = (tap0 + tap_) * w_tap_bytes + nb_ * (PPP * 16);                                      \
+            RPN_TAP_DMA_B1(soff_, s9 % 3, 0, wv_);                                                                 \
+            if constexpr (B_PER_WAVE == 2) RPN_TAP_DMA_B1(soff_, s9 % 3, 1, wv_);                                  \
+        }                                                                                                          \
+    }
+#define RPN_DMA_HALO()      /* halo piece s9 of the next slice: this tile's, or slice 0 of the next tile */                 \
+    {                                                                                                              \
+        int wv_ = wave;                                                                                            \
+        asm volatile("" : "+s"(wv_));                                                                              \
+        if (T == 9 && nxt >= 0 && pair == (chunks >> 1) - 1) {    /* last slice of the tile: from here on the halo */ \
+            _Pragma("unroll") for (int j = 0; j < A_PER_WAVE; ++j) a_goff[j] = halo_goff(j, nimg, noy0, nox0);     /* of the NEXT tile */ \
+        }                                                                                                          \
+        if (s9 < A_PER_WAVE && gt >= 0) {                                                                          \
+            const int nc_ = 2 * pair + c2 + 1;                                                                     \
+            RPN_TAP_DMA_A(s9, a_goff[s9], (cb + (nc_ < chunks ? nc_ : (nxt >= 0 ? 0 : chunks - 1))) * 128, (c2 + 1) & 1, wv_); \
+        }                                                                                                          \
+    }
+    // sched_group_barrier pipelines of the segments between the sites (0x100: one ds_read, 0x008: MFMAs); a pipeline takes its
+    // instructions from the code ABOVE it in its region, so each stands at the end of its segment
+#if RPN_DMA_SCHED
+#define RPN_SCHED_CUT() __builtin_amdgcn_sched_barrier(0)
+#define RPN_G_RM(NR, NM)                                                                                           \
+    _Pragma("unroll") for (int q_ = 0; q_ < (NR); ++q_) {                                                          \
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                         \
+        __builtin_amdgcn_sched_group_barrier(0x008, (NM), 0);                                                      \
+    }
+#define RPN_G00()       /* half 0, MFMAs [0, 2 NJ): a read of row 1's pixels behind each of the first four */       \
+    {                                                                                                              \
+        RPN_G_RM(4, 1);                                                                                            \
+        if constexpr (2 * NJ - 4 > 0) __builtin_amdgcn_sched_group_barrier(0x008, 2 * NJ - 4, 0);                  \
+    }
+#define RPN_GM() __builtin_amdgcn_sched_group_barrier(0x008, 4 * NJ, 0)     /* half 0, MFMAs [2 NJ, 6 NJ): bare */
+#define RPN_G10()       /* half 1, MFMAs [0, 4 NJ): the next tap's weights, a read per MFMA, then its row-0 pixels, one per two */ \
+    {                                                                                                              \
+        RPN_G_RM(2 * NJ, 1);                                                                                       \
+        RPN_G_RM((NJ < 4 ? NJ : 4), 2);                                                                            \
+        if constexpr (NJ > 4) __builtin_amdgcn_sched_group_barrier(0x008, 2 * (NJ - 4), 0);                        \
+    }
+#define RPN_G12()       /* half 1, MFMAs [4 NJ, 6 NJ): the rest of those reads (NJ < 4) */                           \
+    {                                                                                                              \
+        RPN_G_RM((NJ < 4 ? 4 - NJ : 0), 2);                                                                        \
+        if constexpr (NJ - (NJ < 4 ? 4 - NJ : 0) > 0)                                                              \
+            __builtin_amdgcn_sched_group_barrier(0x008, 2 * (NJ - (NJ < 4 ? 4 - NJ : 0)), 0);                      \
+    }
+#else
+#define RPN_SCHED_CUT() ((void)0)
+#define RPN_G00() ((void)0)
+#define RPN_GM() ((void)0)
+#define RPN_G10() ((void)0)
+#define RPN_G12() ((void)0)
+#endif
 
     // Fragment registers.  The interval of a tap is worked in two halves (the wave's first / second pixel row) so that
     // only the weight fragments are double-buffered: fx0 / fx1 hold [hi, lo] of the two 16-pixel tiles of row 0 / 1.
@@ -1220,7 +1323,7 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
 #pragma unroll
     for (int j = 0; j < A_PER_WAVE; ++j) a_goff[j] = halo_goff(j, img, oy0, ox0);
 #pragma unroll
-    for (int j = 0; j < A_PER_WAVE; ++j) RPN_DMA_A(j, a_goff[j], cb * 128, 0);
+    for (int j = 0; j < A_PER_WAVE; ++j) RPN_DMA_A(j, a_goff[j], cb * 128, 0, wave);
 #pragma unroll
     for (int t = 0; t < 3; ++t) RPN_DMA_B((tap0 + t) * w_tap_bytes + n0 * (PPP * 16), t);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1258,33 +1361,12 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
                 const int c2 = T / 9, s9 = T % 9;
                 const int CS = T & 1, CB = c2 & 1, CR = s9 / 3, CC = s9 % 3;                       // this tap
                 const int NS = (T + 1) & 1, NB = ((T + 1) / 9) & 1, NR = ((T + 1) % 9) / 3, NC = ((T + 1) % 9) % 3;   // next
-                {   // weights of tap t+3: this tile's, or the first taps of the next tile (or a harmless re-load)
-                    int tap = gt, nb = n0;
-                    if (gt >= total_taps) {
-                        if (nxt >= 0) { tap = gt - total_taps; nb = nn0; }
-                        else tap = total_taps - 1;
-                    }
-#ifndef RPN_EXP_NO_DMA
-                    RPN_DMA_B((tap0 + tap) * w_tap_bytes + nb * (PPP * 16), s9 % 3);
-#endif
-                    ++gt;
-                }
                 if (dyn && pair == 0) {     // (nothing before tap 9 of the last slice needs to know the next tile)
                     if (T == 4 && tid == 0) tile_q[tile_no & 1] = walk.settle((int)ticket, a.sched + xcd);
                     if (T == 6) {           // two barriers later
                         const int sl = __builtin_amdgcn_readfirstlane(tile_q[tile_no & 1]);
                         nxt = (sl < walk.n_slots && walk.decode(sl, nimg, noy0, nox0, nn0)) ? sl : -1;
                     }
-                }
-                if (T == 9 && nxt >= 0 && pair == (chunks >> 1) - 1) {    // last slice of the tile: from here on the halo
-#pragma unroll
-                    for (int j = 0; j < A_PER_WAVE; ++j) a_goff[j] = halo_goff(j, nimg, noy0, nox0);   // of the NEXT tile
-                }
-                if (s9 < A_PER_WAVE) {      // halo piece s9 of the next slice: this tile's, or slice 0 of the next tile
-                    const int nc = 2 * pair + c2 + 1;
-#ifndef RPN_EXP_NO_DMA
-                    RPN_DMA_A(s9, a_goff[s9], (cb + (nc < chunks ? nc : (nxt >= 0 ? 0 : chunks - 1))) * 128, (c2 + 1) & 1);
-#endif
                 }
                 // ---- half 0: row 0.  Program order = intended issue order: a fragment read behind each of the first MFMAs
 #pragma unroll
@@ -1294,22 +1376,17 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
 #endif
                     acc[i / NJ][i % NJ] = mfma16<F16>(fx0[2 * (i / NJ) + 1], fw[CS][2 * (i % NJ)], acc[i / NJ][i % NJ]);
                 }
+                RPN_G00();
+                RPN_SCHED_CUT();
+                RPN_DMA_WEIGHTS();
+                RPN_SCHED_CUT();
 #pragma unroll
                 for (int i = 0; i < 2 * NJ; ++i) {
                     acc[i / NJ][i % NJ] = mfma16<F16>(fx0[2 * (i / NJ)], fw[CS][2 * (i % NJ) + 1], acc[i / NJ][i % NJ]);   // x hi * w lo
                     acc[i / NJ][i % NJ] = mfma16<F16>(fx0[2 * (i / NJ)], fw[CS][2 * (i % NJ)], acc[i / NJ][i % NJ]);       // x hi * w hi
                 }
-#if RPN_DMA_SCHED
-                if (s9 < A_PER_WAVE) __builtin_amdgcn_sched_group_barrier(0x020, B_PER_WAVE + 1, 0);
-                else __builtin_amdgcn_sched_group_barrier(0x020, B_PER_WAVE, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, 6 * NJ - 4, 0);
-                __builtin_amdgcn_sched_barrier(0);
-#endif
+                RPN_GM();
+                RPN_SCHED_CUT();
                 // ---- half 1: row 1; the next tap's weights and row-0 pixels arrive meanwhile
 #pragma unroll
                 for (int i = 0; i < 2 * NJ; ++i) {
@@ -1322,26 +1399,21 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
                 }
 #pragma unroll
                 for (int i = 0; i < 2 * NJ; ++i) {
+                    if (i == NJ) {
+                        RPN_G10();
+                        RPN_SCHED_CUT();
+                        RPN_DMA_HALO();
+                        RPN_SCHED_CUT();
+                    }
 #ifndef RPN_EXP_NO_LDSREAD
                     if (i < 4) fx0[i] = RPN_X_ADDR(NB, NR, NC, 0, i);
 #endif
                     acc[2 + i / NJ][i % NJ] = mfma16<F16>(fx1[2 * (i / NJ)], fw[CS][2 * (i % NJ) + 1], acc[2 + i / NJ][i % NJ]);
                     acc[2 + i / NJ][i % NJ] = mfma16<F16>(fx1[2 * (i / NJ)], fw[CS][2 * (i % NJ)], acc[2 + i / NJ][i % NJ]);
                 }
-#if RPN_DMA_SCHED
-#pragma unroll
-                for (int i = 0; i < 2 * NJ; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                }
-                if constexpr (4 * NJ - 8 > 0) __builtin_amdgcn_sched_group_barrier(0x008, 4 * NJ - 8, 0);
-                __builtin_amdgcn_sched_barrier(0);     // (register-only MFMAs would otherwise sink below the barrier)
-#endif
+                RPN_G12();
+                RPN_SCHED_CUT();                       // (register-only MFMAs would otherwise sink below the barrier)
+                ++gt;
                 // Leave exactly this interval's own DMAs in flight.  Not in a tile's first interval: what it needs (tap 2) was
                 // retired by the vmcnt(0) in front of the previous tile's epilogue (or by the prologue), and the in-order
                 // counter would otherwise make the wave wait for that epilogue's global stores -- all 256 workgroups
@@ -1427,6 +1499,17 @@ conv3x3_split16_dma_kernel(SplitConvArgs a, int tiles_x, int tiles_y, int n_tile
 #undef RPN_SCHED_EXIT
 #undef RPN_DMA_A
 #undef RPN_DMA_B
+#undef RPN_DMA_B1
+#undef RPN_TAP_DMA_B1
+#undef RPN_TAP_DMA_A
+#undef RPN_DMA_WEIGHTS
+#undef RPN_DMA_HALO
+#undef RPN_SCHED_CUT
+#undef RPN_G_RM
+#undef RPN_G00
+#undef RPN_GM
+#undef RPN_G10
+#undef RPN_G12
 }
 
 // (LABORATORY BUILD ONLY, -DRPN_LAB: measured SLOWER than the 8-wave form and not part of the product library -- see the note at
