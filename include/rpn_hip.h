@@ -607,8 +607,59 @@ int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const flo
  *   rpn_fc_forward_x3: the split product on its own.  d_w is the float32 (K, ldw) matrix ON THE DEVICE; s is taken over its columns
  *     [0, N).  A test entry like rpn_conv2d: every call finds max|w|, allocates, packs and synchronises.  d_status: a device word
  *     that receives RPN_STATUS_F16_RANGE, or NULL.
+ *
+ * Training the head in split float16 (rpn_det_head_set_train_precision on a trainable = 1 head, which is created in float32).  The
+ * master weights, the gradients, the bias sums and Adam stay float32; every PRODUCT runs on v_mfma_f32_16x16x32_f16:
+ *   Forward: every forward of such a head (kept or not) is the contract above, unchanged -- the same image, the same s per layer, the
+ *     same kernel -- so its outputs are bit for bit those of an F16X3 inference head holding the same weights.
+ *   Gradient split: an output gradient dZ (M, N) enters every product as the hi / lo split (round-to-nearest-even, as above) of
+ *     dZ * 2^t, ONE t per gradient tensor: dz (the cls | reg pair side by side, one t over its 5 C real columns), d_h2, d_h1.
+ *     t = 12 - e where max|dZ| = m 2^e, m in [0.5, 1), over the M live rows and the real columns; 0 for an all-zero tensor; NaNs are
+ *     skipped by the maximum.  t is clamped to [-116, 100]: -116 is what the largest finite float32 gives, so every finite
+ *     gradient is brought into float16's range.  The maximum is found on the device (an integer atomicMax on the bits: order-
+ *     independent), with no host round trip.
+ *   dW = in^T dZ: `in` enters unscaled, with the very split the forward applied to it; dZ as above; the accumulator is multiplied by
+ *     2^-t (exact).  The reduction runs over the M rows.
+ *   d_in = dZ W^T: dZ as above; W as the split of W * 2^s, s by the forward's rule over the matrix this product sees -- fc1's and
+ *     fc2's own s, and for the pair ONE s over cls | reg together (the forward's two scales cannot be factored out of one
+ *     reduction).  W is read from the float32 master weights and split on the fly: there is no transposed image.  The accumulator is
+ *     multiplied by 2^-(t + s) as TWO exact multiplications, by 2^a and then 2^b with a = -(t + s) / 2 truncated and b = -(t + s) - a
+ *     (2^-(t + s) may leave float32's range as one factor; 2^-t alone may overflow an accumulator that 2^-s brings back, so the
+ *     halves have the same sign: whatever order of 2^-t and 2^-s stays in range gives these bits).  The reduction runs over the N
+ *     real columns.
+ *   Product and order: hi*hi + hi*lo + lo*hi, lo*lo dropped, float32 accumulation inside the MFMA.  The reduction index is walked in
+ *     steps of 32 from 0, in each step lo*hi, hi*lo, hi*hi; it is never split (2400 rows: 75 steps) and there is no floating-point
+ *     atomic.  Reduction tails enter as zeros; M and N need not be multiples of 4 or 32; the padding columns N .. ld - 1 of dZ and W
+ *     are read and dropped.  A row of d_in reads that row of dZ, W and the two shifts alone: the same bits at M = 1 and in a batch
+ *     whenever the row alone and the batch give the same t (a row that holds an entry of the batch maximum's binade does).
+ *   Everything else as in float32: db = the float32 column sums of dZ; the ReLU mask is [h > 0] on the kept activation (now the
+ *     split forward's), applied in the epilogue of the d_in product; gradients are stored float32; Adam is ONE launch on the master
+ *     weights.  Bit-identical from run to run.
+ *   Repack: adam_step refreshes the image and every s on the device from the master weights, by the rule above, without a
+ *     synchronisation; set_layer marks the image stale and the next forward refreshes it the same way.  The forward reads its 2^-s
+ *     from device memory.
+ *   Range: a non-finite gradient raises RPN_STATUS_F16_RANGE (rpn_det_head_status); a finite one of any magnitude does not.  Inputs
+ *     and activations raise it as in the forward.
+ *   rpn_det_head_set_train_precision: RPN_PRECISION_F32 (the default: exactly the float32 kernels) or RPN_PRECISION_F16X3; BF16X3 and
+ *     F32W are RPN_ERR_UNSUPPORTED, a trainable = 0 head or any other value RPN_ERR_INVALID.  It drops a kept forward, keeps the
+ *     weights, Adam's moments and the step count, and needs no device: the image is allocated at the next call that needs the device.
+ *     rpn_det_head_train_precision reports it.  (rpn_det_head_create_ex(trainable = 1, F16X3) stays RPN_ERR_UNSUPPORTED.)
+ *   Memory: from the first set_train_precision(F16X3) on, memory_bytes reports weights as w, g, m, v AND the image -- FIVE times the
+ *     float32 inference head's when every layer's K is a multiple of 32 (2.4 GB at 25 088 x 4096 x 4096), the rows up to the next
+ *     multiple of 32 more otherwise.  Going back to F32 keeps the image, and the report keeps saying so.
+ *   rpn_fc_wgrad_x3 / rpn_fc_dgrad_x3: the two products on their own.  TEST ENTRIES like rpn_fc_forward_x3: every call finds the
+ *     maxima, allocates and synchronises.  wgrad: d_out (K, N; leading dimension ldo >= N) = d_a (M, K)^T d_dz (M, N; leading
+ *     dimension ldz); the columns N .. ldo - 1 of d_out are not written.  dgrad: d_out (M, K) = d_dz (M, N; ldz) d_w (K, N; ldw)^T,
+ *     times [d_h > 0] when d_h (M, K) is given; s is taken over the K x N real entries of d_w.  K % 4 == 0 (wgrad), ldz % 4 == 0,
+ *     ldw % 4 == 0, d_a, d_dz, d_w 16-byte aligned; M and N free.  d_status as for rpn_fc_forward_x3.
  * ---------------------------------------------------------------------------------- */
 typedef struct rpn_det_head rpn_det_head;
+int rpn_det_head_set_train_precision(rpn_det_head *h, int precision);
+int rpn_det_head_train_precision(const rpn_det_head *h);
+int rpn_fc_wgrad_x3(const float *d_a, const float *d_dz, int M, int K, int N, int ldz, int ldo, float *d_out, unsigned *d_status,
+                    void *stream);
+int rpn_fc_dgrad_x3(const float *d_dz, const float *d_w, int M, int K, int N, int ldz, int ldw, const float *d_h, float *d_out,
+                    unsigned *d_status, void *stream);
 int rpn_det_head_create(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, rpn_det_head **out);
 int rpn_det_head_create_ex(int ph, int pw, int Cf, int H1, int H2, int C, int max_rows, int trainable, int precision,
                            rpn_det_head **out);

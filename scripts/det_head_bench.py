@@ -6,6 +6,15 @@ widths 4096 and 1024:
     head forward f16x3  the same forward on an inference copy of the head at precision "f16x3" (split float16 on the 16-bit MFMA)
     head backward    rpn_det_head_backward with the gradient of the pooled features
     head adam        rpn_det_head_adam_step (one launch over all eight tensors)
+    head step        forward (kept) + backward + adam on the float32 head, back to back between one pair of events
+    head forward (training, f16x3) / head backward f16x3 / head adam + repack / head step f16x3
+                     the same four on a second head of the same weights compiled with precision="f16x3": every product in split
+                     float16, the gradients' shifts found on the device, the packed image refreshed after Adam
+    fc1 wgrad f16x3 / fc1 dgrad f16x3   the two new GEMMs alone at fc1's shape (rpn_fc_wgrad_x3 / rpn_fc_dgrad_x3: test entries,
+                     so a max|.| scan, a small allocation and a synchronisation are inside the events) and
+    fc2 wgrad f16x3 / fc2 dgrad f16x3   the same at fc2's shape (M x H x H), beside
+    fc2 wgrad f32 / fc2 dgrad f32       their float32 counterparts rpn_conv1x1_wgrad / rpn_conv1x1_dgrad, which as single-layer entries
+                     take at most 4096 channels: fc1's K1 is beyond them, so the float32 comparison at fc1's size is the whole backward
     torch fwd+bwd+adam  the same four layers as torch.nn.Linear, float32, forward + backward (to the input) + torch.optim.Adam
     fc1 rpn_fc_forward  the first layer alone on the new GEMM (bias, no activation), with its TFLOP/s
     fc1 f16x3 (packed)  the first layer of the f16x3 head on its packed weights (rpn_det_head_forward_layer: bias and ReLU), events
@@ -14,7 +23,7 @@ widths 4096 and 1024:
     fc1 rpn_conv2d      the same product as a 1 x 1 conv on an (M, 1, 1, K) tensor: the library's way before rpn_fc_forward existed
                         (a single-layer test entry: every call allocates, packs the kernel for its tiles and synchronises)
 
-Also reports max |f16x3 - f32| of the logits and deltas on the benchmark's inputs.  Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
+Also reports max |f16x3 - f32| of the logits and deltas and of the eight parameter gradients on the benchmark's inputs.  Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
     python scripts/det_head_bench.py [--rounds 5] [--iters 3] [--json PATH]
 """
 import argparse
@@ -36,7 +45,7 @@ PEAK_TF, GUIDE_TF = 157.3, 122.0          # float32 matrix peak of the MI355X; a
 
 
 def time_variants(variants, rounds, iters):
-    """{name: callable} -> {name: (median_us, min_us)}; each round times every variant once (iters calls between two events)."""
+    """{name: callable} -> {name: (median_us, min_us, max_us)}; each round times every variant once (iters calls between two events)."""
     for fn in variants.values():
         fn()
     torch.cuda.synchronize()
@@ -50,7 +59,7 @@ def time_variants(variants, rounds, iters):
             e1.record()
             e1.synchronize()
             samples[name].append(e0.elapsed_time(e1) * 1e3 / iters)
-    return {n: (float(np.median(v)), float(np.min(v))) for n, v in samples.items()}
+    return {n: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for n, v in samples.items()}
 
 
 def bench_config(lib, channels, hidden, rounds, iters):
@@ -115,6 +124,62 @@ def bench_config(lib, channels, hidden, rounds, iters):
     def fc_x3():
         L.check(lib.rpn_det_head_forward_layer(head_x3._h, b"fc1", L.ptr(x2), M, L.ptr(out_x3), stream), "forward_layer f16x3")
 
+    # a second trainable head with the same weights, compiled in f16x3
+    head_t = DetectionHead(C, pooling_size=(7, 7), channels=channels, hidden=(hidden, hidden), max_rois=M, seed=1)
+    head_t.compile(precision="f16x3")
+    ht = head_t._h
+    logits_t, deltas_t = torch.empty_like(logits), torch.empty_like(deltas)
+
+    def fwd_t():
+        L.check(lib.rpn_det_head_forward(ht, L.ptr(pooled), M, 1, L.ptr(logits_t), L.ptr(deltas_t), stream), "forward (training, f16x3)")
+
+    def bwd_t():
+        L.check(lib.rpn_det_head_backward(ht, L.ptr(pooled), M, L.ptr(g_logits), L.ptr(g_deltas), L.ptr(g_pooled), stream), "backward f16x3")
+
+    def adam_t():
+        L.check(lib.rpn_det_head_adam_step(ht, 1e-4, 0.9, 0.999, 1e-7, stream), "adam + repack")
+
+    def step():
+        fwd(), bwd(), adam()
+
+    def step_t():
+        fwd_t(), bwd_t(), adam_t()
+
+    # the two new GEMMs alone at fc1's shape, and their float32 counterparts
+    g_h1 = torch.randn((M, hidden), device="cuda", generator=gen) / M
+    dw1, dx1 = torch.empty((K1, hidden), device="cuda"), torch.empty((M, K1), device="cuda")
+    w2 = fc2.weight.detach().t().contiguous()
+    h1 = torch.rand((M, hidden), device="cuda", generator=gen)
+    dw2, dx2 = torch.empty((hidden, hidden), device="cuda"), torch.empty((M, hidden), device="cuda")
+    ws_bytes_w = int(lib.rpn_conv1x1_wgrad_workspace_bytes(M, hidden, hidden))
+    ws_w = torch.empty((max(ws_bytes_w, 4) // 4,), device="cuda")
+
+    def wgrad_x3():
+        L.check(lib.rpn_fc_wgrad_x3(L.ptr(x2), L.ptr(g_h1), M, K1, hidden, hidden, hidden, L.ptr(dw1), None, stream), "rpn_fc_wgrad_x3")
+
+    def dgrad_x3():
+        L.check(lib.rpn_fc_dgrad_x3(L.ptr(g_h1), L.ptr(w1), M, K1, hidden, hidden, hidden, None, L.ptr(dx1), None, stream), "rpn_fc_dgrad_x3")
+
+    def wgrad2_x3():
+        L.check(lib.rpn_fc_wgrad_x3(L.ptr(h1), L.ptr(g_h1), M, hidden, hidden, hidden, hidden, L.ptr(dw2), None, stream), "rpn_fc_wgrad_x3")
+
+    def dgrad2_x3():
+        L.check(lib.rpn_fc_dgrad_x3(L.ptr(g_h1), L.ptr(w2), M, hidden, hidden, hidden, hidden, None, L.ptr(dx2), None, stream), "rpn_fc_dgrad_x3")
+
+    def wgrad2_f32():
+        L.check(lib.rpn_conv1x1_wgrad(L.ptr(h1), L.ptr(g_h1), M, hidden, hidden, L.ptr(dw2), L.ptr(ws_w), ws_bytes_w, stream), "rpn_conv1x1_wgrad")
+
+    def dgrad2_f32():
+        L.check(lib.rpn_conv1x1_dgrad(L.ptr(g_h1), L.ptr(w2), None, M, hidden, hidden, L.ptr(dx2), stream), "rpn_conv1x1_dgrad")
+
+    # max |f16x3 - f32| of the eight gradients, before any Adam step has moved the two heads apart
+    fwd(), bwd(), fwd_t(), bwd_t()
+    torch.cuda.synchronize()
+    g32, g16 = head.get_gradients(), head_t.get_gradients()
+    grad_diff = {"%s/%s" % (n, k): [float(np.abs(g16[n][k].astype(np.float64) - g32[n][k]).max()), float(np.abs(g32[n][k]).max())]
+                 for n in g32 for k in g32[n]}
+    grad_range = head_t.status()["f16_range"]
+
     fwd()
     fwd_x3()
     torch.cuda.synchronize()
@@ -123,8 +188,14 @@ def bench_config(lib, channels, hidden, rounds, iters):
             "f16_range": head_x3.status()["f16_range"]}
 
     variants = {"head forward f16x3": fwd_x3, "fc1 f16x3 (packed)": fc_x3, "head forward": fwd, "head backward": bwd, "head adam": adam, "torch fwd+bwd+adam": torch_step, "fc1 rpn_fc_forward": fc_new,
-                "fc1 torch.addmm": fc_torch}
-    fwd()                                                       # the backward needs a kept forward; every timed backward reuses the last one
+                "fc1 torch.addmm": fc_torch, "head forward (training, f16x3)": fwd_t, "head backward f16x3": bwd_t,
+                "head adam + repack": adam_t, "head step": step, "head step f16x3": step_t, "fc1 wgrad f16x3": wgrad_x3,
+                "fc1 dgrad f16x3": dgrad_x3, "fc2 wgrad f32": wgrad2_f32, "fc2 wgrad f16x3": wgrad2_x3, "fc2 dgrad f32": dgrad2_f32,
+                "fc2 dgrad f16x3": dgrad2_x3}
+    # the backward needs a kept forward; every timed backward reuses the last one, so in every round each head's forward comes before
+    # its backward and its adam (which drops the kept forward) after it
+    fwd()
+    fwd_t()
     conv_note = None
     try:
         fc_conv()
@@ -134,15 +205,23 @@ def bench_config(lib, channels, hidden, rounds, iters):
         variants["fc1 rpn_conv2d"] = fc_conv
     except (ValueError, RuntimeError) as e:
         conv_note = "rpn_conv2d refuses this shape: %s" % e
-    order = ["head forward", "head forward f16x3", "head backward", "head adam", "torch fwd+bwd+adam", "fc1 rpn_fc_forward",
-             "fc1 f16x3 (packed)", "fc1 torch.addmm", "fc1 rpn_conv2d"]
+    order = ["head forward", "head forward f16x3", "head forward (training, f16x3)", "head backward", "head backward f16x3", "head adam",
+             "head adam + repack", "head step", "head step f16x3", "torch fwd+bwd+adam", "fc1 rpn_fc_forward", "fc1 f16x3 (packed)",
+             "fc1 torch.addmm", "fc1 wgrad f16x3", "fc1 dgrad f16x3", "fc2 wgrad f32", "fc2 wgrad f16x3", "fc2 dgrad f32", "fc2 dgrad f16x3",
+             "fc1 rpn_conv2d"]
     variants = {n: variants[n] for n in order if n in variants}
     res = time_variants(variants, rounds, iters)
     flop1 = 2.0 * M * K1 * hidden
     tf = {n: flop1 / (res[n][0] * 1e-6) / 1e12 for n in res if n.startswith("fc1")}
+    tf.update({n: 2.0 * M * hidden * hidden / (res[n][0] * 1e-6) / 1e12 for n in res if n.startswith("fc2")})
     w_bytes, ws_bytes = head.memory_bytes()
     x3_bytes = head_x3.memory_bytes()
-    return dict(us_median_min=res, fc1_tflops=tf, conv_note=conv_note, weights_bytes=w_bytes, workspace_bytes=ws_bytes,
+    spread = lambda n: (res[n][2] - res[n][1]) / res[n][0]      # (max - min) / median over the rounds
+    train = dict(step_f32_over_f16x3=res["head step"][0] / res["head step f16x3"][0],
+                 step_f16x3_over_torch=res["head step f16x3"][0] / res["torch fwd+bwd+adam"][0],
+                 step_spread_f32=spread("head step"), step_spread_f16x3=spread("head step f16x3"), grad_max_abs_diff_and_max_abs=grad_diff,
+                 grad_f16_range=grad_range, train_weights_bytes=head_t.memory_bytes()[0], train_workspace_bytes=head_t.memory_bytes()[1])
+    return dict(us_median_min=res, fc1_tflops=tf, f16x3_training=train, conv_note=conv_note, weights_bytes=w_bytes, workspace_bytes=ws_bytes,
                 f16x3_weights_bytes=x3_bytes[0], f16x3_workspace_bytes=x3_bytes[1], f16x3_minus_f32=diff,
                 f16x3_forward_speedup=res["head forward"][0] / res["head forward f16x3"][0],
                 f16x3_fc1_speedup=res["fc1 rpn_fc_forward"][0] / res["fc1 f16x3 (packed)"][0])
@@ -162,12 +241,18 @@ def main():
             label = "%s K1=%d H=%d" % (backbone, 49 * channels, hidden)
             results[label] = bench_config(lib, channels, hidden, args.rounds, args.iters)
             torch.cuda.empty_cache()
-    print("%-32s %-20s %12s %12s %10s" % ("shape (M = %d)" % M, "variant", "median us", "min us", "TFLOP/s"))
+    print("%-32s %-30s %12s %12s %10s" % ("shape (M = %d)" % M, "variant", "median us", "min us", "TFLOP/s"))
     for label, row in results.items():
         for name, v in row["us_median_min"].items():
             tf = row["fc1_tflops"].get(name)
-            print("%-32s %-20s %12.1f %12.1f %10s" % (label, name, v[0], v[1], "%.1f" % tf if tf else ""))
+            print("%-32s %-30s %12.1f %12.1f %10s" % (label, name, v[0], v[1], "%.1f" % tf if tf else ""))
         print("%-32s %s" % (label, row["conv_note"]))
+        t = row["f16x3_training"]
+        worst = max(t["grad_max_abs_diff_and_max_abs"].items(), key=lambda kv: kv[1][0] / max(kv[1][1], 1e-300))
+        print("%-32s training step f32 / f16x3 %.2fx (spread of the rounds: f32 %.1f %%, f16x3 %.1f %%); f16x3 step / torch step %.2f; max "
+              "|f16x3 - f32| of the gradients, worst relative to max |g|: %s %.3e of %.3e; range flag %s; weights %.0f MB" % (
+                  label, t["step_f32_over_f16x3"], 100 * t["step_spread_f32"], 100 * t["step_spread_f16x3"], t["step_f16x3_over_torch"],
+                  worst[0], worst[1][0], worst[1][1], t["grad_f16_range"], t["train_weights_bytes"] / 1e6))
         d = row["f16x3_minus_f32"]
         print("%-32s f16x3 / f32: head forward %.2fx, fc1 %.2fx; max |f16x3 - f32| logits %.3e (max |logit| %.3e), deltas %.3e (max "
               "|delta| %.3e); range flag %s; f16x3 head weights %.0f MB" % (label, row["f16x3_forward_speedup"], row["f16x3_fc1_speedup"],

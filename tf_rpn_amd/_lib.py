@@ -139,6 +139,10 @@ _SIGNATURES = {
     "rpn_det_head_status": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_int, vp]),
     "rpn_det_head_forward_layer": (ctypes.c_int, [vp, ctypes.c_char_p, vp, ctypes.c_int, vp, vp]),
     "rpn_fc_forward_x3": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
+    "rpn_det_head_set_train_precision": (ctypes.c_int, [vp, ctypes.c_int]),
+    "rpn_det_head_train_precision": (ctypes.c_int, [vp]),
+    "rpn_fc_wgrad_x3": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
+    "rpn_fc_dgrad_x3": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp]),
     "rpn_evaluator_create": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, c_int_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                             ctypes.POINTER(vp)]),
     "rpn_evaluator_destroy": (None, [vp]),

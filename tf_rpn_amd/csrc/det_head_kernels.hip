@@ -2,7 +2,9 @@
 // pair (rpn_det_head_*, rpn_fc_forward; contract in include/rpn_hip.h).  New here: the forward GEMM (fc_forward_f32_kernel) and two
 // small element-wise kernels; the split-float16 forward of the inference head (RPN_PRECISION_F16X3) has its kernels in
 // det_head_x3_kernels.hip and its host side here.  The backward reuses the 1x1-conv backward GEMMs (train_mnv2.h), the column sums and Adam
-// (train_head.h) unchanged; after each input-gradient GEMM one in-place pass applies the ReLU mask (launch_relu_mask).
+// (train_head.h) unchanged; after each input-gradient GEMM one in-place pass applies the ReLU mask (launch_relu_mask).  A trainable
+// head switched to split float16 (rpn_det_head_set_train_precision) runs the split forward and det_head_x3_kernels.hip's two backward
+// GEMMs instead, keeps the packed image beside its float32 master weights and refreshes it on the device (head_repack).
 #include <cstdint>
 #include <cstring>
 
@@ -199,6 +201,13 @@ struct rpn_det_head {
     unsigned *status = nullptr;
     size_t xoff[3] = {0, 0, 0}, xbytes = 0;   // byte offsets of W1, W2, Wp in wx; its size
     int shift[4] = {0, 0, 0, 0};
+    // A trainable head whose products run in split float16 (rpn_det_head_set_train_precision): the same image beside the float32 master
+    // weights, refreshed ON THE DEVICE (head_repack) after every change of w, and every scale in device memory.  xmeta, 64 words:
+    // [0, 7) the bits of max|.| of fc1, fc2, cls, reg, dz, d2, d1; from word 8 the pairs {2^s, 2^-s} of fc1, fc2, cls, reg, cls | reg as
+    // one matrix, dz, d2, d1.  x_stale: w has changed since the image was written.
+    int train_precision = RPN_PRECISION_F32;
+    unsigned *xmeta = nullptr;
+    bool x_stale = false;
 };
 
 namespace {
@@ -247,15 +256,18 @@ void head_free(rpn_det_head *h)
     }
     if (h->wx) (void)hipFree(h->wx);
     if (h->status) (void)hipFree(h->status);
-    h->wx = nullptr, h->status = nullptr;
+    if (h->xmeta) (void)hipFree(h->xmeta);
+    h->wx = nullptr, h->status = nullptr, h->xmeta = nullptr;
     h->loaded = 0;               // the weights went with the buffers
     h->kept_rows = 0;
 }
 
 // the head's device memory, once; zeros everywhere (the padding columns of the pair stay zero for ever)
+int head_ensure_image(rpn_det_head *h);
+
 int head_ensure_device(rpn_det_head *h)
 {
-    if (h->w) return RPN_OK;
+    if (h->w) return head_ensure_image(h);
     RPN_REQUIRE_DEVICE();
     const size_t R = (size_t)h->max_rows;
     struct { float **p; size_t n; bool zero; } bufs[] = {
@@ -273,18 +285,41 @@ int head_ensure_device(rpn_det_head *h)
                         hipGetErrorString(e));
         }
     }
-    if (h->precision == RPN_PRECISION_F16X3) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->wx), h->xbytes);
-        if (e == hipSuccess) e = hipMemset(h->wx, 0, h->xbytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->status), sizeof(unsigned));
-        if (e == hipSuccess) e = hipMemset(h->status, 0, sizeof(unsigned));
-        if (e != hipSuccess) {
-            head_free(h);
-            return fail(RPN_ERR_NO_DEVICE, "rpn_det_head: device allocation of %zu bytes failed: %s", h->xbytes, hipGetErrorString(e));
-        }
+    return head_ensure_image(h);
+}
+
+// the packed image, the status word and (trainable heads) the scale block, once a precision asks for them; a trainable head's image
+// starts stale: whatever w holds by then is packed by the next call that reads the image
+int head_ensure_image(rpn_det_head *h)
+{
+    if (!h->xbytes || h->wx) return RPN_OK;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->wx), h->xbytes);
+    if (e == hipSuccess) e = hipMemset(h->wx, 0, h->xbytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->status), sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(h->status, 0, sizeof(unsigned));
+    if (e == hipSuccess && h->trainable) e = hipMalloc(reinterpret_cast<void **>(&h->xmeta), 64 * sizeof(unsigned));
+    if (e == hipSuccess && h->trainable) e = hipMemset(h->xmeta, 0, 64 * sizeof(unsigned));
+    if (e != hipSuccess) {
+        head_free(h);
+        return fail(RPN_ERR_NO_DEVICE, "rpn_det_head: device allocation of %zu bytes failed: %s", h->xbytes, hipGetErrorString(e));
     }
+    h->x_stale = h->trainable != 0;
     return RPN_OK;
 }
+
+// byte offsets and size of the packed image (host state only)
+void head_size_image(rpn_det_head *h)
+{
+    const size_t xs[6] = {fc_x3_packed_bytes(h->k1, h->h1), (size_t)h->h1 * sizeof(float), fc_x3_packed_bytes(h->h1, h->h2),
+                          (size_t)h->h2 * sizeof(float), fc_x3_packed_bytes(h->h2, h->npad), (size_t)h->npad * sizeof(float)};
+    h->xbytes = 0;
+    for (int i = 0; i < 6; ++i) {
+        if (i % 2 == 0) h->xoff[i / 2] = h->xbytes;
+        h->xbytes += xs[i];
+    }
+}
+
+float *head_scales(const rpn_det_head *h, int pair) { return reinterpret_cast<float *>(h->xmeta + 8) + 2 * pair; }
 
 // kernel / bias of layer `name` between HOST arrays and the buffer `base` (the weights or their gradient)
 int head_copy_layer(rpn_det_head *h, float *base, const char *name, float *kernel, float *bias, bool to_device, hipStream_t s)
@@ -315,12 +350,39 @@ int head_pack_layer(rpn_det_head *h, int i, const float *kernel)
     return RPN_OK;
 }
 
+// A training head's image and scales from its master weights, all on the device and without a synchronisation: max|w| per layer,
+// the shifts by the inference head's rule (plus the pair's joint one, for the input gradient), then fc_pack_x3_kernel per layer.
+hipError_t head_repack(rpn_det_head *h, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(h->xmeta, 0, 4 * sizeof(unsigned), s);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+        const LayerView lv = layer_view(h, i);
+        e = launch_fc_absmax(h->w + lv.kernel, lv.rows, lv.cols, lv.ld, h->xmeta + i, s);
+    }
+    if (e == hipSuccess) e = launch_fc_scales_x3(h->xmeta, 4, 2, 3, false, head_scales(h, 0), s);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) {
+        const LayerView lv = layer_view(h, i);
+        const int mat = i < 2 ? i : 2;
+        e = launch_fc_pack_x3(h->w + h->off[2 * mat], lv.rows, lv.ld, i == 3 ? h->c : 0, lv.cols, 0, h->wx + h->xoff[mat], s, head_scales(h, i));
+    }
+    if (e == hipSuccess) h->x_stale = false;
+    return e;
+}
+
+bool head_trains_x3(const rpn_det_head *h) { return h->train_precision == RPN_PRECISION_F16X3; }
+
+// before a training head's image is read
+hipError_t head_fresh_image(rpn_det_head *h, hipStream_t s) { return head_trains_x3(h) && h->x_stale ? head_repack(h, s) : hipSuccess; }
+
 // one product of the head at its precision: layer 0 (fc1), 1 (fc2) or 2 (the cls | reg pair; out0 / out1)
 hipError_t head_launch_layer(rpn_det_head *h, int mat, const float *in, int M, float *out0, float *out1, hipStream_t s)
 {
     const int K = mat == 0 ? h->k1 : mat == 1 ? h->h1 : h->h2, N = mat == 0 ? h->h1 : mat == 1 ? h->h2 : 5 * h->c;
     const int ld = mat == 2 ? h->npad : N, relu = mat == 2 ? 0 : 1, split = mat == 2 ? h->c : N;
     const float *w = h->w + h->off[2 * mat], *b = h->w + h->off[2 * mat + 1];
+    if (head_trains_x3(h))
+        return launch_fc_forward_x3(in, h->wx + h->xoff[mat], b, M, K, N, ld, relu, split, 1.0f, 1.0f, out0, out1, h->status, s,
+                                    head_scales(h, mat) + 1, head_scales(h, mat == 2 ? 3 : mat) + 1);
     if (h->precision != RPN_PRECISION_F16X3) return launch_fc_forward(in, w, b, M, K, N, ld, relu, split, out0, out1, s);
     return launch_fc_forward_x3(in, h->wx + h->xoff[mat], b, M, K, N, ld, relu, split, ldexpf(1.0f, -h->shift[mat]),
                                 ldexpf(1.0f, -h->shift[mat == 2 ? 3 : mat]), out0, out1, h->status, s);
@@ -367,14 +429,7 @@ extern "C" int rpn_det_head_create_ex(int ph, int pw, int Cf, int H1, int H2, in
         h->off[i] = h->n;
         h->n += sizes[i];
     }
-    if (precision == RPN_PRECISION_F16X3) {
-        const size_t xs[6] = {fc_x3_packed_bytes(h->k1, H1), sizes[1] * sizeof(float), fc_x3_packed_bytes(H1, H2), sizes[3] * sizeof(float),
-                              fc_x3_packed_bytes(H2, npad), sizes[5] * sizeof(float)};
-        for (int i = 0; i < 6; ++i) {
-            if (i % 2 == 0) h->xoff[i / 2] = h->xbytes;
-            h->xbytes += xs[i];
-        }
-    }
+    if (precision == RPN_PRECISION_F16X3) head_size_image(h);
     const long long R = max_rows;
     h->part_floats = std::max({conv1x1_wgrad_ws_floats(R, h->k1, H1), conv1x1_wgrad_ws_floats(R, H1, H2), conv1x1_wgrad_ws_floats(R, H2, npad),
                                colsum_ws_floats(R, H1), colsum_ws_floats(R, H2), colsum_ws_floats(R, npad)});
@@ -408,6 +463,7 @@ extern "C" int rpn_det_head_set_layer(rpn_det_head *h, const char *name, const f
     h->kept_rows = 0;            // a kept forward was made with the weights this call replaces
     st = head_copy_layer(h, h->w, name, const_cast<float *>(kernel), const_cast<float *>(bias), true, nullptr);
     if (st == RPN_OK && h->precision == RPN_PRECISION_F16X3) st = head_pack_layer(h, i, kernel);
+    h->x_stale = true;           // (a training head's image follows at the next call that reads it)
     if (st == RPN_OK) h->loaded |= 1u << i;
     return st;
 }
@@ -436,6 +492,23 @@ extern "C" int rpn_det_head_get_gradient(rpn_det_head *h, const char *name, floa
 
 extern "C" long long rpn_det_head_steps(const rpn_det_head *h) { return h ? h->t : 0; }
 
+extern "C" int rpn_det_head_set_train_precision(rpn_det_head *h, int precision)
+{
+    const char *who = "rpn_det_head_set_train_precision";
+    RPN_REQUIRE(h, "%s: null head", who);
+    RPN_REQUIRE(precision == RPN_PRECISION_F32 || precision == RPN_PRECISION_BF16X3 || precision == RPN_PRECISION_F16X3 ||
+                    precision == RPN_PRECISION_F32W, "%s: precision = %d is no rpn_precision value", who, precision);
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
+    if (precision == RPN_PRECISION_BF16X3 || precision == RPN_PRECISION_F32W)
+        return fail(RPN_ERR_UNSUPPORTED, "%s: a head trains in RPN_PRECISION_F32 or RPN_PRECISION_F16X3, not in precision %d", who, precision);
+    h->kept_rows = 0;            // a kept forward was made at the other precision
+    h->train_precision = precision;
+    if (precision == RPN_PRECISION_F16X3 && !h->xbytes) head_size_image(h);   // (allocated by the next call that needs the device)
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_train_precision(const rpn_det_head *h) { return h ? h->train_precision : RPN_PRECISION_F32; }
+
 extern "C" int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int M, int keep, float *d_logits, float *d_deltas,
                                     void *stream)
 {
@@ -449,7 +522,8 @@ extern "C" int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int 
     if (st != RPN_OK) return st;
     const hipStream_t s = as_stream(stream);
     h->kept_rows = 0;                    // the activations of an earlier forward are overwritten from here on
-    hipError_t e = head_launch_layer(h, 0, d_pooled, M, h->a1, nullptr, s);
+    hipError_t e = head_fresh_image(h, s);
+    if (e == hipSuccess) e = head_launch_layer(h, 0, d_pooled, M, h->a1, nullptr, s);
     if (e == hipSuccess) e = head_launch_layer(h, 1, h->a1, M, h->a2, nullptr, s);
     if (e == hipSuccess) e = head_launch_layer(h, 2, h->a2, M, d_logits, d_deltas, s);
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
@@ -468,7 +542,8 @@ extern "C" int rpn_det_head_forward_layer(rpn_det_head *h, const char *name, con
     RPN_REQUIRE(h->loaded >> i & 1u, "%s: layer '%s' was never set", who, name);
     const int st = head_ensure_device(h);
     if (st != RPN_OK) return st;
-    const hipError_t e = head_launch_layer(h, i, d_in, M, d_out, nullptr, as_stream(stream));
+    hipError_t e = head_fresh_image(h, as_stream(stream));
+    if (e == hipSuccess) e = head_launch_layer(h, i, d_in, M, d_out, nullptr, as_stream(stream));
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
     return RPN_OK;
 }
@@ -501,6 +576,34 @@ extern "C" int rpn_det_head_backward(rpn_det_head *h, const float *d_pooled, int
     const hipStream_t s = as_stream(stream);
     const int K1 = h->k1, H1 = h->h1, H2 = h->h2, NP = h->npad;
     float *w = h->w, *g = h->g;
+    if (head_trains_x3(h)) {
+        // the same chain in split float16: each gradient tensor's max|.| (over its M rows and real columns) gives its shift, on the
+        // device; the ReLU mask sits in the input-gradient product's epilogue; the bias sums stay float32
+        const int NC = 5 * h->c;
+        const float *sdz = head_scales(h, 5), *sd2 = head_scales(h, 6), *sd1 = head_scales(h, 7);
+        auto shift_of = [&](const float *t, int cols, int ld, int slot) {
+            hipError_t r = launch_fc_absmax(t, M, cols, ld, h->xmeta + 4 + slot, s);
+            if (r == hipSuccess) r = launch_fc_scales_x3(h->xmeta + 4 + slot, 1, -1, -1, true, head_scales(h, 5 + slot), s);
+            return r;
+        };
+        hipError_t e = hipMemsetAsync(h->xmeta + 4, 0, 3 * sizeof(unsigned), s);
+        if (e == hipSuccess) e = launch_pack_pair_grad(d_grad_logits, d_grad_deltas, M, h->c, NP, h->dz, s);
+        if (e == hipSuccess) e = shift_of(h->dz, NC, NP, 0);
+        if (e == hipSuccess) e = launch_fc_wgrad_x3(h->a2, h->dz, M, H2, NC, NP, NP, sdz, g + h->off[4], h->status, s);
+        if (e == hipSuccess) e = launch_colsum(h->dz, M, NP, h->part, g + h->off[5], s);
+        if (e == hipSuccess) e = launch_fc_dgrad_x3(h->dz, w + h->off[4], h->a2, M, H2, NC, NP, NP, sdz, head_scales(h, 4), h->d2, h->status, s);
+        if (e == hipSuccess) e = shift_of(h->d2, H2, H2, 1);
+        if (e == hipSuccess) e = launch_fc_wgrad_x3(h->a1, h->d2, M, H1, H2, H2, H2, sd2, g + h->off[2], h->status, s);
+        if (e == hipSuccess) e = launch_colsum(h->d2, M, H2, h->part, g + h->off[3], s);
+        if (e == hipSuccess) e = launch_fc_dgrad_x3(h->d2, w + h->off[2], h->a1, M, H1, H2, H2, H2, sd2, head_scales(h, 1), h->d1, h->status, s);
+        if (e == hipSuccess) e = shift_of(h->d1, H1, H1, 2);
+        if (e == hipSuccess) e = launch_fc_wgrad_x3(d_pooled, h->d1, M, K1, H1, H1, H1, sd1, g + h->off[0], h->status, s);
+        if (e == hipSuccess) e = launch_colsum(h->d1, M, H1, h->part, g + h->off[1], s);
+        if (e == hipSuccess && d_grad_pooled)
+            e = launch_fc_dgrad_x3(h->d1, w + h->off[0], nullptr, M, K1, H1, H1, H1, sd1, head_scales(h, 0), d_grad_pooled, h->status, s);
+        if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+        return RPN_OK;
+    }
     // the pair: dz = [grad_logits | grad_deltas | 0]; dWp = a2^T dz, dbp = sum dz, d2 = (dz Wp^T) [a2 > 0]
     hipError_t e = launch_pack_pair_grad(d_grad_logits, d_grad_deltas, M, h->c, NP, h->dz, s);
     if (e == hipSuccess) e = launch_conv1x1_wgrad(h->a2, h->dz, M, H2, NP, h->part, g + h->off[4], s);
@@ -531,7 +634,9 @@ extern "C" int rpn_det_head_adam_step(rpn_det_head *h, float lr, float beta_1, f
     const int st = head_ensure_device(h);
     if (st != RPN_OK) return st;
     h->kept_rows = 0;            // a kept forward was made with the weights this step changes
-    const hipError_t e = launch_adam(h->w, h->g, h->m, h->v, (long long)h->n, h->t + 1, lr, beta_1, beta_2, epsilon, as_stream(stream));
+    hipError_t e = launch_adam(h->w, h->g, h->m, h->v, (long long)h->n, h->t + 1, lr, beta_1, beta_2, epsilon, as_stream(stream));
+    h->x_stale = true;
+    if (e == hipSuccess) e = head_fresh_image(h, as_stream(stream));          // split float16: repacked here, without a synchronisation
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
     h->t += 1;
     return RPN_OK;
@@ -583,6 +688,71 @@ extern "C" int rpn_fc_forward_x3(const float *d_a, const float *d_w, const float
     if (e == hipSuccess) e = launch_fc_forward_x3(d_a, buf, d_bias, M, K, N, ldw, relu, N, scale, scale, d_out, nullptr, d_status, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(buf);
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}
+
+namespace {
+
+// the scale block of a test entry: the maximum's bits at word 0, pairs from word 8
+hipError_t entry_scales(const float *t, int rows, int cols, int ld, bool gradient, unsigned *meta, int slot, hipStream_t s)
+{
+    hipError_t e = launch_fc_absmax(t, rows, cols, ld, meta + slot, s);
+    if (e == hipSuccess) e = launch_fc_scales_x3(meta + slot, 1, -1, -1, gradient, reinterpret_cast<float *>(meta + 8) + 2 * slot, s);
+    return e;
+}
+
+}  // namespace
+
+extern "C" int rpn_fc_wgrad_x3(const float *d_a, const float *d_dz, int M, int K, int N, int ldz, int ldo, float *d_out,
+                               unsigned *d_status, void *stream)
+{
+    const char *who = "rpn_fc_wgrad_x3";
+    RPN_REQUIRE(d_a && d_dz && d_out, "%s: null pointer", who);
+    RPN_REQUIRE(M >= 1 && N >= 1, "%s: M = %d, N = %d", who, M, N);
+    RPN_REQUIRE(K >= 4 && K % 4 == 0 && K <= kFcMaxRows, "%s: K = %d must be a positive multiple of 4 (at most %lld)", who, K, kFcMaxRows);
+    RPN_REQUIRE(ldz >= N && ldz % 4 == 0, "%s: ldz = %d must be a multiple of 4 and >= N = %d", who, ldz, N);
+    RPN_REQUIRE(ldo >= N, "%s: ldo = %d must be >= N = %d", who, ldo, N);
+    RPN_REQUIRE(aligned16(d_a) && aligned16(d_dz), "%s: a and dz must be 16-byte aligned", who);
+    RPN_REQUIRE((reinterpret_cast<uintptr_t>(d_out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3u) == 0,
+                "%s: out and the status word must be 4-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const hipStream_t s = as_stream(stream);
+    unsigned *meta = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&meta), 64 * sizeof(unsigned));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: device allocation failed: %s", who, hipGetErrorString(e));
+    e = hipMemsetAsync(meta, 0, 64 * sizeof(unsigned), s);
+    if (e == hipSuccess) e = entry_scales(d_dz, M, N, ldz, true, meta, 0, s);
+    if (e == hipSuccess) e = launch_fc_wgrad_x3(d_a, d_dz, M, K, N, ldz, ldo, reinterpret_cast<float *>(meta + 8), d_out, d_status, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(meta);
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}
+
+extern "C" int rpn_fc_dgrad_x3(const float *d_dz, const float *d_w, int M, int K, int N, int ldz, int ldw, const float *d_h, float *d_out,
+                               unsigned *d_status, void *stream)
+{
+    const char *who = "rpn_fc_dgrad_x3";
+    RPN_REQUIRE(d_dz && d_w && d_out, "%s: null pointer", who);
+    RPN_REQUIRE(M >= 1 && M <= kFcMaxRows && K >= 1 && N >= 1, "%s: M = %d (1 .. %lld), K = %d, N = %d", who, M, kFcMaxRows, K, N);
+    RPN_REQUIRE(ldz >= N && ldz % 4 == 0 && ldw >= N && ldw % 4 == 0, "%s: ldz = %d and ldw = %d must be multiples of 4 and >= N = %d", who,
+                ldz, ldw, N);
+    RPN_REQUIRE(aligned16(d_dz) && aligned16(d_w), "%s: dz and w must be 16-byte aligned", who);
+    RPN_REQUIRE((reinterpret_cast<uintptr_t>(d_out) & 3u) == 0 && (reinterpret_cast<uintptr_t>(d_h) & 3u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(d_status) & 3u) == 0, "%s: out, h and the status word must be 4-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const hipStream_t s = as_stream(stream);
+    unsigned *meta = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&meta), 64 * sizeof(unsigned));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: device allocation failed: %s", who, hipGetErrorString(e));
+    float *sc = reinterpret_cast<float *>(meta + 8);
+    e = hipMemsetAsync(meta, 0, 64 * sizeof(unsigned), s);
+    if (e == hipSuccess) e = entry_scales(d_dz, M, N, ldz, true, meta, 0, s);
+    if (e == hipSuccess) e = entry_scales(d_w, K, N, ldw, false, meta, 1, s);
+    if (e == hipSuccess) e = launch_fc_dgrad_x3(d_dz, d_w, d_h, M, K, N, ldz, ldw, sc, sc + 2, d_out, d_status, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(meta);
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
     return RPN_OK;
 }

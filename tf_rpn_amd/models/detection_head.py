@@ -16,6 +16,12 @@ carried as hi + lo float16 halves (``hi*hi + hi*lo + lo*hi``, float32 accumulati
 the same batch independence and run-to-run bit identity, an error a little above float32's, and twice the weight memory (the
 float32 weights are kept beside their packed image).  Features or activations beyond the float16 range raise a flag
 (``status()``); the outputs of such a forward are invalid and the float32 head is the one to use.
+
+A trainable head is created in float32 and may TRAIN in split float16: ``compile(..., precision="f16x3")`` runs every product
+of the forward and of the backward in ``f16x3`` (the output gradients carried as the split of ``dZ * 2^t``, one power of two per
+gradient tensor found on the device) while the master weights, the gradients, the bias sums and Adam stay float32.  Its forward
+is bit for bit the ``f16x3`` inference head's on the same weights; the packed image (a fifth copy of the weights: 2.4 GB in all
+at 25 088 x 4096 x 4096) is refreshed on the device after every ``apply_gradients()``.
 """
 import ctypes
 
@@ -72,7 +78,8 @@ class DetectionHead(object):
     it is one forward, one backward, one ``apply_gradients``.  Under ``torch.no_grad()`` nothing is kept.  ``trainable=False`` is the inference head: weights and the two hidden activations only.
 
     ``precision``: ``"f32"`` (exact float32, the default) or ``"f16x3"`` (split float16 on the 16-bit matrix cores; needs
-    ``trainable=False``: training stays exact float32).  ``head.precision`` reports it.
+    ``trainable=False``).  ``head.precision`` reports it.  A trainable head is always constructed in float32; the precision it
+    TRAINS in is ``compile``'s ``precision`` (``head.train_precision``).
 
     Initial weights are Keras' ``Dense`` defaults, Glorot-uniform kernels and zero biases, drawn from ``seed``; ``seed=None`` sets
     none (every layer must then be given with ``set_weights`` before the first call)."""
@@ -183,8 +190,9 @@ class DetectionHead(object):
 
     def status(self, reset=False):
         """Sticky flags raised on the device by the forwards so far -> {"f16_range": bool}.  ``f16_range`` (``precision="f16x3"``
-        only; a float32 head always reports False): a pooled feature or a hidden activation did not fit float16 (|x| > 65504 or
-        non-finite), the outputs of that forward are invalid -- use the float32 head.  Synchronises the current stream."""
+        or a head compiled with it; a float32 head always reports False): a pooled feature or a hidden activation did not fit
+        float16 (|x| > 65504 or non-finite), or an output gradient was non-finite; the outputs of that forward / backward are
+        invalid -- use the float32 head.  Synchronises the current stream."""
         flags = ctypes.c_uint(0)
         stream = L.stream_ptr() if torch.cuda.is_available() else None     # (without a device there is no flag either)
         L.check(L.lib().rpn_det_head_status(self._h, ctypes.byref(flags), 1 if reset else 0, stream), "rpn_det_head_status")
@@ -233,9 +241,27 @@ class DetectionHead(object):
         return self._forward(x.detach(), keep=False)
 
     # ---- optimiser ----------------------------------------------------------------------
-    def compile(self, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        """Adam's parameters (Keras' defaults but for the learning rate); the moments live in the head from its creation."""
+    def compile(self, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7, precision="f32"):
+        """Adam's parameters (Keras' defaults but for the learning rate); the moments live in the head from its creation.
+
+        ``precision``: what a trainable head computes in from here on -- ``"f32"`` (exact float32) or ``"f16x3"`` (every product of the
+        forward and the backward in split float16; master weights, gradients, bias sums and Adam stay float32).  Compiling again
+        switches back and forth; the weights, Adam's moments and the step count are kept, a kept forward is dropped."""
+        if precision not in PRECISIONS:
+            raise ValueError("precision must be one of %r, got %r" % (PRECISIONS, precision))
+        if precision == "f16x3" and not self.trainable:
+            raise ValueError("compile(precision='f16x3') needs a trainable head; an inference head takes its precision at construction")
+        if self.trainable:
+            self._serial += 1
+            L.check(L.lib().rpn_det_head_set_train_precision(self._h, L.PRECISIONS[precision]), "rpn_det_head_set_train_precision")
         self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
+
+    @property
+    def train_precision(self):
+        """the precision of a trainable head's products (``compile``); an inference head reports its construction precision"""
+        if not self.trainable:
+            return self.precision
+        return "f16x3" if int(L.lib().rpn_det_head_train_precision(self._h)) == L.PRECISIONS["f16x3"] else "f32"
 
     def apply_gradients(self):
         """one Adam step (one launch) from the gradients the last backward left"""
