@@ -230,6 +230,16 @@ int rpn_model_status(rpn_model *m, unsigned *flags, int reset, void *stream);
 /* debug / test hook: copy the activation of layer `name` (NHWC float32) into d_out */
 int rpn_model_get_activation(rpn_model *m, const char *name, float *d_out, size_t out_bytes, int shape[4],
                              void *stream);
+/* debug / test hook: which form of the head (rpn_reg | rpn_cls) a forward of B images on this handle runs.  Host arithmetic
+ * only, nothing is launched; the forward takes its choice from the same functions.
+ *   info[0]  RPN_HEAD_ROUTE_SPLITK (rpn_head_splitk<NB>) or RPN_HEAD_ROUTE_F32 (the float32 implicit GEMM: 5K > 96 or RPN_HEAD_SPLITK=0)
+ *   info[1]  NB = ceil(5K / 16), the kernel's 16-column blocks               (0 on the float32 route)
+ *   info[2]  pixels per workgroup: 32, 16, or 4 (at most 1024 pixels in slabs) (0 on the float32 route)
+ *   info[3]  partial-sum slabs of rpn_conv that the head adds: 1, 2 or 4     (1 on the float32 route)
+ * RPN_ERR_INVALID for B outside [1, max_batch]. */
+#define RPN_HEAD_ROUTE_SPLITK 0
+#define RPN_HEAD_ROUTE_F32 1
+int rpn_model_head_launch_info(const rpn_model *m, int B, int info[4]);
 /* algorithmic FLOPs (2*MACs) of one image through the conv stack */
 double rpn_model_flops_per_image(const rpn_model *m);
 /* per-op timing with HIP events recorded on the caller's stream around every launch of a forward:

@@ -12,9 +12,19 @@ from tf_rpn_amd.predictor import Proposer
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("backbone,img,fm", [("vgg16", 160, 10), ("mobilenet_v2", 160, 10)])
-def test_propose_against_oracle_pipeline(backbone, img, fm):
-    hp = bo.get_hyper_params(backbone, img_size=img, feature_map_shape=fm)
+# anchor tables (ratios, scales): None = the reference's 3 x 3 (K = 9); 4 scales x 3 ratios (K = 12: rpn_head_splitk<4>, n_reg = 48 on a
+# 16-column boundary) and 2 x 2 (K = 4: rpn_head_splitk<2>), the scales sized to a 160-pixel image
+ANCHORS_4X3 = ([1.0, 2.0, 0.5], [32, 64, 96, 128])
+ANCHORS_2X2 = ([1.0, 2.0], [48, 96])
+
+
+@pytest.mark.parametrize("backbone,img,fm,table", [
+    pytest.param("vgg16", 160, 10, None, id="vgg16-160-10"), pytest.param("mobilenet_v2", 160, 10, None, id="mobilenet_v2-160-10"),
+    pytest.param("vgg16", 160, 10, ANCHORS_4X3, id="vgg16-160-10-4x3"), pytest.param("mobilenet_v2", 160, 10, ANCHORS_4X3, id="mobilenet_v2-160-10-4x3"),
+    pytest.param("vgg16", 160, 10, ANCHORS_2X2, id="vgg16-160-10-2x2"), pytest.param("mobilenet_v2", 160, 10, ANCHORS_2X2, id="mobilenet_v2-160-10-2x2")])
+def test_propose_against_oracle_pipeline(backbone, img, fm, table):
+    hp = bo.get_hyper_params(backbone, img_size=img, feature_map_shape=fm, anchor_ratios=table and table[0], anchor_scales=table and table[1])
+    assert hp["anchor_count"] == (len(table[0]) * len(table[1]) if table else 9)
     weights = synthetic_weights(backbone, hp, seed=3)
     prop = Proposer(backbone, hyper_params=dict(hp), weights=weights, max_batch=2, iou_threshold=0.7)
     imgs = np.random.RandomState(1).uniform(0, 1, size=(2, img, img, 3)).astype(np.float32)

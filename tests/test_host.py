@@ -201,6 +201,39 @@ def test_graph_builder_shapes_and_flops(lib, backbone, img, K, F, gflops, nlayer
     assert w_bytes > 0 and arena_bytes > 0
 
 
+def test_head_launch_info_query(lib):
+    """rpn_model_head_launch_info: host arithmetic (no device).  A valid (route, NB, pixels per workgroup, slabs) for every K in
+    1 .. 19 at B = 1 and 8, the float32 GEMM from K = 20 on, an error for a batch the handle cannot run."""
+    from tf_rpn_amd.models._rpn_model import RPNModel
+    for K in range(1, 20):
+        for precision in ("f32", "f16x3"):
+            m = RPNModel("vgg16", {"img_size": 80, "anchor_count": K}, precision=precision, max_batch=8)
+            for B in (1, 8):
+                info = m.head_launch_info(B)
+                assert info["route"] == "splitk" and info["NB"] == (5 * K + 15) // 16, (K, B, info)
+                assert info["pixels_per_workgroup"] in (32, 16, 4) and info["slabs"] in (1, 2, 4), (K, B, info)
+                # 25 B pixels: never 32-pixel workgroups; 4-pixel ones exactly when slabs are added (at most 1024 pixels)
+                assert info["pixels_per_workgroup"] == (4 if info["slabs"] > 1 else 16), (K, B, info)
+                if precision == "f32":
+                    assert info["slabs"] == 1                       # only the split-precision rpn_conv splits K
+            assert [op["kernel"] for op in m.ops()][-1] == "rpn_head_splitk<%d>" % ((5 * K + 15) // 16)
+    # the three grids: 8 x 33 x 33 = 8712 pixels -> 32 per workgroup; one image -> 16
+    m = RPNModel("mobilenet_v2", {"img_size": 528, "anchor_count": 12}, max_batch=8)
+    assert m.head_launch_info(8) == {"route": "splitk", "NB": 4, "pixels_per_workgroup": 32, "slabs": 1}
+    assert m.head_launch_info(7)["pixels_per_workgroup"] == 16 and m.head_launch_info(1)["pixels_per_workgroup"] == 16
+    m = RPNModel("vgg16", {"img_size": 80, "anchor_count": 20}, max_batch=8)
+    for B in (1, 8):
+        assert m.head_launch_info(B) == {"route": "f32", "NB": 0, "pixels_per_workgroup": 0, "slabs": 1}
+    info = (ctypes.c_int * 4)()
+    for bad in (0, -1, 9):
+        assert lib.rpn_model_head_launch_info(m._h, bad, info) == L.RPN_ERR_INVALID
+        assert b"batch" in lib.rpn_last_error()
+        with pytest.raises(ValueError, match="batch"):
+            m.head_launch_info(bad)
+    assert lib.rpn_model_head_launch_info(None, 1, info) == L.RPN_ERR_INVALID
+    assert lib.rpn_model_head_launch_info(m._h, 1, None) == L.RPN_ERR_INVALID
+
+
 # ---- config --------------------------------------------------------------------------------
 def test_get_hyper_params_contract():
     import copy

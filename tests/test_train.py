@@ -191,6 +191,15 @@ def test_wgrad_kernel_register_budget(lib):
         assert name in tab, name
         v, ss, vs, scratch, l, _wg = tab[name]
         assert v <= vgpr and ss <= sspill and vs == 0 and scratch == 0 and l <= lds, (name, tab[name])
+    # every instantiation rpn_head_trainer_create accepts (NC = 5K, K = 1 .. 12): in the library, no scratch, no spilled VGPR,
+    # LDS = the dZ rows of one chunk (kChunkRows = 64 for the weight gradient, 16 for the data gradient).  head_dgrad_kernel runs
+    # 512-thread workgroups: above 256 registers it cannot be launched, and <50> takes exactly 256
+    for nc in range(5, 65, 5):
+        for name, vgpr, lds in (("head_wgrad_kernel<%d>" % nc, 512, 64 * nc * 4), ("head_dgrad_kernel<%d>" % nc, 256, 16 * nc * 4)):
+            assert name in tab, name
+            v, _ss, vs, scratch, l, wg = tab[name]
+            assert vs == 0 and scratch == 0 and v <= vgpr and l <= lds, (name, tab[name])
+            assert wg == (256 if "wgrad" in name else 512), (name, wg)
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------------

@@ -64,6 +64,8 @@ void pack_head_weights_host(const float *w, int ld, int ncols, float *dst);
 hipError_t launch_rpn_head(const float *x, long long P, const float *w_packed, const float *bias, int n_reg, int n_cls,
                            float *reg, float *cls, hipStream_t stream, int n_slabs = 1, long long slab_floats = 0,
                            const float *conv_bias = nullptr);
+// which instantiation that launch runs (NB 16-column blocks; 32 | 16 | 4 pixels per workgroup); false: the launcher refuses
+bool rpn_head_launch_form(long long P, int ncols, int n_slabs, int *NB, int *px_per_wg);
 
 // ---- 3x3 stride-1 'same' conv as Winograd F(2x2, 3x3) on the float32 MFMA (conv_wino_kernels.hip; precision "f32w") ----
 // variant: 2 = F(2x2, 3x3), 4 = F(4x4, 3x3) on 16 x 32-pixel x 64-channel tiles, 16 = F(4x4, 3x3) on 16 x 16-pixel x 128-channel tiles

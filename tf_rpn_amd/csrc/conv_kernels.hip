@@ -738,19 +738,33 @@ rpn_head_kernel(const float *__restrict__ x, long long P, const float *__restric
 
 bool rpn_head_supported(int Cin, int ncols) { return Cin == 512 && ncols >= 1 && ncols <= 96; }
 
-hipError_t launch_rpn_head(const float *x, long long P, const float *w_packed, const float *bias, int n_reg, int n_cls,
-                           float *reg, float *cls, hipStream_t stream, int n_slabs, long long slab_floats, const float *conv_bias)
+// The instantiation launch_rpn_head runs for P pixels, ncols columns and n_slabs partial-sum slabs: NB = 16-column blocks,
+// px_per_wg = pixels a workgroup owns (32: MB = 2; 16: MB = 1; 4: MB = 1, PXV = 4).  false: a launch the launcher refuses.
+// The launcher takes its template arguments and its grid from HERE, so a query of the form cannot disagree with the launch.
+bool rpn_head_launch_form(long long P, int ncols, int n_slabs, int *NB, int *px_per_wg)
 {
-    if ((n_slabs != 1 && n_slabs != 2 && n_slabs != 4) || (n_slabs > 1 && !conv_bias)) return hipErrorInvalidValue;   // the kernel adds 1, 2 or 4 slabs, nothing else
-    const int ncols = n_reg + n_cls;
-    if (!rpn_head_supported(512, ncols) || P <= 0 || (P + 31) / 32 > 0x7fffffffll) return hipErrorInvalidValue;
+    if (n_slabs != 1 && n_slabs != 2 && n_slabs != 4) return false;    // the kernel adds 1, 2 or 4 slabs, nothing else
+    if (!rpn_head_supported(512, ncols) || P <= 0 || (P + 31) / 32 > 0x7fffffffll) return false;
     // a grid of fewer than 256 workgroups (one image): 16 pixels per workgroup instead of 32 -- its operand, up to four slabs of
     // 2 KB per pixel, is read at one CU's bandwidth per workgroup
     static const int mb1_max = RPN_LAB_KNOB("RPN_HEAD_MB1", 256);      // 32-pixel workgroups from this many on (16-pixel ones below)
     const int MB = (P + 31) / 32 < mb1_max ? 1 : 2;
     const bool px4 = MB == 1 && (P + 15) / 16 <= 64 && n_slabs > 1;     // <= 64 workgroups of up to four slabs: 4 pixels each instead
-    const dim3 grid((unsigned)(px4 ? (P + 3) / 4 : (P + 16 * MB - 1) / (16 * MB)));
-    const int NB = (ncols + 15) / 16;
+    *NB = (ncols + 15) / 16;
+    *px_per_wg = px4 ? 4 : 16 * MB;
+    return true;
+}
+
+hipError_t launch_rpn_head(const float *x, long long P, const float *w_packed, const float *bias, int n_reg, int n_cls,
+                           float *reg, float *cls, hipStream_t stream, int n_slabs, long long slab_floats, const float *conv_bias)
+{
+    if (n_slabs > 1 && !conv_bias) return hipErrorInvalidValue;
+    const int ncols = n_reg + n_cls;
+    int NB = 0, pxw = 0;
+    if (!rpn_head_launch_form(P, ncols, n_slabs, &NB, &pxw)) return hipErrorInvalidValue;
+    const bool px4 = pxw == 4;
+    const int MB = pxw == 32 ? 2 : 1;
+    const dim3 grid((unsigned)((P + pxw - 1) / pxw));
 #define RPN_HEAD(NB_)                                                                                                 \
     if (px4)                                                                                                          \
         hipLaunchKernelGGL((rpn_head_kernel<NB_, 1, 4>), grid, dim3(256), 0, stream, x, P, w_packed, bias, n_reg, n_cls, reg, cls,  \

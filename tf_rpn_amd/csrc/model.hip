@@ -958,6 +958,15 @@ extern "C" int rpn_model_set_layer(rpn_model *m, const char *name, const float *
 
 namespace rpn {
 
+// The split-K factor of a 3x3 layer at THIS batch size: > 1 only for rpn_conv feeding the slab-adding head, when its output tensor
+// has room for factor * B images (conv3x3_split16_ksplit says when it pays).  run_ops and rpn_model_head_launch_info both ask here.
+static int conv_ksplit_at(const rpn_model *m, const Op &op, int B)
+{
+    if (op.route != RT_SPLIT16 || !op.ksplit) return 1;
+    const int f = conv3x3_split16_ksplit(B, op.H, op.W, op.Cin, op.Cout, split_cout_pad(op.Cout));
+    return f > 1 && (size_t)f * B <= (size_t)m->tensors[op.out].slabs * m->max_batch ? f : 1;
+}
+
 // The first `n_ops` ops of the graph on stream s (all of them: the forward; fewer: the backbone of a training step, which keeps
 // the per-op timing out of it).  The caller has validated the arguments and called ensure_device.
 static int run_ops(rpn_model *m, const float *d_imgs, int B, float *d_reg, float *d_cls, hipStream_t s, size_t n_ops)
@@ -1032,11 +1041,9 @@ static int run_ops(rpn_model *m, const float *d_imgs, int B, float *d_reg, float
                                      op.out_f32, m->f16, op.pools_next, s, false);
             break;
         case RT_SPLIT16: {
-            // the split-K factor at THIS batch size: > 1 only for rpn_conv feeding the slab-adding head, when its output tensor has
-            // room for factor * B images (conv3x3_split16_ksplit says when it pays)
             const int cpad = split_cout_pad(op.Cout);
-            const int f = op.ksplit ? conv3x3_split16_ksplit(B, op.H, op.W, op.Cin, op.Cout, cpad) : 1;
-            if (f > 1 && (size_t)f * B <= (size_t)m->tensors[op.out].slabs * m->max_batch) {
+            const int f = conv_ksplit_at(m, op, B);
+            if (f > 1) {
                 // raw partial sums; the head adds the slabs (+ this layer's bias, ReLU)
                 head_slabs = f;
                 head_conv_bias = op.b_off;
@@ -1387,6 +1394,29 @@ extern "C" int rpn_model_get_activation(rpn_model *m, const char *name, float *d
     const size_t bytes = t.floats() * (size_t)m->max_batch * sizeof(float);
     RPN_REQUIRE(out_bytes >= bytes, "rpn_model_get_activation: %zu bytes needed, %zu given", bytes, out_bytes);
     return tensor_to_f32(m, ti, tensor_ptr(m, ti, nullptr), m->max_batch, d_out, as_stream(stream), "rpn_model_get_activation");
+}
+
+// Which form of the head a forward of B images runs: host arithmetic only.  The slab count comes from conv_ksplit_at (what run_ops
+// asks for the conv in front of the head), NB and the pixels per workgroup from rpn_head_launch_form (where launch_rpn_head takes
+// its template arguments from).
+extern "C" int rpn_model_head_launch_info(const rpn_model *m, int B, int info[4])
+{
+    RPN_REQUIRE(m && info, "rpn_model_head_launch_info: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_head_launch_info: batch %d outside [1, %d]", B, m->max_batch);
+    size_t hi = m->ops.size();
+    for (size_t i = 0; i < m->ops.size(); ++i)
+        if (m->ops[i].kind == OP_HEAD) hi = i;
+    RPN_REQUIRE(hi < m->ops.size(), "rpn_model_head_launch_info: the graph has no head");
+    const Op &op = m->ops[hi];
+    info[0] = op.route == RT_HEAD_SPLITK ? RPN_HEAD_ROUTE_SPLITK : RPN_HEAD_ROUTE_F32;
+    info[1] = info[2] = 0;
+    info[3] = 1;
+    if (op.route != RT_HEAD_SPLITK) return RPN_OK;
+    const int slabs = hi > 0 && m->ops[hi - 1].out == op.in ? conv_ksplit_at(m, m->ops[hi - 1], B) : 1;
+    RPN_REQUIRE(rpn_head_launch_form((long long)B * op.H * op.W, 5 * m->K, slabs, &info[1], &info[2]),
+                "rpn_model_head_launch_info: the head launcher refuses %d images of %d x %d pixels", B, op.H, op.W);
+    info[3] = slabs;
+    return RPN_OK;
 }
 
 // RoI pooling of the feature tap, read where the last forward left it: float32 NHWC, or the split form of the bf16x3 / f16x3 graphs

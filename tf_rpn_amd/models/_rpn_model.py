@@ -274,6 +274,14 @@ class RPNModel(object):
                         "launches": 0 if kernel.startswith("fused:") else 1})
         return out
 
+    def head_launch_info(self, batch):
+        """Which form of the head a forward of ``batch`` images runs (test hook; host arithmetic, nothing is launched) ->
+        {"route": "splitk" | "f32", "NB", "pixels_per_workgroup": 32 | 16 | 4, "slabs": 1 | 2 | 4} (zeros / 1 on "f32")."""
+        info = (ctypes.c_int * 4)()
+        L.check(L.lib().rpn_model_head_launch_info(self._h, int(batch), info), "rpn_model_head_launch_info")
+        return {"route": "splitk" if info[0] == 0 else "f32", "NB": int(info[1]), "pixels_per_workgroup": int(info[2]),
+                "slabs": int(info[3])}
+
     def profile_ms(self):
         """Mean milliseconds per op over the kept forwards -> (list, n_forwards)."""
         n = L.lib().rpn_model_num_ops(self._h)
