@@ -221,12 +221,14 @@ def test_shape_tables_reach_every_path(lib):
 
 # ---- GPU: guard bands ---------------------------------------------------------------------------------------------------------------------------
 class Band:
-    """n floats, 16-byte aligned, inside a device buffer whose every other word -- and, without data, every word -- is CANARY."""
+    """n floats, 16-byte aligned, inside a device buffer whose every other word -- and, without data, every word -- is `canary`
+    (CANARY unless a buffer is also read as float64: see test_gpu_backward_mnv2.py)."""
 
-    def __init__(self, n, data=None):
+    def __init__(self, n, data=None, canary=CANARY):
         assert n >= 1
         self.n = n
-        self.buf = torch.full((n + 2 * GUARD,), CANARY, dtype=torch.int32, device="cuda")
+        self.canary = canary
+        self.buf = torch.full((n + 2 * GUARD,), canary, dtype=torch.int32, device="cuda")
         self.view = self.buf[GUARD:GUARD + n].view(torch.float32)
         assert self.view.data_ptr() % 16 == 0
         if data is not None:
@@ -238,7 +240,7 @@ class Band:
         return L.ptr(self.view)
 
     def intact(self):
-        return bool((self.buf[:GUARD] == CANARY).all()) and bool((self.buf[GUARD + self.n:] == CANARY).all())
+        return bool((self.buf[:GUARD] == self.canary).all()) and bool((self.buf[GUARD + self.n:] == self.canary).all())
 
     def numpy(self, shape):
         return self.view.cpu().numpy().reshape(shape)
