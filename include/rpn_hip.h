@@ -240,6 +240,29 @@ int rpn_model_get_activation(rpn_model *m, const char *name, float *d_out, size_
 #define RPN_HEAD_ROUTE_SPLITK 0
 #define RPN_HEAD_ROUTE_F32 1
 int rpn_model_head_launch_info(const rpn_model *m, int B, int info[4]);
+/* debug / test hook: run the ops of the handle's own graph up to the one that writes tensor `name` -- at the handle's precision, on
+ * its production (fused) graph, no rpn_model_keep_activations needed -- and copy that tensor's first B images into d_out as NHWC
+ * float32 (rpn_model_get_activation(m, name, NULL, 0, shape, NULL) gives H, W, C).  A fused MobileNetV2 block's tensor carries the name
+ * of its projection, "block_<k>_project"; the stem block (Conv1 + expanded_conv) writes "expanded_conv_project".  Only the layers of
+ * those ops need weights.  RPN_ERR_INVALID for B outside [1, max_batch], for a name no op of this graph writes, and for a tensor the
+ * graph never holds as such (a conv whose 2 x 2 max-pool runs in its epilogue; rpn_conv where the head adds its split-K slabs). */
+int rpn_model_forward_to(rpn_model *m, const char *name, const float *d_imgs, int B, float *d_out, void *stream);
+/* debug / test hook: which form of the fused MobileNetV2 block that writes tensor `name` a forward of B images on this handle
+ * runs.  Host arithmetic only, nothing is launched; the launchers take their choice from the same functions.
+ *   info[0]  RPN_IR_ROUTE_*: the kernel family.  F16X3 decides per HANDLE (grid at max_batch) between ir_block_x3 and
+ *            ir_block_hrx3 for blocks 4 and 5; the float32 precisions decide per CALL between ir_block and ir_block_hr for block 3
+ *            (512 tiles at B), two kernels that add the same chunks in the same order
+ *   info[1]  expanded channels per chunk (F16X3 block 3: per handle, 48 up to 512 tiles at max_batch, 16 above)
+ *   info[2]  K-split factor: workgroups per tile, 1 | 2 | 3 | 4 | 6 (always 1 on the float32 routes); follows the grid at B, every
+ *            factor adds the same tree
+ *   info[3]  tiles over the B images (4 x 8 output pixels; RPN_IR_ROUTE_STEM: 8 x 16)
+ * RPN_ERR_INVALID for B outside [1, max_batch], for a name no op writes, and for an op that is not a fused block. */
+#define RPN_IR_ROUTE_IR_BLOCK 0
+#define RPN_IR_ROUTE_IR_BLOCK_HR 1
+#define RPN_IR_ROUTE_IR_BLOCK_X3 2
+#define RPN_IR_ROUTE_IR_BLOCK_HRX3 3
+#define RPN_IR_ROUTE_STEM 4
+int rpn_model_ir_launch_info(const rpn_model *m, const char *name, int B, int info[4]);
 /* algorithmic FLOPs (2*MACs) of one image through the conv stack */
 double rpn_model_flops_per_image(const rpn_model *m);
 /* per-op timing with HIP events recorded on the caller's stream around every launch of a forward:

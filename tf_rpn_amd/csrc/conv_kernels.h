@@ -96,6 +96,19 @@ hipError_t launch_dwconv3x3(const float *x, int B, int H, int W, int C, const fl
 // image) takes the place of the expand stage (stem + expanded_conv block).  Weights (BatchNorm folded): we [KP][cexp]
 // (KP = cin; stem: 28 = 27 im2col rows + a zero row), wd [9][cexp], wp [cexp][round_up(cout, 16)] + their biases.
 bool ir_block_supported(int cin, int cexp, int cout, int stride, bool residual);
+// The form one fused-block launch takes at B images: which kernel family, its chunk size (expanded channels per step), the
+// K-split factor (workgroups per tile) and the number of tiles.  One host function per launcher computes it -- ir_block_form,
+// ir_block_x3_form, ir_block_hrx3_form -- and the launcher only switches on the result; rpn_model_ir_launch_info (test hook)
+// reports the same value.  kernel == IR_K_NONE: the launcher refuses the shape.
+enum IrKernel { IR_K_NONE = -1, IR_K_PIPE = 0, IR_K_HR = 1, IR_K_X3 = 2, IR_K_HRX3 = 3, IR_K_STEM = 4 };   // >= 0: rpn_hip.h's RPN_IR_ROUTE_*
+struct IrForm {
+    int kernel = IR_K_NONE;
+    int ce = 0;                 // expanded channels per chunk
+    int ksplit = 1;             // workgroups per tile
+    long long tiles = 0;        // 4 x 8 output tiles (IR_K_STEM: th x 16) over the B images
+    int th = 4;                 // tile height
+};
+IrForm ir_block_form(int B, int cin, int cexp, int cout, int stride, bool residual, bool stem, int OH, int OW);
 hipError_t launch_ir_block(const float *x, int B, int H, int W, int cin, int cexp, int cout, int stride, bool residual,
                            bool stem, int pad, int OH, int OW, const float *we, const float *be, const float *wd,
                            const float *bd, const float *wp, const float *bp, float *out, hipStream_t s);
@@ -113,6 +126,7 @@ void pack_ir_x3_dw(const float *wd, const float *bd, int cexp, float *dst);
 // null = never split.  The kernel leaves the tickets at zero.
 size_t ir_block_x3_scratch_floats();
 int ir_block_x3_ksplit(long long tiles);
+IrForm ir_block_x3_form(int B, int H, int W, int cin, int cexp, int cout, bool residual, bool have_scratch);
 hipError_t launch_ir_block_x3(const float *x, int B, int H, int W, int cin, int cexp, int cout, bool residual,
                               const void *we, const float *be, const float *wd, const float *bd, const void *wp,
                               const float *bp, float scale_e, float scale_p, float *out, unsigned *status, float *scratch,
@@ -137,6 +151,7 @@ int ir_hrx3_chunk_for(int cin, int stride, long long tiles_at_max_batch);
 size_t ir_hrx3_project_floats(int cin, int cexp, int cout, int stride, int ce_ov = 0);
 void pack_ir_hrx3_expand(const float *w, int cin, int cexp, int stride, int shift, unsigned short *dst, int ce_ov = 0);
 void pack_ir_hrx3_project(const float *w, int cin, int cexp, int cout, int stride, int shift, unsigned short *dst, int ce_ov = 0);
+IrForm ir_block_hrx3_form(int B, int cin, int cexp, int cout, int stride, bool residual, int OH, int OW, bool have_scratch, int ce_ov = 0);
 hipError_t launch_ir_block_hrx3(const float *x, int B, int H, int W, int cin, int cexp, int cout, int stride, bool residual,
                                 int pad, int OH, int OW, const void *we, const float *be, const float *wd, const float *bd,
                                 const void *wp, const float *bp, float scale_e, float scale_p, float *out, unsigned *status,

@@ -2192,50 +2192,77 @@ int ir_block_hrx3_ksplit(int cin, long long tiles, bool have_scratch)
     return 1;
 }
 
+// Room of the handle's K-split scratch (ir_block_x3_scratch_floats: the partials of 128 tiles x 6 parts x 32 px x 96 channels, then
+// 1024 tickets) for `tiles` tiles of `ksplit` parts and coutp channels.  The split rules cannot reach either limit: a factor above 1
+// comes with at most 42 x 6, 85 x 3 or 128 x 2 tile parts (ir_block_x3_ksplit) and 64 x 4, 160 x 2 or 160 x 3 (ir_block_hrx3_ksplit),
+// i.e. at most 480 of the 768 parts and 160 of the 1024 tickets, and no block has more than 96 output channels.  The guard is for
+// the forced factors of laboratory builds (RPN_MN_KSPLIT), which come without a tile limit.
+static bool ir_ksplit_fits(long long tiles, int ksplit, int coutp)
+{
+    return tiles <= 1024 && (size_t)tiles * ksplit * 32 * coutp <= (size_t)128 * 6 * 32 * 96;
+}
+
+// What launch_ir_block_hrx3 runs (and rpn_model_ir_launch_info reports): the chunk size is the handle's (ce_ov) or the family's;
+// blocks 3 and 6 are K TREES (IrHrX3Args::ksplit) whose factor follows the grid at B.
+IrForm ir_block_hrx3_form(int B, int cin, int cexp, int cout, int stride, bool residual, int OH, int OW, bool have_scratch, int ce_ov)
+{
+    IrForm f;
+    if (!ir_block_hrx3_supported(cin, cexp, cout, stride, residual)) return f;
+    f.tiles = (long long)((OW + HR_T - 1) / HR_T) * ((OH + 3) / 4) * B;
+    if (f.tiles <= 0 || f.tiles > 0x7fffffffll) return f;
+    if (cin == 32 && stride == 1) f.ce = 48;         // (blocks 4, 5 on large grids: ir_block_hrx3_preferred)
+    else if (cin == 32) f.ce = ir_hrx3_b6() == 48 ? 48 : 16;
+    else if (cin == 16) f.ce = ir_hrx3_b1();
+    else f.ce = ir_hrx3_ce(cin, stride, ce_ov) == 48 ? 48 : 16;
+    const bool tree = stride == 2 && ((cin == 32 && f.ce == 48) || cin == 24);
+    f.ksplit = tree ? ir_block_hrx3_ksplit(cin, f.tiles, have_scratch) : 1;
+    if (f.ksplit > 1 && !ir_ksplit_fits(f.tiles, f.ksplit, (cout + 15) / 16 * 16)) f.ksplit = 1;
+    f.kernel = IR_K_HRX3;
+    return f;
+}
+
 hipError_t launch_ir_block_hrx3(const float *x, int B, int H, int W, int cin, int cexp, int cout, int stride, bool residual,
                                 int pad, int OH, int OW, const void *we, const float *be, const float *wd, const float *bd,
                                 const void *wp, const float *bp, float scale_e, float scale_p, float *out, unsigned *status,
                                 float *scratch, hipStream_t s, int ce_ov)
 {
-    if (!ir_block_hrx3_supported(cin, cexp, cout, stride, residual)) return hipErrorInvalidValue;
+    const IrForm f = ir_block_hrx3_form(B, cin, cexp, cout, stride, residual, OH, OW, scratch != nullptr, ce_ov);
+    if (f.kernel != IR_K_HRX3) return hipErrorInvalidValue;
     IrHrX3Args a{};
     a.x = x; a.out = out; a.we = reinterpret_cast<const u32x4 *>(we); a.wp = reinterpret_cast<const u32x4 *>(wp);
     a.be = be; a.wd = wd; a.bd = bd; a.bp = bp; a.scale_e = scale_e; a.scale_p = scale_p;
     a.B = B; a.H = H; a.W = W; a.OH = OH; a.OW = OW; a.pad = pad; a.status = status;
     a.tiles_x = (OW + HR_T - 1) / HR_T;
     a.tiles_y = (OH + 3) / 4;
-    const long long tiles = (long long)a.tiles_x * a.tiles_y * B;
-    if (tiles <= 0 || tiles > 0x7fffffffll) return hipErrorInvalidValue;
-    // blocks 3 and 6 are K TREES (IrHrX3Args::ksplit); the scratch is the fused x3 blocks' (partials, then 1024 tickets)
-    const bool tree = stride == 2 && (cin == 32 || cin == 24);
-    a.ksplit = tree ? ir_block_hrx3_ksplit(cin, tiles, scratch != nullptr) : 1;
-    const int coutp = (cout + 15) / 16 * 16;
-    if (a.ksplit > 1 && (tiles > 1024 || (size_t)tiles * a.ksplit * 32 * coutp > (size_t)128 * 6 * 32 * 96)) a.ksplit = 1;
+    a.ksplit = f.ksplit;
     a.part = scratch;
     a.tickets = scratch ? reinterpret_cast<unsigned *>(scratch + (size_t)128 * 6 * 32 * 96) : nullptr;
-    const long long nb = tiles * a.ksplit;
-#define RPN_HRX3(KS_, ...) hipLaunchKernelGGL((ir_block_hrx3_kernel<__VA_ARGS__, KS_>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a)
+    const long long nb = f.tiles * f.ksplit;
+    // the kernel is a function of the block (cin, stride) and of the form's chunk size and K-split factor, nothing else
+#define RPN_HRX3(...) hipLaunchKernelGGL((ir_block_hrx3_kernel<__VA_ARGS__>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a)
+    bool launched = true;
     if (cin == 32 && stride == 1) {                  // (blocks 4, 5 on large grids: ir_block_hrx3_preferred)
-        a.ksplit = 1;
-        hipLaunchKernelGGL((ir_block_hrx3_kernel<32, 192, 48, 32, 1, true>), dim3((unsigned)tiles), dim3(HR_THREADS), 0, s, a);
-    } else if (cin == 32 && ir_hrx3_b6() == 48) {
-        if (a.ksplit == 4) RPN_HRX3(4, 32, 192, 48, 64, 2, false, 4);
-        else if (a.ksplit == 2) RPN_HRX3(2, 32, 192, 48, 64, 2, false, 4);
-        else RPN_HRX3(1, 32, 192, 48, 64, 2, false, 4);
+        if (f.ce == 48 && f.ksplit == 1) RPN_HRX3(32, 192, 48, 32, 1, true); else launched = false;
+    } else if (cin == 32 && f.ce == 48) {
+        if (f.ksplit == 4) RPN_HRX3(32, 192, 48, 64, 2, false, 4, 4);
+        else if (f.ksplit == 2) RPN_HRX3(32, 192, 48, 64, 2, false, 4, 2);
+        else if (f.ksplit == 1) RPN_HRX3(32, 192, 48, 64, 2, false, 4, 1);
+        else launched = false;
     } else if (cin == 32) {
-        a.ksplit = 1;
-        hipLaunchKernelGGL((ir_block_hrx3_kernel<32, 192, 16, 64, 2, false, 4>), dim3((unsigned)tiles), dim3(HR_THREADS), 0, s, a);
-    }
-    else if (cin == 16 && ir_hrx3_b1() == 32) hipLaunchKernelGGL((ir_block_hrx3_kernel<16, 96, 32, 24, 2, false>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a);
-    else if (cin == 16 && ir_hrx3_b1() == 48) hipLaunchKernelGGL((ir_block_hrx3_kernel<16, 96, 48, 24, 2, false>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a);
-    else if (cin == 16) hipLaunchKernelGGL((ir_block_hrx3_kernel<16, 96, 16, 24, 2, false>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a);
-    else if (stride == 1 && ir_hrx3_ce(cin, stride, ce_ov) == 16) hipLaunchKernelGGL((ir_block_hrx3_kernel<24, 144, 16, 24, 1, true>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a);
-    else if (stride == 1) hipLaunchKernelGGL((ir_block_hrx3_kernel<24, 144, 48, 24, 1, true>), dim3((unsigned)nb), dim3(HR_THREADS), 0, s, a);
-    else if (ir_hrx3_ce(cin, stride, ce_ov) == 48) { if (a.ksplit == 3) RPN_HRX3(3, 24, 144, 48, 32, 2, false, 3); else RPN_HRX3(1, 24, 144, 48, 32, 2, false, 3); }
-    else if (a.ksplit == 3) RPN_HRX3(3, 24, 144, 16, 32, 2, false, 3);
-    else RPN_HRX3(1, 24, 144, 16, 32, 2, false, 3);
+        if (f.ce == 16 && f.ksplit == 1) RPN_HRX3(32, 192, 16, 64, 2, false, 4); else launched = false;
+    } else if (f.ksplit != 1 && !(cin == 24 && stride == 2 && f.ksplit == 3)) launched = false;
+    else if (cin == 16 && f.ce == 32) RPN_HRX3(16, 96, 32, 24, 2, false);
+    else if (cin == 16 && f.ce == 48) RPN_HRX3(16, 96, 48, 24, 2, false);
+    else if (cin == 16 && f.ce == 16) RPN_HRX3(16, 96, 16, 24, 2, false);
+    else if (cin == 16) launched = false;
+    else if (stride == 1 && f.ce == 16) RPN_HRX3(24, 144, 16, 24, 1, true);
+    else if (stride == 1 && f.ce == 48) RPN_HRX3(24, 144, 48, 24, 1, true);
+    else if (stride == 1) launched = false;
+    else if (f.ce == 48) { if (f.ksplit == 3) RPN_HRX3(24, 144, 48, 32, 2, false, 3, 3); else RPN_HRX3(24, 144, 48, 32, 2, false, 3, 1); }
+    else if (f.ce == 16) { if (f.ksplit == 3) RPN_HRX3(24, 144, 16, 32, 2, false, 3, 3); else RPN_HRX3(24, 144, 16, 32, 2, false, 3, 1); }
+    else launched = false;
 #undef RPN_HRX3
-    return hipGetLastError();
+    return launched ? hipGetLastError() : hipErrorInvalidValue;      // (a form no kernel was built for: never from ir_block_hrx3_form)
 }
 
 bool ir_block_x3_supported(int cin, int cexp, int cout, int stride, bool residual)
@@ -2312,25 +2339,37 @@ int ir_block_x3_ksplit(long long tiles)
 }
 size_t ir_block_x3_scratch_floats() { return (size_t)128 * 6 * 32 * 96 + 1024; }    // partials of <= 128 tiles x 6 parts x 32 px x 96 ch, then 1024 tickets
 
+// What launch_ir_block_x3 runs (and rpn_model_ir_launch_info reports): chunks of 32 expanded channels, the K-split factor of the grid at B
+IrForm ir_block_x3_form(int B, int H, int W, int cin, int cexp, int cout, bool residual, bool have_scratch)
+{
+    IrForm f;
+    if (!ir_block_x3_supported(cin, cexp, cout, 1, residual)) return f;
+    f.tiles = (long long)((W + IR_TW - 1) / IR_TW) * ((H + IR_TH - 1) / IR_TH) * B;
+    if (f.tiles <= 0 || f.tiles > 0x7fffffffll) return f;
+    f.ce = 32;
+    f.ksplit = have_scratch ? ir_block_x3_ksplit(f.tiles) : 1;
+    if (f.ksplit > 1 && !ir_ksplit_fits(f.tiles, f.ksplit, cout)) f.ksplit = 1;       // (not for any factor the rule returns: ir_ksplit_fits)
+    f.kernel = IR_K_X3;
+    return f;
+}
+
 hipError_t launch_ir_block_x3(const float *x, int B, int H, int W, int cin, int cexp, int cout, bool residual,
                               const void *we, const float *be, const float *wd, const float *bd, const void *wp,
                               const float *bp, float scale_e, float scale_p, float *out, unsigned *status, float *scratch,
                               hipStream_t s)
 {
-    if (!ir_block_x3_supported(cin, cexp, cout, 1, residual)) return hipErrorInvalidValue;
+    const IrForm f = ir_block_x3_form(B, H, W, cin, cexp, cout, residual, scratch != nullptr);
+    if (f.kernel != IR_K_X3) return hipErrorInvalidValue;
     IrX3Args a{};
     a.x = x; a.out = out; a.we = reinterpret_cast<const u32x4 *>(we); a.wp = reinterpret_cast<const u32x4 *>(wp);
     a.be = be; a.wd = wd; a.bd = bd; a.bp = bp; a.scale_e = scale_e; a.scale_p = scale_p;
     a.B = B; a.H = H; a.W = W; a.status = status;
     a.tiles_x = (W + IR_TW - 1) / IR_TW;
     a.tiles_y = (H + IR_TH - 1) / IR_TH;
-    const long long tiles = (long long)a.tiles_x * a.tiles_y * B;
-    if (tiles <= 0 || tiles > 0x7fffffffll) return hipErrorInvalidValue;
-    a.ksplit = scratch ? ir_block_x3_ksplit(tiles) : 1;
-    if (a.ksplit > 1 && (tiles > 1024 || (size_t)tiles * a.ksplit * 32 * cout > (size_t)128 * 6 * 32 * 96)) a.ksplit = 1;
+    a.ksplit = f.ksplit;
     a.part = scratch;
     a.tickets = scratch ? reinterpret_cast<unsigned *>(scratch + (size_t)128 * 6 * 32 * 96) : nullptr;
-    const long long nblocks = tiles * a.ksplit;
+    const long long nblocks = f.tiles * f.ksplit;
 #ifdef RPN_STAMP
     {
         const char *sel = getenv("RPN_IR_STAMP_OP");
@@ -2377,6 +2416,41 @@ bool ir_block_supported(int cin, int cexp, int cout, int stride, bool residual)
     return false;
 }
 
+// What launch_ir_block runs (and rpn_model_ir_launch_info reports): the stem's 8 x 16-tile kernel, blocks 1-3 on the
+// every-wave-in-every-phase kernel (block 3 only on grids of >= 512 tiles at B), everything else on the two-group pipeline.
+IrForm ir_block_form(int B, int cin, int cexp, int cout, int stride, bool residual, bool stem, int OH, int OW)
+{
+    IrForm f;
+    const long long tiles48 = (long long)((OW + IR_TW - 1) / IR_TW) * ((OH + IR_TH - 1) / IR_TH) * B;
+    if (stem) {
+        if (!(cin == 3 && cexp == 32 && cout == 16 && stride == 1 && !residual)) return f;
+        static const int stem8 = RPN_LAB_KNOB("RPN_MN_STEM8", 1);     // 0: the 4 x 8 tile pipeline
+        f.ce = 32;
+        if (stem8) {
+            f.th = stem8 == 4 ? 4 : 8;      // (4 x 16 tiles, six workgroups per CU: no faster at batch 8, slower at 1024 x 1024)
+            f.tiles = (long long)((OW + ST_TW - 1) / ST_TW) * ((OH + f.th - 1) / f.th) * B;
+            f.kernel = IR_K_STEM;
+        } else {
+            f.tiles = tiles48;
+            f.kernel = IR_K_PIPE;
+        }
+    } else {
+        if (!ir_block_supported(cin, cexp, cout, stride, residual)) return f;
+        f.tiles = tiles48;                  // (HR_T x 4 = IR_TW x IR_TH: both kernels tile alike)
+        // blocks 1-3 (16 / 24 input channels at 250 x 250 / 125 x 125) on the 4 x 8-tile, every-wave-in-every-phase kernel
+        // (six 256-thread workgroups per CU).  Batch 8, 500 x 500: 0.094 -> 0.059, 0.067 -> 0.055, 0.045 -> 0.035 ms (block 3
+        // only on grids of >= 512 tiles: at one 500 x 500 image the pipeline kernel is faster, 0.017 vs 0.021 ms).  Blocks
+        // 4-6 (32 channels in, smaller grids) are as fast or faster on the two-group pipeline: they stay there.
+        // Both kernels walk block 3's expanded channels in the same chunks of 16 and add them in the same order: the choice
+        // follows the grid at B without touching an image's bits (tests/test_gpu_mnv2_blocks.py forwards one image on both).
+        const bool hr = ir_hr_mode() && (cin == 16 || cin == 24) && (stride == 1 || cin == 16 || f.tiles >= 512);
+        f.kernel = hr ? IR_K_HR : IR_K_PIPE;
+        f.ce = cin == 16 ? 16 : (cin == 24 ? (stride == 1 ? 48 : 16) : ((cin == 32 && stride == 1) ? 32 : 48));
+    }
+    if (f.tiles <= 0 || f.tiles > 0x7fffffffll) f.kernel = IR_K_NONE;
+    return f;
+}
+
 // x: (B,H,W,cin) [stem: the (B,H,W,3) image]; weights as in IrArgs; pad = top/left zero padding of the depthwise
 // (stem: of Conv1).  Returns hipErrorInvalidValue for a block shape outside ir_block_supported().
 hipError_t launch_ir_block(const float *x, int B, int H, int W, int cin, int cexp, int cout, int stride, bool residual,
@@ -2391,10 +2465,11 @@ hipError_t launch_ir_block(const float *x, int B, int H, int W, int cin, int cex
         a.DH = (H + pad + 1 - 3) / 2 + 1;
         a.DW = (W + pad + 1 - 3) / 2 + 1;
     }
-    a.tiles_x = (OW + IR_TW - 1) / IR_TW;
-    a.tiles_y = (OH + IR_TH - 1) / IR_TH;
-    const long long nblocks = (long long)a.tiles_x * a.tiles_y * B;
-    if (nblocks <= 0 || nblocks > 0x7fffffffll) return hipErrorInvalidValue;
+    const IrForm f = ir_block_form(B, cin, cexp, cout, stride, residual, stem, OH, OW);
+    if (f.kernel == IR_K_NONE) return hipErrorInvalidValue;
+    a.tiles_x = f.kernel == IR_K_STEM ? (OW + ST_TW - 1) / ST_TW : (OW + IR_TW - 1) / IR_TW;
+    a.tiles_y = (OH + f.th - 1) / f.th;
+    const long long nblocks = f.tiles;
 #ifdef RPN_STAMP
     {   // RPN_IR_STAMP_OP="cin,stride" selects the block that records stamps in a -DRPN_STAMP build ("3,1": the stem)
         const char *sel = getenv("RPN_IR_STAMP_OP");
@@ -2405,38 +2480,17 @@ hipError_t launch_ir_block(const float *x, int B, int H, int W, int cin, int cex
 #define RPN_IR(KP_, CEXP_, CE_, COUT_, S_, RES_, STEM_)                                                              \
     hipLaunchKernelGGL((ir_block_kernel<KP_, CEXP_, CE_, COUT_, S_, RES_, STEM_>), dim3((unsigned)nblocks),          \
                        dim3(IR_THREADS), 0, s, a)
-    if (stem) {
-        if (!(cin == 3 && cexp == 32 && cout == 16 && stride == 1 && !residual)) return hipErrorInvalidValue;
-        static const int stem8 = RPN_LAB_KNOB("RPN_MN_STEM8", 1);     // 0: the 4 x 8 tile pipeline
-        if (stem8) {
-            const int th = stem8 == 4 ? 4 : 8;      // (4 x 16 tiles, six workgroups per CU: no faster at batch 8, slower at 1024 x 1024)
-            a.tiles_x = (OW + ST_TW - 1) / ST_TW;
-            a.tiles_y = (OH + th - 1) / th;
-            const long long nb8 = (long long)a.tiles_x * a.tiles_y * B;
-            if (nb8 <= 0 || nb8 > 0x7fffffffll) return hipErrorInvalidValue;
-            if (th == 8) hipLaunchKernelGGL(stem_block_kernel<8>, dim3((unsigned)nb8), dim3(ST_THREADS), 0, s, a);
-            else hipLaunchKernelGGL(stem_block_kernel<4>, dim3((unsigned)nb8), dim3(ST_THREADS), 0, s, a);
-        } else {
-            RPN_IR(28, 32, 32, 16, 1, false, true);
-        }
-    } else if (!ir_block_supported(cin, cexp, cout, stride, residual)) {
-        return hipErrorInvalidValue;
-    } else if (ir_hr_mode() && (cin == 16 || cin == 24) &&
-               (stride == 1 || cin == 16 || (long long)((OW + HR_T - 1) / HR_T) * ((OH + 3) / 4) * B >= 512)) {
-        // blocks 1-3 (16 / 24 input channels at 250 x 250 / 125 x 125) on the 4 x 8-tile, every-wave-in-every-phase kernel
-        // (six 256-thread workgroups per CU).  Batch 8, 500 x 500: 0.094 -> 0.059, 0.067 -> 0.055, 0.045 -> 0.035 ms (block 3
-        // only on grids of >= 512 tiles: at one 500 x 500 image the pipeline kernel is faster, 0.017 vs 0.021 ms).  Blocks
-        // 4-6 (32 channels in, smaller grids) are as fast or faster on the two-group pipeline: they stay there.
-        a.tiles_x = (OW + HR_T - 1) / HR_T;
-        a.tiles_y = (OH + 3) / 4;
-        const long long nbh = (long long)a.tiles_x * a.tiles_y * B;
-        if (nbh <= 0 || nbh > 0x7fffffffll) return hipErrorInvalidValue;
 #define RPN_IRHR(CIN_, CEXP_, CE_, COUT_, S_, RES_)                                                                    \
-    hipLaunchKernelGGL((ir_block_hr_kernel<CIN_, CEXP_, CE_, COUT_, S_, RES_, 4>), dim3((unsigned)nbh), dim3(HR_THREADS), 0, s, a)
+    hipLaunchKernelGGL((ir_block_hr_kernel<CIN_, CEXP_, CE_, COUT_, S_, RES_, 4>), dim3((unsigned)nblocks), dim3(HR_THREADS), 0, s, a)
+    if (f.kernel == IR_K_STEM) {
+        if (f.th == 8) hipLaunchKernelGGL(stem_block_kernel<8>, dim3((unsigned)nblocks), dim3(ST_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(stem_block_kernel<4>, dim3((unsigned)nblocks), dim3(ST_THREADS), 0, s, a);
+    } else if (stem) {
+        RPN_IR(28, 32, 32, 16, 1, false, true);
+    } else if (f.kernel == IR_K_HR) {
         if (cin == 16) RPN_IRHR(16, 96, 16, 24, 2, false);       // (32-channel chunks: fewer workgroups per CU, slower)
         else if (stride == 1) RPN_IRHR(24, 144, 48, 24, 1, true);
         else RPN_IRHR(24, 144, 16, 32, 2, false);
-#undef RPN_IRHR
     } else if (cin == 16) RPN_IR(16, 96, 16, 24, 2, false, false);
     else if (cin == 24 && stride == 1) RPN_IR(24, 144, 48, 24, 1, true, false);
     else if (cin == 24) RPN_IR(24, 144, 16, 32, 2, false, false);
@@ -2445,6 +2499,7 @@ hipError_t launch_ir_block(const float *x, int B, int H, int W, int cin, int cex
     else if (cin == 64 && cout == 64) RPN_IR(64, 384, 48, 64, 1, true, false);
     else if (cin == 64) RPN_IR(64, 384, 48, 96, 1, false, false);
     else RPN_IR(96, 576, 48, 96, 1, true, false);
+#undef RPN_IRHR
 #undef RPN_IR
     return hipGetLastError();
 }

@@ -1419,6 +1419,50 @@ extern "C" int rpn_model_head_launch_info(const rpn_model *m, int B, int info[4]
     return RPN_OK;
 }
 
+// Which form of the fused MobileNetV2 block writing tensor `name` a forward of B images runs: host arithmetic only.  The route is
+// the op's (decide_routes, per handle); chunk size, K-split factor and tile count come from the launcher's own form function
+// (ir_block_form / ir_block_x3_form / ir_block_hrx3_form), called with what run_ops hands the launcher -- the handle always owns the
+// K-split scratch on the f16x3 routes (ensure_device).
+extern "C" int rpn_model_ir_launch_info(const rpn_model *m, const char *name, int B, int info[4])
+{
+    RPN_REQUIRE(m && name && info, "rpn_model_ir_launch_info: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_ir_launch_info: batch %d outside [1, %d]", B, m->max_batch);
+    const Op *op = nullptr;
+    for (const Op &o : m->ops)
+        if (o.out >= 0 && m->tensors[o.out].name == name) op = &o;
+    RPN_REQUIRE(op, "rpn_model_ir_launch_info: no op writes a tensor named '%s'", name);
+    RPN_REQUIRE(op->kind == OP_IRBLOCK, "rpn_model_ir_launch_info: '%s' is not a fused MobileNetV2 block", name);
+    IrForm f;
+    switch (op->route) {
+    case RT_IR_HRX3: f = ir_block_hrx3_form(B, op->Cin, op->cexp, op->Cout, op->stride, op->ir_res, op->OH, op->OW, true, op->ir_ce); break;
+    case RT_IR_X3: f = ir_block_x3_form(B, op->H, op->W, op->Cin, op->cexp, op->Cout, op->ir_res, true); break;
+    case RT_IR: f = ir_block_form(B, op->Cin, op->cexp, op->Cout, op->stride, op->ir_res, op->ir_stem, op->OH, op->OW); break;
+    default: break;
+    }
+    RPN_REQUIRE(f.kernel != IR_K_NONE, "rpn_model_ir_launch_info: the launcher refuses block '%s' at %d images", name, B);
+    info[0] = f.kernel; info[1] = f.ce; info[2] = f.ksplit; info[3] = (int)f.tiles;
+    return RPN_OK;
+}
+
+// Test hook: the ops of the handle's own graph up to the one writing tensor `name` (model_features_at, as the trainers run a frozen
+// prefix), that tensor's first B images as NHWC float32 into d_out.  Works on the production graph: no kept activations needed.
+extern "C" int rpn_model_forward_to(rpn_model *m, const char *name, const float *d_imgs, int B, float *d_out, void *stream)
+{
+    RPN_REQUIRE(m && name && d_imgs && d_out, "rpn_model_forward_to: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_forward_to: batch %d outside [1, %d]", B, m->max_batch);
+    const int ti = tensor_by_name(m, name);
+    RPN_REQUIRE(ti >= 1 && !m->tensors[ti].external, "rpn_model_forward_to: no op of this graph writes a tensor named '%s'", name);
+    const size_t n = ops_through(m, ti);
+    RPN_REQUIRE(n > 0, "rpn_model_forward_to: no op of this graph writes a tensor named '%s'", name);
+    // (a conv whose epilogue pools writes the pool's tensor; a split-K rpn_conv leaves raw partial sums for the head to add)
+    RPN_REQUIRE(!m->ops[n - 1].pools_next && conv_ksplit_at(m, m->ops[n - 1], B) == 1,
+                "rpn_model_forward_to: tensor '%s' is never written as such by this graph at %d images", name, B);
+    for (const Param &p : m->params)
+        if (p.op >= 0 && (size_t)p.op < n)
+            RPN_REQUIRE(p.loaded, "rpn_model_forward_to: weights of layer '%s' were never set", p.name.c_str());
+    return model_features_at(m, name, d_imgs, B, d_out, as_stream(stream));
+}
+
 // RoI pooling of the feature tap, read where the last forward left it: float32 NHWC, or the split form of the bf16x3 / f16x3 graphs
 // (roi_kernels.hip joins hi + lo per corner exactly as split_to_f32_kernel does, so the result equals pooling the float32 copy)
 extern "C" int rpn_model_roi_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, const int *d_valid, float *d_out,

@@ -282,6 +282,31 @@ class RPNModel(object):
         return {"route": "splitk" if info[0] == 0 else "f32", "NB": int(info[1]), "pixels_per_workgroup": int(info[2]),
                 "slabs": int(info[3])}
 
+    IR_ROUTES = ("ir_block", "ir_block_hr", "ir_block_x3", "ir_block_hrx3", "stem")      # rpn_hip.h: RPN_IR_ROUTE_*
+
+    def ir_launch_info(self, name, batch):
+        """Which form of the fused MobileNetV2 block writing tensor ``name`` ("block_<k>_project", "expanded_conv_project") a forward
+        of ``batch`` images runs (test hook; host arithmetic shared with the launchers, nothing is launched) ->
+        {"route": one of ``IR_ROUTES``, "chunk": expanded channels per step, "ksplit": workgroups per tile, "tiles"}."""
+        info = (ctypes.c_int * 4)()
+        L.check(L.lib().rpn_model_ir_launch_info(self._h, name.encode(), int(batch), info), "rpn_model_ir_launch_info")
+        return {"route": self.IR_ROUTES[info[0]], "chunk": int(info[1]), "ksplit": int(info[2]), "tiles": int(info[3])}
+
+    def forward_to(self, name, imgs):
+        """The handle's own graph up to the op that writes tensor ``name``, at the handle's precision (test hook: no kept
+        activations needed) -> that tensor for the ``B`` images given, a fresh float32 CUDA tensor (B, H, W, C)."""
+        self._sync_head()
+        x, _ = L.to_device(imgs)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.img_size, self.img_size, 3):
+            raise ValueError("imgs must be (B,%d,%d,3) NHWC, got %s" % (self.img_size, self.img_size, tuple(x.shape)))
+        B = int(x.shape[0])
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("batch %d outside [1, %d]" % (B, self.max_batch))
+        shape = self.activation_shape(name)
+        out = torch.empty((B,) + tuple(shape[1:]), dtype=torch.float32, device="cuda")
+        L.check(L.lib().rpn_model_forward_to(self._h, name.encode(), L.ptr(x), B, L.ptr(out), L.stream_ptr()), "rpn_model_forward_to")
+        return out
+
     def profile_ms(self):
         """Mean milliseconds per op over the kept forwards -> (list, n_forwards)."""
         n = L.lib().rpn_model_num_ops(self._h)
