@@ -477,6 +477,60 @@ size_t rpn_conv3x3_wgrad_wide_workspace_bytes(int B, int H, int W, int Cin, int 
 int rpn_conv3x3_wgrad_wide(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw, float *d_db,
                            void *d_ws, size_t ws_bytes, void *stream);
 
+/* Training the backbone's backward in split float16 (rpn_head_trainer_set_backward_precision on a VGG16 trainer).  The trainer's
+ * forward stays exact float32, so the kept activations, the ReLU masks, the pool maxima and the losses are bit for bit those of the
+ * float32 step; the head's three layers (rpn_conv's weight gradient included), block1_conv1's weight gradient (Cin = 3: 37 GEMM rows),
+ * the max-pool backward and Adam stay float32 as well.  Every other 3x3 product of the backbone's backward -- each input gradient,
+ * the first one from rpn_conv's dS with its feature_grad addend included, and each weight + bias gradient -- runs on
+ * v_mfma_f32_16x16x32_f16 under the contract of "Training the head in split float16" below, applied to the implicit GEMMs:
+ *   Operands: an activation x enters as hi = f16(x), lo = f16(x - hi), round-to-nearest-even, unscaled; |x| > 65504 or a non-finite
+ *     value raises RPN_STATUS_F16_RANGE.  A gradient tensor dY enters as the split of dY * 2^t, ONE t per gradient tensor, t = 12 - e
+ *     with max|dY| = m 2^e, m in [0.5, 1), clamped to [-116, 100], NaNs skipped, 0 for an all-zero tensor; the SAME t serves the weight
+ *     gradient and the input gradient that read the same dY.  A kernel w enters as the split of w * 2^s, one s per layer over its
+ *     whole HWIO kernel (the forward rule of the head: 12 - e clamped to [-100, 24]).  Both maxima are found on the device (an integer
+ *     atomicMax on the bits), with no host round trip and no synchronisation.  Each product is lo*hi, hi*lo, hi*hi in that order per
+ *     step of 32 of the reduction, float32 accumulation inside the MFMA; lo*lo is dropped.  A non-finite gradient raises the flag, a
+ *     finite one of any magnitude does not.
+ *   dx (P x Cin) = 2^-(t + s) (im2col'(2^t dY) (P x 9 Cout)) (2^s W'), W'[r][s][co][ci] = W[2-r][2-s][ci][co], packed once per layer per
+ *     step into a hi / lo image.  The reduction runs over k = (3 r + s) Cout + co in steps of 32 from 0 (the tail of 9 Cout as zeros):
+ *     its order follows from the shape alone, is the same at both tile widths (128 x 128 | 128 x 64, chosen from the shape alone:
+ *     rpn_conv3x3_dgrad_x3_tile_n), and a pixel's result reads no other pixel's tile -- the same bits at B = 1 and inside a batch
+ *     whenever t is the same.  Epilogue: dx = mask > 0 ? fl32(acc * 2^a * 2^b + add) : 0, a + b = -(t + s) in halves of the same sign
+ *     (two exact factors, as the head's d_in); add and mask are optional, add == dx is allowed, every element is written once.
+ *   dW (9 Cin x Cout) = 2^-t (im2col(X)^T (2^t dY)), the reduction over the pixels: the leaves of rpn_conv3x3_wgrad_wide (fixed
+ *     ranges of pixels chosen from the shape alone), each walked in steps of 32 pixels from its start with its tail as zeros and
+ *     multiplied by 2^-t, then added in the float32 path's fixed pairwise tree.  db is one more row of the same GEMM, a row of ones
+ *     (hi = 1, lo = 0): db = 2^-t sum (hi + lo)(2^t dY) in the same leaves and tree.
+ *   No floating-point atomics: bit-identical from run to run.
+ *   rpn_head_trainer_set_backward_precision: RPN_PRECISION_F32 (the default: exactly the float32 launches, bit for bit) or
+ *     RPN_PRECISION_F16X3; BF16X3 and F32W are RPN_ERR_UNSUPPORTED, F16X3 on a head-only or a MobileNetV2 trainer is
+ *     RPN_ERR_UNSUPPORTED, any other value RPN_ERR_INVALID.  It needs no device and keeps the weights, Adam's moments and the step
+ *     count.  rpn_head_trainer_backward_precision reports it.  A VGG16 trainer allocates the image and the max / scale words with its
+ *     other buffers, whatever the precision: rpn_head_trainer_backward_x3_bytes bytes (9.4 MB for VGG16's 512 x 512 layers; 0 for a
+ *     trainer without a VGG16 span).
+ *   rpn_head_trainer_status: the sticky RPN_STATUS_F16_RANGE of the backward's products (0 before the first step); reset = 1 clears
+ *     it; synchronises `stream`.
+ *   rpn_conv3x3_dgrad_x3 / rpn_conv3x3_wgrad_wide_x3: the two products on their own, TEST AND TIMING ENTRIES like rpn_conv3x3_dgrad /
+ *     rpn_conv3x3_wgrad_wide (same shapes and tensors; d_mask, d_add as rpn_conv3x3_dgrad_add, either may be NULL).  Each call finds t
+ *     (and s) itself; neither allocates nor synchronises.  d_ws: *_workspace_bytes(...) bytes, 16-byte aligned -- the packed image or
+ *     the leaf slabs, plus 256 bytes of max / scale words.  d_dy, d_x 16-byte aligned; d_w 4-byte aligned (a 16-byte aligned d_w is
+ *     read with wider loads: the same bits).  d_status: a device word that receives
+ *     RPN_STATUS_F16_RANGE, or NULL.  dgrad: Cin % 4 == 0, Cout % 16 == 0.  wgrad: Cin % 4 == 0 (Cin = 3 is RPN_ERR_UNSUPPORTED:
+ *     block1_conv1 stays on rpn_conv3x3_wgrad_wide), Cout % 4 == 0, B H W < 2^31 - 64.
+ *   rpn_conv3x3_dgrad_x3_tile_n: A TEST HOOK like rpn_conv3x3_dgrad_tile_n -- the input-channel width (128 | 64) of the tile
+ *     rpn_conv3x3_dgrad_x3 runs a shape on, 0 for a bad shape; host only. */
+int rpn_head_trainer_set_backward_precision(rpn_head_trainer *t, int precision);
+int rpn_head_trainer_backward_precision(const rpn_head_trainer *t);
+size_t rpn_head_trainer_backward_x3_bytes(const rpn_head_trainer *t);
+int rpn_head_trainer_status(rpn_head_trainer *t, unsigned *flags, int reset, void *stream);
+size_t rpn_conv3x3_dgrad_x3_workspace_bytes(int Cin, int Cout);
+int rpn_conv3x3_dgrad_x3_tile_n(int B, int H, int W, int Cin);
+int rpn_conv3x3_dgrad_x3(const float *d_dy, const float *d_w, const float *d_mask, const float *d_add, int B, int H, int W, int Cin,
+                         int Cout, float *d_dx, unsigned *d_status, void *d_ws, size_t ws_bytes, void *stream);
+size_t rpn_conv3x3_wgrad_wide_x3_workspace_bytes(int B, int H, int W, int Cin, int Cout);
+int rpn_conv3x3_wgrad_wide_x3(const float *d_x, const float *d_dy, int B, int H, int W, int Cin, int Cout, float *d_dw, float *d_db,
+                              unsigned *d_status, void *d_ws, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * single conv layer, for kernel-level parity tests and micro-benchmarks.
  *   x (B,H,W,Cin) NHWC, w HWIO (device), bias (Cout, device, may be NULL).

@@ -5,6 +5,7 @@
     python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone-from block_7_expand [--batch 8] ...
     python scripts/train_step_bench.py --backbone mobilenet_v2 --train-backbone [--batch 8] ...     (the whole model; also vgg16)
     python scripts/train_step_bench.py --train-backbone --feature-grad ...       (any backbone-training leg: + the joint step)
+    python scripts/train_step_bench.py --backward-precision f16x3 [--batch 8] [--steps 10] [--warmup 2]    (VGG16, the whole model)
 
 Times on the device with HIP events around (a) a whole training step (backbone at the handle's precision + float32 head forward,
 losses, backward, Adam), (b) an evaluation step (no backward), (c) the 3x3 weight-gradient entry rpn_conv3x3_wgrad on the
@@ -21,6 +22,13 @@ With --train-backbone: compile(train_backbone=True), every layer of the backbone
 (a) and (b) for the whole-model trainer, the device memory the trainer allocated at its first step, and the three stride-2 kernels'
 single-layer entries on their largest layers (block_1_depthwise: 250 x 250 x 96 in, 125 x 125 out; Conv1: 500 x 500 x 3 in, 250 x
 250 x 32 out) with the bytes each must move and its rate.
+
+With --backward-precision f16x3 (VGG16, compile(train_backbone=True)): the float32 and the f16x3 training step of the same model in
+ONE process -- two trainers holding the same weights, timed with HIP events in interleaved rounds, the median of 5 rounds (as
+scripts/det_head_bench.py times the head) -- and per trained conv the single-layer entries of both arithmetics side by side
+(rpn_conv3x3_dgrad | rpn_conv3x3_dgrad_x3 with the mask, rpn_conv3x3_wgrad_wide | rpn_conv3x3_wgrad_wide_x3; the x3 entries include
+their max scan and, for the dgrad, the weight packing), with the effective TF/s of the split-float16 ones, and "d": per layer
+max|g_x3 - g_f32| / max|g_f32| of the kernel gradients of one step from the same weights and batch.
 
 With --feature-grad (a backbone-training leg): after the plain step, in the same process and with the same HIP-event method, the step
 in two halves with a fixed random second-stage gradient G (B,F,F,C) at the feature tap -- "ms_feature_grad_step":
@@ -203,6 +211,82 @@ def bench_backbone(train_from, precision, B, steps, warmup, feature_grad=False):
                  "layers": layers}, **joint)
 
 
+def median_rounds(fns, steps, warmup, rounds=5):
+    """{name: median over `rounds` of the ms per call}, the functions timed in turn inside every round (interleaved)"""
+    got = {k: [] for k in fns}
+    for r in range(rounds):
+        for k, fn in fns.items():
+            got[k].append(timed(fn, steps, warmup if r == 0 else 1))
+    return {k: float(np.median(v)) for k, v in got.items()}
+
+
+def bench_backward_x3(precision, B, steps, warmup):
+    """module docstring, --backward-precision f16x3"""
+    hp = train_utils.get_hyper_params("vgg16")
+    lib = L.lib()
+    models = {}
+    for bp in ("f32", "f16x3"):
+        model, _ = rpn_vgg16.get_model(hp, precision=precision, max_batch=B)
+        model.compile(learning_rate=1e-5, train_backbone=True, backward_precision=bp)
+        models[bp] = model
+    imgs, deltas, lab = step_inputs(models["f32"], hp, B)
+    losses = torch.empty(3, device="cuda")
+
+    def step(model):
+        L.check(lib.rpn_head_trainer_step(model._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(lab), 1, 1e-5, 0.9, 0.999, 1e-7, L.ptr(losses),
+                                          L.stream_ptr()), "rpn_head_trainer_step")
+
+    # one step each from the same weights: the per-layer distance of the gradients, and the losses, which must agree exactly
+    grads, first = {}, {}
+    for bp, model in models.items():
+        step(model)
+        torch.cuda.synchronize()
+        first[bp] = losses.cpu().numpy().copy()
+        grads[bp] = model.get_gradients()
+    assert first["f32"].tobytes() == first["f16x3"].tobytes(), "the two steps' losses differ"
+    d = {name: float(np.abs(grads["f16x3"][name]["kernel"].astype(np.float64) - grads["f32"][name]["kernel"]).max()
+                     / np.abs(grads["f32"][name]["kernel"]).max()) for name, _, _, _ in VGG16}
+    ms = median_rounds({bp: (lambda m=m: step(m)) for bp, m in models.items()}, steps, warmup)
+    status = models["f16x3"].train_status()
+    layers = []
+    H = hp["img_size"]
+    for i, (name, cin, cout, pool) in enumerate(VGG16):
+        f = 2.0 * 9 * cin * cout * B * H * H
+        x, dy = torch.randn((B, H, H, cin), device="cuda"), torch.randn((B, H, H, cout), device="cuda")
+        dw, db = torch.empty((3, 3, cin, cout), device="cuda"), torch.empty((cout,), device="cuda")
+        w = torch.randn((3, 3, cin, cout), device="cuda") * (2.0 / (9 * cin)) ** 0.5
+        sizes = [lib.rpn_conv3x3_wgrad_wide_workspace_bytes(B, H, H, cin, cout)]
+        if cin % 4 == 0:
+            sizes += [lib.rpn_conv3x3_wgrad_wide_x3_workspace_bytes(B, H, H, cin, cout), lib.rpn_conv3x3_dgrad_workspace_bytes(cin, cout),
+                      lib.rpn_conv3x3_dgrad_x3_workspace_bytes(cin, cout)]
+        ws = torch.empty(max(sizes), dtype=torch.uint8, device="cuda")
+        n, s = ws.numel(), L.stream_ptr
+        fns = {"ms_wgrad_f32": lambda: L.check(lib.rpn_conv3x3_wgrad_wide(L.ptr(x), L.ptr(dy), B, H, H, cin, cout, L.ptr(dw), L.ptr(db),
+                                                                          L.ptr(ws), n, s()), "rpn_conv3x3_wgrad_wide")}
+        if cin % 4 == 0:
+            dx = torch.empty((B, H, H, cin), device="cuda")
+            fns["ms_wgrad_x3"] = lambda: L.check(lib.rpn_conv3x3_wgrad_wide_x3(L.ptr(x), L.ptr(dy), B, H, H, cin, cout, L.ptr(dw), L.ptr(db),
+                                                                              None, L.ptr(ws), n, s()), "rpn_conv3x3_wgrad_wide_x3")
+            fns["ms_dgrad_f32"] = lambda: L.check(lib.rpn_conv3x3_dgrad(L.ptr(dy), L.ptr(w), L.ptr(x), B, H, H, cin, cout, L.ptr(dx),
+                                                                       L.ptr(ws), n, s()), "rpn_conv3x3_dgrad")
+            fns["ms_dgrad_x3"] = lambda: L.check(lib.rpn_conv3x3_dgrad_x3(L.ptr(dy), L.ptr(w), L.ptr(x), None, B, H, H, cin, cout, L.ptr(dx),
+                                                                         None, L.ptr(ws), n, s()), "rpn_conv3x3_dgrad_x3")
+        t = median_rounds(fns, max(2, steps // 2), 1)
+        row = {"layer": name, "H": H, "cin": cin, "cout": cout, "gflop": round(f / 1e9, 2), "d": float("%.3e" % d[name])}
+        row.update({k: round(v, 4) for k, v in t.items()})
+        for kind in ("wgrad", "dgrad"):
+            if "ms_%s_x3" % kind in t:
+                row["%s_x3_tflops" % kind] = round(f / t["ms_%s_x3" % kind] / 1e9, 1)
+                row["%s_speedup" % kind] = round(t["ms_%s_f32" % kind] / t["ms_%s_x3" % kind], 2)
+        layers.append(row)
+        del x, dy, w, ws
+        if pool:
+            H //= 2
+    return {"backbone": "vgg16", "train_backbone": True, "precision": precision, "batch": B, "ms_train_step_f32": round(ms["f32"], 3),
+            "ms_train_step_f16x3": round(ms["f16x3"], 3), "step_speedup": round(ms["f32"] / ms["f16x3"], 3),
+            "f16_range": status["f16_range"], "layers": layers}
+
+
 def bench_mobilenet_span(train_from, precision, B, steps, warmup, feature_grad=False):
     """MobileNetV2 from `train_from` (block_7_expand .. block_13_expand): ms per training / evaluation step, and each new kernel family's
     single-layer entry on the block_12 shape (96 -> 576 -> 96 at F x F) with its fraction of its own floor: bytes / 8 TB/s for the
@@ -311,11 +395,18 @@ def main():
     ap.add_argument("--feature-grad", action="store_true",
                     help="with --train-backbone / --train-backbone-from: also time the step in two halves with a second-stage gradient at "
                          "the feature tap (forward_for_training + apply_gradients(G))")
+    ap.add_argument("--backward-precision", default=None, choices=("f16x3",),
+                    help="VGG16, the whole model: time the float32 and the f16x3 backward step side by side, and the single-layer entries")
     args = ap.parse_args()
     if args.feature_grad and not (args.train_backbone or args.train_backbone_from):
         ap.error("--feature-grad needs a trained backbone span: --train-backbone or --train-backbone-from")
     L.require_gpu()
     fg = args.feature_grad
+    if args.backward_precision:
+        if args.backbone == "mobilenet_v2" or args.train_backbone_from or fg:
+            ap.error("--backward-precision times the whole VGG16 model's step: no --backbone mobilenet_v2, --train-backbone-from, --feature-grad")
+        print(json.dumps(bench_backward_x3(args.precision, args.batch, args.steps, args.warmup)), flush=True)
+        return
     if args.train_backbone:
         if args.train_backbone_from:
             ap.error("--train-backbone trains every layer: it cannot be combined with --train-backbone-from")

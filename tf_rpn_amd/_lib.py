@@ -115,6 +115,15 @@ _SIGNATURES = {
     "rpn_maxpool2x2_backward": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_conv3x3_wgrad_wide_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "rpn_conv3x3_wgrad_wide": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_head_trainer_set_backward_precision": (ctypes.c_int, [vp, ctypes.c_int]),
+    "rpn_head_trainer_backward_precision": (ctypes.c_int, [vp]),
+    "rpn_head_trainer_backward_x3_bytes": (ctypes.c_size_t, [vp]),
+    "rpn_head_trainer_status": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint), ctypes.c_int, vp]),
+    "rpn_conv3x3_dgrad_x3_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "rpn_conv3x3_dgrad_x3_tile_n": (ctypes.c_int, [ctypes.c_int] * 4),
+    "rpn_conv3x3_dgrad_x3": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_conv3x3_wgrad_wide_x3_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "rpn_conv3x3_wgrad_wide_x3": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "rpn_conv2d": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 10 + [vp, vp]),
     "rpn_maxpool2x2": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "rpn_dwconv3x3": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),

@@ -1,43 +1,14 @@
 // det_head_x3_kernels.hip -- the detection head's products in split float16 (RPN_PRECISION_F16X3; contract in include/rpn_hip.h,
 // host interface in det_head.h): the forward GEMM on v_mfma_f32_16x16x32_f16, the device-side weight packing and max|.| scan, and
 // for a head that TRAINS in split float16 the two backward GEMMs (fc_wgrad_x3_kernel "TN", fc_dgrad_x3_kernel "NT") and the kernel
-// that turns maxima into power-of-two scales on the device.  The head object and the ABI live in det_head_kernels.hip.
+// that turns maxima into power-of-two scales on the device.  The head object and the ABI live in det_head_kernels.hip; the device
+// helpers shared with the backbone's split-float16 backward (split, MFMA wrapper, tile, one reduction step) in x3_tile.h.
 #include <cstdint>
 
 #include "det_head.h"
+#include "x3_tile.h"
 
 namespace rpn {
-
-using x3_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using x3_f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// 8 floats -> the 16-byte piece of their hi halves and the piece of their lo halves (x - hi), round-to-nearest-even, unscaled:
-// conv_split_kernels.hip's split_piece<true>, both pieces at once.  `status` (may be null) receives RPN_STATUS_F16_RANGE when a
-// value does not fit float16 (|x| > 65504 or non-finite); fmaxf drops NaNs, so x * 0 accumulates to NaN for any NaN / inf.
-__device__ __forceinline__ void split8_x3(const float (&x)[8], uint4 &hi, uint4 &lo, unsigned *status)
-{
-    if (status) {
-        const float m = fmaxf(fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3]))),
-                              fmaxf(fmaxf(fabsf(x[4]), fabsf(x[5])), fmaxf(fabsf(x[6]), fabsf(x[7]))));
-        float nan_probe = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) nan_probe = fmaf(x[k], 0.0f, nan_probe);
-        if (!(m <= 65504.0f) || nan_probe != 0.0f) atomicOr(status, 1u /* RPN_STATUS_F16_RANGE */);
-    }
-    x3_f16x8 h, l;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        h[k] = (_Float16)x[k];
-        l[k] = (_Float16)(x[k] - (float)h[k]);
-    }
-    hi = __builtin_bit_cast(uint4, h);
-    lo = __builtin_bit_cast(uint4, l);
-}
-
-__device__ __forceinline__ x3_f32x4 mfma_x3(uint4 a, uint4 b, x3_f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(x3_f16x8, a), __builtin_bit_cast(x3_f16x8, b), c, 0, 0, 0);
-}
 
 // ---- forward GEMM on v_mfma_f32_16x16x32_f16 -----------------------------------------------------------------------------------------
 // out (M x N) = act(scale * (A (M x K float32, K contiguous) . W) + bias), W the packed image of det_head.h.
@@ -54,8 +25,6 @@ __device__ __forceinline__ x3_f32x4 mfma_x3(uint4 a, uint4 b, x3_f32x4 c)
 // Each accumulator takes, per step in k order, lo*hi, hi*lo, hi*hi: the order over K follows from K alone and a row's result reads
 // that row of A only.  Rows / columns beyond the matrix and k beyond K enter as zeros; stores are scalar and guarded, columns < split
 // to out0, the others to out1.
-constexpr int kX3BM = 128, kX3BN = 128, kX3BK = 32;
-
 __global__ void __launch_bounds__(256) fc_forward_x3_kernel(const float *__restrict__ A, const uint4 *__restrict__ Wp,
                                                            const float *__restrict__ bias, int M, int K, int N, int ld, int relu,
                                                            int split, float scale0, float scale1,
@@ -230,30 +199,6 @@ __global__ void __launch_bounds__(64) fc_scales_x3_kernel(const unsigned *__rest
     scales[2 * i + 1] = ldexpf(1.0f, -s);
 }
 
-// one step of 32 of the reduction from the LDS records: the forward's fragment reads and MFMA order
-__device__ __forceinline__ void x3_mma_step(const uint4 *__restrict__ As, const uint4 *__restrict__ Bs, x3_f32x4 (&acc)[4][4], int wm,
-                                            int wn, int l16, int q)
-{
-    uint4 ah[4], al[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = wm * 64 + 16 * i + l16, sw = (r >> 1) & 7;
-        ah[i] = As[r * 8 + (q ^ sw)];
-        al[i] = As[r * 8 + ((4 + q) ^ sw)];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = wn * 64 + 16 * j + l16, sw = (c >> 1) & 7;
-        const uint4 bh = Bs[c * 8 + (q ^ sw)], bl = Bs[c * 8 + ((4 + q) ^ sw)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][j] = mfma_x3(al[i], bh, acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][j] = mfma_x3(ah[i], bl, acc[i][j]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][j] = mfma_x3(ah[i], bh, acc[i][j]);
-    }
-}
-
 // "TN": out (K x N, leading dimension ldo) = 2^-t * (A^T (2^t DZ)), A (M x K) and DZ (M x N, leading dimension ldz) float32 with the
 // reduction index M STRIDED in both.  Tile rows are columns of A, tile columns are columns of DZ.  Threads 0-127 stage A, 128-255 DZ:
 // a thread loads eight rows (one octet of the step's 32) of one column quad as float4s -- 32 lanes read 512 contiguous bytes of a
@@ -411,11 +356,9 @@ __global__ void __launch_bounds__(256) fc_dgrad_x3_kernel(const float *__restric
         __syncthreads();
         cur ^= 1;
     }
-    // acc * 2^-(t + s) as two exact multiplications by 2^a 2^b, a + b = -(t + s) in halves of the same sign: 2^-(t + s) may leave
-    // float32's range as one factor, and 2^-t alone may overflow an accumulator that 2^-s brings back (a huge gradient, small weights)
-    const int ex = (int)((__float_as_uint(gscale[1]) >> 23) & 0xffu) + (int)((__float_as_uint(wscale[1]) >> 23) & 0xffu) - 254;
-    const int ea = ex / 2, eb = ex - ea;
-    const float f1 = __uint_as_float((unsigned)(ea + 127) << 23), f2 = __uint_as_float((unsigned)(eb + 127) << 23);
+    // acc * 2^-(t + s) as two exact multiplications (x3_unscale_factors, x3_tile.h)
+    float f1, f2;
+    x3_unscale_factors(gscale[1], wscale[1], f1, f2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int col = k0 + wn * 64 + 16 * j + l16;

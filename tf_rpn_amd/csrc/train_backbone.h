@@ -1,5 +1,6 @@
-// train_backbone.h -- host-side interface of the VGG16 backbone backward kernels (train_backbone_kernels.hip; internal to
-// librpn_hip.so).  Every kernel is float32, writes each output once, and uses no floating-point atomics.  launch_wgrad_wide runs the
+// train_backbone.h -- host-side interface of the VGG16 backbone backward kernels (train_backbone_kernels.hip: float32;
+// train_backbone_x3_kernels.hip: the two 3x3 products in split float16; internal to librpn_hip.so).  Every kernel writes each output
+// once and uses no floating-point atomics.  launch_wgrad_wide runs the
 // 3x3 weight-gradient kernel of train_kernels.hip (train_head.h: launch_wgrad_slabs); the helpers the training kernel files share are
 // in train_common.h.
 #pragma once
@@ -30,6 +31,32 @@ int wgrad_wide_leaves(int B, int H, int W, int Cin, int Cout);
 size_t wgrad_wide_ws_floats(int B, int H, int W, int Cin, int Cout);
 hipError_t launch_wgrad_wide(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, float *db,
                              hipStream_t s);
+
+// the sum of the L leaf slabs of (9 cin_x + 1) x Cout floats in part, slab i with slab i + half down the fixed pairwise tree, ->
+// dw (3,3,Cin,Cout) without the padded channels and db (Cout) from row 9 cin_x: the second half of launch_wgrad_wide, which the
+// split-float16 weight gradient below shares
+hipError_t launch_wgrad_wide_sum(float *part, int L, int cin_x, int Cin, int Cout, float *dw, float *db, hipStream_t s);
+
+// ---- the same two products in split float16 (train_backbone_x3_kernels.hip; contract in include/rpn_hip.h) ---------------------------
+// A scale pair in device memory is {2^e, 2^-e}.  launch_scale_x3: max|x| over n floats (any 4-byte aligned x: float4 loads when x is
+// 16-byte aligned and n % 4 == 0, scalar ones otherwise -- the maximum is the same) into *bits
+// (zeroed here) and its pair into scale[0 .. 1] by the head's rule (launch_fc_scales_x3: gradient -> t in [-116, 100], else the
+// weights' s), all on the stream.
+hipError_t launch_scale_x3(const float *x, long long n, bool gradient, unsigned *bits, float *scale, hipStream_t s);
+// dgrad: gscale = the pair of dy's t (launch_scale_x3 over dy; the weight gradient that reads the same dy takes the same pair);
+// image: dgrad_x3_image_bytes(Cin, Cout) bytes that receive the flipped, transposed, split 2^s W'; wbits / wscale: one word and one
+// pair that receive max|w| and s.  add / mask as launch_conv3x3_dgrad; status (or null) receives RPN_STATUS_F16_RANGE.  dy must be
+// 16-byte aligned; w_hwio needs 4-byte alignment only (the trainer's master kernels follow the head's 5 K columns in one flat buffer):
+// the scan and the packing read an unaligned w with scalar loads.
+size_t dgrad_x3_image_bytes(int Cin, int Cout);
+bool conv3x3_dgrad_x3_wide_tile(int B, int H, int W, int Cin);
+hipError_t launch_conv3x3_dgrad_x3(const float *dy, const float *w_hwio, const float *mask, const float *add, int B, int H, int W, int Cin,
+                                   int Cout, const float *gscale, void *image, unsigned *wbits, float *wscale, float *dx, unsigned *status,
+                                   hipStream_t s);
+// wgrad: Cin % 4 == 0; the leaves, the slab layout (part: wgrad_wide_ws_floats(...) floats) and the tree are launch_wgrad_wide's; db
+// is the GEMM's row of ones
+hipError_t launch_wgrad_wide_x3(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, const float *gscale, float *part,
+                                float *dw, float *db, unsigned *status, hipStream_t s);
 
 // (P, 3) -> (P, 4) with a zero fourth channel: the first layer's input as wgrad_wide reads it
 hipError_t launch_pad_channels3to4(const float *x, long long P, float *out, hipStream_t s);

@@ -286,16 +286,21 @@ size_t wgrad_wide_ws_floats(int B, int H, int W, int Cin, int Cout)
     return (size_t)wgrad_wide_leaves(B, H, W, Cin, Cout) * (9 * (size_t)cin_x + 1) * Cout;
 }
 
-hipError_t launch_wgrad_wide(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, float *db,
-                             hipStream_t s)
+hipError_t launch_wgrad_wide_sum(float *part, int L, int cin_x, int Cin, int Cout, float *dw, float *db, hipStream_t s)
 {
-    const int cin_x = (Cin + 3) & ~3, M1 = 9 * cin_x + 1, L = wgrad_wide_leaves(B, H, W, Cin, Cout);
-    launch_wgrad_slabs(x, dy, B, H, W, cin_x, Cout, L, true, part, s);
-    const long long len = (long long)M1 * Cout;
+    const long long len = (9LL * cin_x + 1) * Cout;
     for (int half = L / 2; half >= 2; half /= 2)
         hipLaunchKernelGGL(wgrad_tree_kernel, dim3(grid_1d(half * len, kGridCap)), dim3(256), 0, s, part, len, half);
     hipLaunchKernelGGL(wgrad_wide_finish_kernel, dim3(grid_1d(len, kGridCap)), dim3(256), 0, s, part, L >= 2 ? 1 : 0, cin_x, Cin, Cout, dw, db);
     return hipGetLastError();
+}
+
+hipError_t launch_wgrad_wide(const float *x, const float *dy, int B, int H, int W, int Cin, int Cout, float *part, float *dw, float *db,
+                             hipStream_t s)
+{
+    const int cin_x = (Cin + 3) & ~3, L = wgrad_wide_leaves(B, H, W, Cin, Cout);
+    launch_wgrad_slabs(x, dy, B, H, W, cin_x, Cout, L, true, part, s);
+    return launch_wgrad_wide_sum(part, L, cin_x, Cin, Cout, dw, db, s);
 }
 
 __global__ void __launch_bounds__(256) pad_channels3to4_kernel(const float *__restrict__ x, long long P, float *__restrict__ out)

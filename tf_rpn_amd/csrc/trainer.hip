@@ -1,6 +1,7 @@
 // trainer.hip -- the training step of the RPN, host code only: the counterpart of the reference's trainer.py:54-69 (compile with
 // Adam(1e-5) and loss=[reg_loss, cls_loss], then fit).  The kernels, their launchers and the loss / Adam / BatchNorm forms are in
-// train_kernels.hip (train_head.h), train_backbone_kernels.hip (train_backbone.h) and train_mnv2_kernels.hip (train_mnv2.h).
+// train_kernels.hip (train_head.h), train_backbone_kernels.hip / train_backbone_x3_kernels.hip (train_backbone.h) and
+// train_mnv2_kernels.hip (train_mnv2.h).
 //
 // rpn_head_trainer_create trains the head (rpn_conv, rpn_reg, rpn_cls) on a frozen backbone:
 //   backbone (the handle's own ops and precision) -> X (B,F,F,Cin) float32
@@ -68,6 +69,8 @@ struct TrainerDevice {
     float *wt;                                   // a dgrad's flipped, transposed weights (any trained backbone)
     // the VGG16 backbone
     float *frozen, *pack, *wpart, *img4;
+    char *x3img;                                 // the split-float16 dgrad's weight image (the largest trained layer's)
+    unsigned *x3meta;                            // 64 words: max bits of a gradient (0) and a kernel (1), the sticky status (2), the pairs {2^t, 2^-t}, {2^s, 2^-s} from word 8
     float *act[13], *pool[13], *ping[2], *grad[2];
     // MobileNetV2
     float *bn, *bstat, *x0, *mpack, *mwpart;
@@ -94,6 +97,7 @@ struct rpn_head_trainer {
     // ---- the VGG16 backbone (rpn_model_trainer_create; backbone_*) ----
     // bb_from: the first trained conv (index into kVgg), -1 on a head-only trainer
     int bb_from = -1, img = 0;
+    int bw_precision = RPN_PRECISION_F32;        // the backbone backward's products (rpn_head_trainer_set_backward_precision)
     int hs[13] = {};                             // spatial side of each conv's input and output
     PackedShape ps_bb[13]{};
     // ---- MobileNetV2 (rpn_model_trainer_create / _create_full on a MobileNetV2 handle; mn_*) ----
@@ -322,10 +326,21 @@ size_t trainer_part_floats(const rpn_head_trainer *t)
     return std::max(std::max(head_backward_ws_floats(P, t->nc), wgrad_ws_floats(t->cin, 512)), colsum_ws_floats(P, 512));
 }
 
-// the backbone's buffers, sized by max_batch and the trained span (about 3.5 GB at batch 8, 500 x 500, from block1_conv1)
+// the backbone's buffers, sized by max_batch and the trained span (about 3.5 GB at batch 8, 500 x 500, from block1_conv1); the
+// split-float16 backward's image and words (backbone_x3_bytes) are allocated whatever the backward precision: setting it needs no device
+size_t backbone_x3_bytes(const rpn_head_trainer *t)
+{
+    size_t img = dgrad_x3_image_bytes(t->cin, 512);
+    for (int i = std::max(1, t->bb_from + 1); i < 13; ++i) img = std::max(img, dgrad_x3_image_bytes(kVgg[i].cin, kVgg[i].cout));
+    return img;
+}
+
 int backbone_device(rpn_head_trainer *t)
 {
     size_t pack = 0, ping = 0, grad = 0, wpart = 0;
+    RPN_HIP_CHECK(dev_alloc(t, &t->d.x3img, backbone_x3_bytes(t)));
+    RPN_HIP_CHECK(dev_alloc(t, &t->d.x3meta, 64));
+    RPN_HIP_CHECK(hipMemset(t->d.x3meta, 0, 64 * sizeof(unsigned)));
     for (int i = 0; i < 13; ++i) {
         if (i > 0) pack = std::max(pack, t->ps_bb[i].floats());
         if (!vgg_kept(t, i)) ping = std::max(ping, std::max(vgg_act_floats(t, i), kVgg[i].pool ? vgg_pool_floats(t, i) : 0));
@@ -491,21 +506,41 @@ hipError_t backbone_forward(rpn_head_trainer *t, const float *d_imgs, int B, hip
 // max-pool backward (+ the mask of the pooled conv) between layers, the weight and bias gradient of each trained conv.  add (B,F,F,cin)
 // or NULL: a second stage's gradient with respect to the tap (the post-ReLU block5_conv3 output); it joins the RPN's gradient in the
 // first dgrad's epilogue, before block5_conv3's ReLU mask: (dgrad + add) [feat > 0].
+// With bw_precision F16X3 every dgrad and every weight gradient but block1_conv1's (Cin = 3) runs in split float16
+// (train_backbone_x3_kernels.hip): one t per gradient tensor, found on the device before the two products that read it.
 hipError_t backbone_backward(rpn_head_trainer *t, int B, const float *add, hipStream_t s)
 {
     float *g = t->d.grad[0], *h = t->d.grad[1];
     const int F = t->hs[12];
-    hipError_t e = launch_conv3x3_dgrad(t->d.dS, param_dev(t, kConvK), t->d.act[12], add, B, F, F, t->cin, 512, t->d.wt, g, s);
+    const bool x3 = t->bw_precision == RPN_PRECISION_F16X3;
+    unsigned *meta = t->d.x3meta, *status = meta + 2;
+    float *sc = reinterpret_cast<float *>(meta + 8);
+    auto scale = [&](const float *dy, int H, int Cout) {
+        return x3 ? launch_scale_x3(dy, (long long)B * H * H * Cout, true, meta, sc, s) : hipSuccess;
+    };
+    auto dgrad = [&](const float *dy, const float *w, const float *mask, const float *a, int H, int Cin, int Cout, float *dx) {
+        if (!x3) return launch_conv3x3_dgrad(dy, w, mask, a, B, H, H, Cin, Cout, t->d.wt, dx, s);
+        return launch_conv3x3_dgrad_x3(dy, w, mask, a, B, H, H, Cin, Cout, sc, t->d.x3img, meta + 1, sc + 2, dx, status, s);
+    };
+    hipError_t e = scale(t->d.dS, F, 512);
+    if (e == hipSuccess) e = dgrad(t->d.dS, param_dev(t, kConvK), t->d.act[12], add, F, t->cin, 512, g);
     for (int i = 12; i >= t->bb_from && e == hipSuccess; --i) {
         const int H = t->hs[i], p = vgg_param(i);
         const float *x = i == 0 ? t->d.img4 : (kVgg[i - 1].pool ? t->d.pool[i - 1] : t->d.act[i - 1]);
-        e = launch_wgrad_wide(x, g, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d.wpart, param_grad(t, p + kKernel), param_grad(t, p + kBias), s);
+        const bool wgrad_x3 = x3 && kVgg[i].cin % 4 == 0;
+        if (wgrad_x3 || i > t->bb_from) e = scale(g, H, kVgg[i].cout);      // (block1_conv1 as the last layer: nobody reads the pair)
+        if (e != hipSuccess) break;
+        if (wgrad_x3)
+            e = launch_wgrad_wide_x3(x, g, B, H, H, kVgg[i].cin, kVgg[i].cout, sc, t->d.wpart, param_grad(t, p + kKernel),
+                                     param_grad(t, p + kBias), status, s);
+        else
+            e = launch_wgrad_wide(x, g, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d.wpart, param_grad(t, p + kKernel), param_grad(t, p + kBias), s);
         if (e != hipSuccess || i == t->bb_from) break;
         if (kVgg[i - 1].pool) {
-            e = launch_conv3x3_dgrad(g, param_dev(t, p), nullptr, nullptr, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d.wt, h, s);
+            e = dgrad(g, param_dev(t, p), nullptr, nullptr, H, kVgg[i].cin, kVgg[i].cout, h);
             if (e == hipSuccess) e = launch_maxpool2x2_backward(t->d.act[i - 1], h, B, t->hs[i - 1], t->hs[i - 1], kVgg[i - 1].cout, g, s);
         } else {
-            e = launch_conv3x3_dgrad(g, param_dev(t, p), t->d.act[i - 1], nullptr, B, H, H, kVgg[i].cin, kVgg[i].cout, t->d.wt, h, s);
+            e = dgrad(g, param_dev(t, p), t->d.act[i - 1], nullptr, H, kVgg[i].cin, kVgg[i].cout, h);
             std::swap(g, h);
         }
     }
@@ -942,6 +977,41 @@ extern "C" int rpn_head_trainer_backward(rpn_head_trainer *t, const float *d_img
 }
 
 extern "C" long long rpn_head_trainer_steps(const rpn_head_trainer *t) { return t ? t->t : -1; }
+
+// ---- C ABI: the arithmetic of the backbone's backward products ---------------------------------------------------------------------------
+extern "C" int rpn_head_trainer_set_backward_precision(rpn_head_trainer *t, int precision)
+{
+    const char *who = "rpn_head_trainer_set_backward_precision";
+    RPN_REQUIRE(t, "%s: null argument", who);
+    RPN_REQUIRE(precision >= RPN_PRECISION_F32 && precision <= RPN_PRECISION_F32W, "%s: unknown precision %d", who, precision);
+    if (precision == RPN_PRECISION_BF16X3 || precision == RPN_PRECISION_F32W)
+        return fail(RPN_ERR_UNSUPPORTED, "%s: the backward runs in RPN_PRECISION_F32 or RPN_PRECISION_F16X3 only", who);
+    if (precision == RPN_PRECISION_F16X3 && t->bb_from < 0)
+        return fail(RPN_ERR_UNSUPPORTED, t->mn_from >= 0 ? "%s: the MobileNetV2 backward has no split-float16 kernels (VGG16 only)"
+                                                         : "%s: this trainer trains the head only: there is no backbone backward to run in split float16",
+                    who);
+    t->bw_precision = precision;
+    return RPN_OK;
+}
+
+extern "C" int rpn_head_trainer_backward_precision(const rpn_head_trainer *t) { return t ? t->bw_precision : RPN_PRECISION_F32; }
+
+extern "C" size_t rpn_head_trainer_backward_x3_bytes(const rpn_head_trainer *t)
+{
+    return t && t->bb_from >= 0 ? backbone_x3_bytes(t) + 64 * sizeof(unsigned) : 0;
+}
+
+extern "C" int rpn_head_trainer_status(rpn_head_trainer *t, unsigned *flags, int reset, void *stream)
+{
+    RPN_REQUIRE(t && flags, "rpn_head_trainer_status: null argument");
+    *flags = 0;
+    if (!t->d.x3meta) return RPN_OK;          // no VGG16 span, or the trainer has not touched the device yet
+    const hipStream_t s = as_stream(stream);
+    RPN_HIP_CHECK(hipMemcpyAsync(flags, t->d.x3meta + 2, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (reset) RPN_HIP_CHECK(hipMemsetAsync(t->d.x3meta + 2, 0, sizeof(unsigned), s));
+    RPN_HIP_CHECK(hipStreamSynchronize(s));
+    return RPN_OK;
+}
 
 extern "C" int rpn_head_trainer_outputs(rpn_head_trainer *t, float *d_reg, float *d_cls, int B, void *stream)
 {

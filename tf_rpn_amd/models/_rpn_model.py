@@ -353,7 +353,7 @@ class RPNModel(object):
 
     # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
     def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None,
-                train_backbone=False):
+                train_backbone=False, backward_precision="f32"):
         """``rpn_model.compile(optimizer=tf.optimizers.Adam(learning_rate), loss=[reg_loss, cls_loss])`` (trainer.py:54-56).
 
         ``train_backbone_from=None`` (default) trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone,
@@ -378,6 +378,11 @@ class RPNModel(object):
 
         ``trainable`` names the head layers only and must be exactly the three of them.
 
+        ``backward_precision``: ``"f32"`` (default) or ``"f16x3"``.  ``"f16x3"`` runs the 3x3 products of a trained VGG16 span's
+        backward -- every input gradient and every weight gradient but ``block1_conv1``'s -- in split float16 on the 16-bit MFMA
+        (include/rpn_hip.h, "Training the backbone's backward in split float16"); the forward, the losses and the head's backward
+        stay exact float32.  It needs a VGG16 backbone span (``train_backbone_from`` / ``train_backbone``).
+
         Adam is TF 2.0's ApplyAdam (as recalled from its sources): alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t),
         m += (g - m)(1 - beta_1), v += (g^2 - v)(1 - beta_2), w -= alpha m / (sqrt(v) + epsilon), m = v = 0 at compile, t = the
         number of applied steps.  The trainer starts from the weights last given to ``set_weights`` / ``load_weights`` (or from
@@ -400,6 +405,16 @@ class RPNModel(object):
                                      % (train_backbone_from, self.backbone, MOBILENET_V2_TRAIN_FROM))
             elif train_backbone_from not in VGG16_CONVS:
                 raise ValueError("train_backbone_from=%r is not a VGG16 conv (one of %s)" % (train_backbone_from, VGG16_CONVS))
+        if backward_precision in ("bf16x3", "f32w"):
+            raise ValueError("backward_precision=%r: the backward has no %s kernels -- it runs in 'f32' or 'f16x3'"
+                             % (backward_precision, backward_precision))
+        if backward_precision not in ("f32", "f16x3"):
+            raise ValueError("backward_precision=%r is not a backward precision: 'f32' or 'f16x3'" % (backward_precision,))
+        if backward_precision == "f16x3" and (self.backbone != "vgg16" or train_backbone_from is None):
+            raise ValueError("backward_precision='f16x3' runs the VGG16 backbone's backward products in split float16: "
+                             + ("the %s backward has no such kernels" % self.backbone if self.backbone != "vgg16" else
+                                "this compile trains the head only, so there is no backbone backward (give train_backbone_from or "
+                                "train_backbone=True)"))
         self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
         if self._t:
             self._sync_head()       # layers the new trainer freezes run on the handle: they keep what the old one trained
@@ -423,6 +438,8 @@ class RPNModel(object):
         self._t = t
         self._pending = None
         self._train_from = train_backbone_from
+        L.check(L.lib().rpn_head_trainer_set_backward_precision(t, L.PRECISIONS[backward_precision]),
+                "rpn_head_trainer_set_backward_precision")
         for name in self._head:
             self._trainer_set(name)
         if train_backbone_from is not None:
@@ -431,6 +448,23 @@ class RPNModel(object):
             for name in self._mn:
                 if name in self.trained_layers():
                     self._trainer_set(name)
+
+    @property
+    def backward_precision(self):
+        """``"f32"`` or ``"f16x3"``: the arithmetic of the backbone's backward products (``compile(backward_precision=...)``)."""
+        if not self._t:
+            return "f32"
+        return {0: "f32", 2: "f16x3"}[L.lib().rpn_head_trainer_backward_precision(self._t)]
+
+    def train_status(self, reset=False):
+        """``{"f16_range": bool}``: whether a value of the split-float16 backward left float16's range (an activation with
+        |x| > 65504, a non-finite activation or gradient) since the last reset; synchronises the current stream."""
+        if not self._t:
+            raise RuntimeError("call compile() first")
+        flags = ctypes.c_uint(0)
+        L.check(L.lib().rpn_head_trainer_status(self._t, ctypes.byref(flags), 1 if reset else 0,
+                                                L.stream_ptr() if torch.cuda.is_available() else None), "rpn_head_trainer_status")
+        return {"f16_range": bool(flags.value & L.STATUS_F16_RANGE)}
 
     def trained_layers(self):
         """The layers a training step updates: the head, plus the backbone convs from ``train_backbone_from`` up, or all of them
