@@ -158,11 +158,13 @@ hipError_t launch_ir_block_hrx3(const float *x, int B, int H, int W, int cin, in
                                 float *scratch, hipStream_t s, int ce_ov = 0);   // scratch: ir_block_x3_scratch_floats() (K tree of blocks 3 / 6), or null
 
 // Device word into which the split-format writers launched from THIS host thread flag float16 range violations
-// (RPN_STATUS_F16_RANGE); null = no reporting.  rpn_model_forward sets it around its launches.
+// (RPN_STATUS_F16_RANGE); null = no reporting.  rpn_model_forward sets it around its launches.  (split_format.hip)
 void set_range_status(unsigned *p);
 unsigned *range_status();
 
-// ---- x3-split 16-bit MFMA path (conv_split_kernels.hip) ----------------------------------------
+// ---- x3-split 16-bit MFMA path -----------------------------------------------------------------
+// (weight packers, format conversions and max-pool: split_format.hip; launch_conv3x3_split16* and the conv3x3_split16_*
+// predicates: conv_split16_kernels.hip; launch_conv3x3_split and launch_vgg_block1: conv_split_kernels.hip)
 // SPLIT16 activation layout: [B][H][W][C/16][64 B] = {hi[0:8], lo[0:8], hi[8:16], lo[8:16]} (bf16 or f16).
 // Split weights: [Cin/16][9][cout_pad][64 B], cout_pad = 64 for Cout <= 64, else round_up(Cout, 128).
 inline int split_cout_pad(int Cout) { return Cout <= 64 ? 64 : (Cout + 127) / 128 * 128; }   // a multiple of the N tile
@@ -211,6 +213,7 @@ hipError_t launch_conv3x3_split(const void *x, const void *w, const float *bias,
 hipError_t launch_vgg_block1(const float *img, const void *w1, const float *b1, float scale1, const void *w2,
                              const float *b2, float scale2, void *out, int B, int H, int W, bool f16, hipStream_t s);
 
+// ---- first layer (conv_cin3_kernels.hip) --------------------------------------------------------
 // first layer (Cin = 3, 3x3): direct conv on the vector ALU; w (27,Cout) float32; out_fmt 0 = float32 NHWC,
 // 1 = SPLIT16.  Cout % 16 == 0.
 hipError_t launch_conv_cin3(const float *x, const float *w, const float *bias, void *out, int B, int H, int W,

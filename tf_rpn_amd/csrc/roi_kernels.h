@@ -4,7 +4,7 @@
 
 namespace rpn {
 
-// how the feature map is stored: float32 NHWC, or SPLIT16 (hi / lo 16-bit halves, conv_split_kernels.hip) in bfloat16 / float16
+// how the feature map is stored: float32 NHWC, or SPLIT16 (hi / lo 16-bit halves, split_format.hip) in bfloat16 / float16
 enum RoiSource { ROI_SRC_F32 = 0, ROI_SRC_SPLIT_BF16 = 1, ROI_SRC_SPLIT_F16 = 2 };
 
 // validates the geometry (RPN_ERR_INVALID, message prefixed with `who`), then launches; x is (B,H,W,C) in the form `src` names

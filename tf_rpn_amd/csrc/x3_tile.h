@@ -13,7 +13,7 @@ using x3_f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using x3_f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // 8 floats -> the 16-byte piece of their hi halves and the piece of their lo halves (x - hi), round-to-nearest-even, unscaled:
-// conv_split_kernels.hip's split_piece<true>, both pieces at once.  `status` (may be null) receives RPN_STATUS_F16_RANGE when a
+// split_conv.h's split_piece<true>, both pieces at once.  `status` (may be null) receives RPN_STATUS_F16_RANGE when a
 // value does not fit float16 (|x| > 65504 or non-finite); fmaxf drops NaNs, so x * 0 accumulates to NaN for any NaN / inf.
 __device__ __forceinline__ void split8_x3(const float (&x)[8], uint4 &hi, uint4 &lo, unsigned *status)
 {
