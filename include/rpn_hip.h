@@ -263,12 +263,33 @@ int rpn_model_forward_to(rpn_model *m, const char *name, const float *d_imgs, in
 #define RPN_IR_ROUTE_IR_BLOCK_HRX3 3
 #define RPN_IR_ROUTE_STEM 4
 int rpn_model_ir_launch_info(const rpn_model *m, const char *name, int B, int info[4]);
+/* debug / test hook: which form of the split-precision (BF16X3 / F16X3) op that writes tensor `name` a forward of B images on this
+ * handle runs.  Host arithmetic only, nothing is launched, no device is needed; the launchers take their choice from the same
+ * functions.  A pooled tensor ("block2_pool") whose 2 x 2 max-pool runs in a conv's epilogue is written by that conv.
+ *   info[0]  RPN_CONV_ROUTE_*: the kernel family.  The route is the HANDLE's; between the two conv3x3_split16 families and their
+ *            tile widths the launcher decides per CALL, from the grid at B
+ *   info[1]  channels per tile: 64 or 128 (the first layer: its Cout; RPN_CONV_ROUTE_MAXPOOL_SPLIT: 0)
+ *   info[2]  1 when the 2 x 2 max-pool runs in this kernel's epilogue, else 0
+ *   info[3]  K form: 0 one accumulation chain; 1 the K tree inside one workgroup (rpn_conv in front of the slab-adding head);
+ *            2 | 4 the K tree split over that many workgroups per tile (the head adds the slabs)
+ * RPN_ERR_INVALID for B outside [1, max_batch], for a name no op writes, and for an op that is not on a split route (a float32
+ * kernel, the head). */
+#define RPN_CONV_ROUTE_VGG_BLOCK1 0    /* block1_conv1 + block1_conv2 + block1_pool in one launch (F16X3) */
+#define RPN_CONV_ROUTE_FIRST_LAYER 1   /* the Cin = 3 kernels writing SPLIT16 (BF16X3: float32 arithmetic; F16X3: the 16-bit MFMA) */
+#define RPN_CONV_ROUTE_SPLIT 2         /* conv3x3_split, 32x32x16 MFMA */
+#define RPN_CONV_ROUTE_SPLIT16_REG 3   /* conv3x3_split16, 16x16x32 MFMA, register-staged */
+#define RPN_CONV_ROUTE_SPLIT16_DMA 4   /* conv3x3_split16, persistent LDS-DMA form */
+#define RPN_CONV_ROUTE_MAXPOOL_SPLIT 5 /* the un-fused 2 x 2 max-pool on SPLIT16 */
+int rpn_model_conv_launch_info(const rpn_model *m, const char *name, int B, int info[4]);
 /* algorithmic FLOPs (2*MACs) of one image through the conv stack */
 double rpn_model_flops_per_image(const rpn_model *m);
 /* per-op timing with HIP events recorded on the caller's stream around every launch of a forward:
  * keep the events of the last n_forwards forwards (0 = off), run forwards, then read the mean elapsed
  * milliseconds of each op over the kept forwards.
- * rpn_model_op_info names op i, the kernel that runs it and its algorithmic FLOPs / HBM bytes per image. */
+ * rpn_model_op_info names op i, the kernel that runs it and its algorithmic FLOPs / HBM bytes per image.  The kernel name is the
+ * one a forward of max_batch images runs: a conv3x3_split16 layer picks its form (register-staged or LDS-DMA, 64 or 128 channels
+ * wide) from the grid of each CALL, so a smaller batch may run another one -- rpn_model_conv_launch_info(m, name, B, ..) says which.
+ * Every form gives the same bits (the batch invariance of rpn_model_forward). */
 int rpn_model_set_profiling(rpn_model *m, int n_forwards);
 /* time only the ops with mask[i] != 0 (n = rpn_model_num_ops; NULL: every op); untimed ops read back as 0 ms */
 int rpn_model_set_profiling_mask(rpn_model *m, const unsigned char *mask, int n);

@@ -63,6 +63,7 @@ _SIGNATURES = {
     "rpn_model_head_launch_info": (ctypes.c_int, [vp, ctypes.c_int, c_int_p]),
     "rpn_model_forward_to": (ctypes.c_int, [vp, ctypes.c_char_p, vp, ctypes.c_int, vp, vp]),
     "rpn_model_ir_launch_info": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_int_p]),
+    "rpn_model_conv_launch_info": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_int_p]),
     "rpn_model_flops_per_image": (ctypes.c_double, [vp]),
     "rpn_model_set_profiling": (ctypes.c_int, [vp, ctypes.c_int]),
     "rpn_model_set_profiling_mask": (ctypes.c_int, [vp, vp, ctypes.c_int]),

@@ -183,6 +183,11 @@ hipError_t launch_conv3x3_split16(const void *x, const void *w, const float *bia
 // which 16x16x32 kernel launch_conv3x3_split16 picks for a layer: "dma,128" | "dma,64" (persistent LDS-DMA kernel,
 // tile width in channels) or "reg,128" | "reg,64" (register-staged kernels); nullptr: not launchable
 const char *conv3x3_split16_variant(int B, int H, int W, int Cin, int Cout, int cout_pad, bool pool);
+// the same for the call launch_conv3x3_split16 really makes: a K-tree layer (ktree) always takes the 64-wide persistent kernel
+inline const char *conv3x3_split16_launch_variant(int B, int H, int W, int Cin, int Cout, int cout_pad, bool pool, bool ktree)
+{
+    return ktree ? "dma,64" : conv3x3_split16_variant(B, H, W, Cin, Cout, cout_pad, pool);
+}
 // K tree of a layer whose consumer adds partial-sum slabs (rpn_conv -> the RPN head): the layer's value is (l0 + l1) + (l2 +
 // l3) over four fixed leaves of K at every batch size, computed by one workgroup per tile (launch_conv3x3_split16, ktree) or by
 // 2 / 4 (launch_conv3x3_split16_ksplit: slabs l0 + l1 | l2 + l3, or the four leaves; the head adds them in tree order).
@@ -207,6 +212,8 @@ hipError_t launch_maxpool_split(const void *x, int B, int H, int W, int C, bool 
 hipError_t launch_conv3x3_split(const void *x, const void *w, const float *bias, void *out, int B, int H, int W,
                                 int Cin, int Cout, int cout_pad, float out_scale, int act, bool out_f32, bool f16,
                                 bool pool, hipStream_t s, bool ktree = false);
+// the 32x32x16 kernel's tile for a layer, as launch_conv3x3_split picks it: 10 * rows + 64-channel columns (81 | 82 | 42 | 41)
+int conv3x3_split_tile(int B, int H, int W, int Cout, bool pool);
 
 // VGG16 block 1 (block1_conv1 + block1_conv2 + block1_pool) in one launch: the 64-channel full-resolution tensor stays
 // on chip.  w1 = pack_weights_cin3_mfma_host records, w2 = pack_weights_split_host records; out: SPLIT16 (B,H/2,W/2,64).

@@ -994,7 +994,7 @@ hipError_t launch_conv3x3_split16(const void *x, const void *w, const float *bia
     a.x = (const uint4 *)x; a.w = (const uint4 *)w; a.bias = bias; a.out = out;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.cout_pad = cout_pad;
     a.out_scale = out_scale; a.act = act; a.out_f32 = out_f32 ? 1 : 0;
-    const char *variant = ktree ? "dma,64" : conv3x3_split16_variant(B, H, W, Cin, Cout, cout_pad, pool);
+    const char *variant = conv3x3_split16_launch_variant(B, H, W, Cin, Cout, cout_pad, pool, ktree);
     if (!variant) return hipErrorInvalidValue;
     a.ktree = ktree ? 1 : 0;
     const long long big_blocks = (long long)((W + 31) / 32) * ((H + 7) / 8) * B * ((Cout + 127) / 128);

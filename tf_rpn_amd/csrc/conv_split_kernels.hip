@@ -453,21 +453,29 @@ static hipError_t launch_split_variant(const SplitConvArgs &a, hipStream_t s)
 // RPN_SPLIT_BBUF = 1 | 2 the number of weight buffers.  The instantiations that only RPN_SPLIT_BBUF, RPN_SPLIT_WAVES and
 // RPN_SPLIT_SMALL reach are compiled into the laboratory library alone.
 
+// 10 * tile rows + 64-channel columns of the 32x32x16 kernel's tile for a layer: 81 | 82 | 42 | 41 (launch_split_tiles launches it;
+// rpn_model_conv_launch_info reports its width)
+int conv3x3_split_tile(int B, int H, int W, int Cout, bool pool)
+{
+    static const int force_tile = RPN_LAB_KNOB("RPN_SPLIT_TILE", 0);
+    const long long mt8 = (long long)((W + 31) / 32) * ((H + 7) / 8) * B;
+    const long long mt4 = (long long)((W + 31) / 32) * ((H + 3) / 4) * B;
+    const int nt128 = (Cout + 127) / 128;
+    int tile;
+    if (Cout <= 64) tile = 81;
+    else if (mt8 * nt128 >= 512) tile = 82;
+    else if (mt4 * nt128 >= 512 || pool) tile = 42;
+    else tile = 41;
+    if (force_tile && Cout > 64 && !(pool && force_tile == 41)) tile = force_tile;
+    return tile;
+}
+
 template <bool F16, bool POOL>
 static hipError_t launch_split_tiles(const SplitConvArgs &a, hipStream_t s)
 {
     // tile choice: 64-wide N tiles for Cout <= 64; shorter / narrower tiles when the grid would not put
     // two workgroups on each of the 256 CUs
-    static const int force_tile = RPN_LAB_KNOB("RPN_SPLIT_TILE", 0);
-    const long long mt8 = (long long)((a.W + 31) / 32) * ((a.H + 7) / 8) * a.B;
-    const long long mt4 = (long long)((a.W + 31) / 32) * ((a.H + 3) / 4) * a.B;
-    const int nt128 = (a.Cout + 127) / 128;
-    int tile;
-    if (a.Cout <= 64) tile = 81;
-    else if (mt8 * nt128 >= 512) tile = 82;
-    else if (mt4 * nt128 >= 512 || POOL) tile = 42;
-    else tile = 41;
-    if (force_tile && a.Cout > 64 && !(POOL && force_tile == 41)) tile = force_tile;
+    const int tile = conv3x3_split_tile(a.B, a.H, a.W, a.Cout, POOL);
     // default buffers: two wherever LDS still admits two workgroups per CU (<= 80 KB)
     int bbuf = (tile == 82) ? 1 : 2;
 #ifdef RPN_LAB
@@ -480,6 +488,8 @@ static hipError_t launch_split_tiles(const SplitConvArgs &a, hipStream_t s)
     // 31x31x512, batch 8: 0.137 ms vs 0.126 ms for the default 4-wave 128 x 64 tiles, so it stays off.
     static const int small_mode = RPN_LAB_KNOB("RPN_SPLIT_SMALL", 0);
     if constexpr (!POOL) {
+        const long long mt4 = (long long)((a.W + 31) / 32) * ((a.H + 3) / 4) * a.B;
+        const int nt128 = (a.Cout + 127) / 128;
         if (tile == 41 && small_mode == 2 && mt4 * nt128 >= 256) return launch_split_variant<4, 2, 2, F16, false, 8>(a, s);
     }
 #endif

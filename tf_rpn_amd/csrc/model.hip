@@ -1252,6 +1252,8 @@ extern "C" int rpn_model_num_ops(const rpn_model *m) { return m ? (int)m->ops.si
 
 // name, kernel family ("conv128x128", "conv128x64", "conv128x32", "conv_generic*", "dwconv", "maxpool") and
 // algorithmic FLOPs (2*MACs, whole batch of the last profiled forward... per image here) of op i
+// The kernel named is the one a forward of max_batch images runs; a conv3x3_split16 layer chooses its form per call
+// (rpn_model_conv_launch_info reports it at any B).
 extern "C" int rpn_model_op_info(const rpn_model *m, int i, char *name, int name_len, char *kernel, int kernel_len,
                                  double *flops_per_image, double *bytes_per_image)
 {
@@ -1441,6 +1443,57 @@ extern "C" int rpn_model_ir_launch_info(const rpn_model *m, const char *name, in
     }
     RPN_REQUIRE(f.kernel != IR_K_NONE, "rpn_model_ir_launch_info: the launcher refuses block '%s' at %d images", name, B);
     info[0] = f.kernel; info[1] = f.ce; info[2] = f.ksplit; info[3] = (int)f.tiles;
+    return RPN_OK;
+}
+
+// Which form of the split-precision op writing tensor `name` a forward of B images runs: host arithmetic only.  The route is the op's
+// (decide_routes, per handle); the 16x16x32 kernel and its tile width come from conv3x3_split16_launch_variant with what run_ops
+// hands launch_conv3x3_split16 (the CALL's B, op.pools_next, op.ktree), the split over workgroups from conv_ksplit_at and, for the
+// kernel of a 2-way split, conv3x3_split16_ksplit_dma (launch_conv3x3_split16_ksplit's own test); the 32x32x16 kernel's tile from
+// conv3x3_split_tile.  A pooled tensor whose pool runs in a conv's epilogue (RT_FUSED) is written by that conv.
+extern "C" int rpn_model_conv_launch_info(const rpn_model *m, const char *name, int B, int info[4])
+{
+    RPN_REQUIRE(m && name && info, "rpn_model_conv_launch_info: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_conv_launch_info: batch %d outside [1, %d]", B, m->max_batch);
+    const Op *op = nullptr;
+    for (size_t i = 0; i < m->ops.size(); ++i) {
+        const Op &o = m->ops[i];
+        if (o.out < 0 || m->tensors[o.out].name != name) continue;
+        op = o.route == RT_FUSED && i > 0 ? &m->ops[i - 1] : &o;
+    }
+    RPN_REQUIRE(op, "rpn_model_conv_launch_info: no op writes a tensor named '%s'", name);
+    info[0] = -1; info[1] = info[2] = info[3] = 0;
+    switch (op->route) {
+    case RT_VGGB1: info[0] = RPN_CONV_ROUTE_VGG_BLOCK1; info[1] = 64; info[2] = 1; break;
+    case RT_CIN3: case RT_CIN3_MFMA:
+        if (op->out >= 0 && m->tensors[op->out].split_fmt) { info[0] = RPN_CONV_ROUTE_FIRST_LAYER; info[1] = op->Cout; }
+        break;
+    case RT_SPLIT:
+        info[0] = RPN_CONV_ROUTE_SPLIT;
+        info[1] = 64 * (conv3x3_split_tile(B, op->H, op->W, op->Cout, op->pools_next) % 10);
+        info[2] = op->pools_next ? 1 : 0;
+        break;
+    case RT_SPLIT16: {
+        const int cpad = split_cout_pad(op->Cout);
+        const int f = conv_ksplit_at(m, *op, B);
+        if (f > 1) {
+            info[0] = f == 2 && conv3x3_split16_ksplit_dma(B, op->H, op->W, op->Cin, op->Cout, cpad) ? RPN_CONV_ROUTE_SPLIT16_DMA
+                                                                                                      : RPN_CONV_ROUTE_SPLIT16_REG;
+            info[1] = 64; info[3] = f;
+            break;
+        }
+        const char *v = conv3x3_split16_launch_variant(B, op->H, op->W, op->Cin, op->Cout, cpad, op->pools_next, op->ktree);
+        RPN_REQUIRE(v, "rpn_model_conv_launch_info: the launcher refuses layer '%s' at %d images", name, B);
+        info[0] = v[0] == 'd' ? RPN_CONV_ROUTE_SPLIT16_DMA : RPN_CONV_ROUTE_SPLIT16_REG;
+        info[1] = v[4] == '6' ? 64 : 128;
+        info[2] = op->pools_next ? 1 : 0;
+        info[3] = op->ktree ? 1 : 0;
+        break;
+    }
+    case RT_POOL_SPLIT: info[0] = RPN_CONV_ROUTE_MAXPOOL_SPLIT; break;
+    default: break;
+    }
+    RPN_REQUIRE(info[0] >= 0, "rpn_model_conv_launch_info: '%s' is not written on a split-precision route", name);
     return RPN_OK;
 }
 

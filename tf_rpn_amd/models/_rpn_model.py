@@ -259,7 +259,9 @@ class RPNModel(object):
     def ops(self):
         """[{name, kernel, flops_per_image, bytes_per_image, arith, launches}] in graph order.  `arith` is the arithmetic the
         op's matrix work runs in ("f32" | "bf16x3" | "f16x3"); `launches` is 0 for a max-pool that runs inside the previous
-        conv's epilogue (kernel "fused:maxpool_split": no launch, no bytes of its own), else 1."""
+        conv's epilogue (kernel "fused:maxpool_split": no launch, no bytes of its own), else 1.  ``kernel`` is what a forward of
+        ``max_batch`` images runs: a ``conv3x3_split16`` layer picks its form from the grid of each call, so a smaller batch may
+        run another one (same bits) -- ``conv_launch_info(name, batch)`` reports the form at any batch size."""
         lib = L.lib()
         out = []
         nb, kb = ctypes.create_string_buffer(128), ctypes.create_string_buffer(128)
@@ -291,6 +293,17 @@ class RPNModel(object):
         info = (ctypes.c_int * 4)()
         L.check(L.lib().rpn_model_ir_launch_info(self._h, name.encode(), int(batch), info), "rpn_model_ir_launch_info")
         return {"route": self.IR_ROUTES[info[0]], "chunk": int(info[1]), "ksplit": int(info[2]), "tiles": int(info[3])}
+
+    CONV_ROUTES = ("vgg_block1", "first_layer", "split", "split16_reg", "split16_dma", "maxpool_split")   # rpn_hip.h: RPN_CONV_ROUTE_*
+
+    def conv_launch_info(self, name, batch):
+        """Which form of the split-precision op writing tensor ``name`` ("block2_conv1", "block2_pool", "rpn_conv", ...) a forward of
+        ``batch`` images runs (test hook; host arithmetic shared with the launchers, nothing is launched) ->
+        {"route": one of ``CONV_ROUTES``, "width": channels per tile, "pool": the 2 x 2 max-pool runs in the epilogue,
+        "kform": 0 one chain | 1 K tree in one workgroup | 2 | 4 K tree over that many workgroups}."""
+        info = (ctypes.c_int * 4)()
+        L.check(L.lib().rpn_model_conv_launch_info(self._h, name.encode(), int(batch), info), "rpn_model_conv_launch_info")
+        return {"route": self.CONV_ROUTES[info[0]], "width": int(info[1]), "pool": bool(info[2]), "kform": int(info[3])}
 
     def forward_to(self, name, imgs):
         """The handle's own graph up to the op that writes tensor ``name``, at the handle's precision (test hook: no kept
