@@ -655,7 +655,8 @@ int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const flo
  *   fc2: h2 = relu(h1 W2 + b2)    W2 (H1, H2)
  *   cls: logits = h2 Wc + bc      Wc (H2, C)    -> d_logits (M, C)    LOGITS: what rpn_roi_losses / rpn_roi_decode_scores take
  *   reg: deltas = h2 Wr + br      Wr (H2, 4C)   -> d_deltas (M, 4C)   class-specific
- *   Cf, H1, H2 multiples of 4; C >= 2.  No dropout (it would break the run-to-run bit identity of every training entry point).
+ *   Cf, H1, H2 multiples of 4; C >= 2.  Dropout after h1 and h2 is off by default (rate 0) and counter-based ("Dropout" below): it
+ *   keeps the run-to-run bit identity of every training entry point.
  * Arithmetic: exact float32 on v_mfma_f32_32x32x2_f32.  Forward: every output element is ONE fmaf chain in k order over the whole
  *   of K starting from +0, then + bias, then max(., 0) where there is a ReLU; no split of K.  A row's result depends on that row
  *   of the input and on the weights alone: the same RoI features give the same bits at any M and beside any other rows.
@@ -718,8 +719,9 @@ int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const flo
  *
  * Training the head in split float16 (rpn_det_head_set_train_precision on a trainable = 1 head, which is created in float32).  The
  * master weights, the gradients, the bias sums and Adam stay float32; every PRODUCT runs on v_mfma_f32_16x16x32_f16:
- *   Forward: every forward of such a head (kept or not) is the contract above, unchanged -- the same image, the same s per layer, the
- *     same kernel -- so its outputs are bit for bit those of an F16X3 inference head holding the same weights.
+ *   Forward: every forward of such a head that is NOT kept, and every kept forward at dropout rate 0, is the contract above,
+ *     unchanged -- the same image, the same s per layer, the same kernel -- so its outputs are bit for bit those of an F16X3
+ *     inference head holding the same weights.  (A kept forward at rate > 0 drops its hidden activations: "Dropout" below.)
  *   Gradient split: an output gradient dZ (M, N) enters every product as the hi / lo split (round-to-nearest-even, as above) of
  *     dZ * 2^t, ONE t per gradient tensor: dz (the cls | reg pair side by side, one t over its 5 C real columns), d_h2, d_h1.
  *     t = 12 - e where max|dZ| = m 2^e, m in [0.5, 1), over the M live rows and the real columns; 0 for an all-zero tensor; NaNs are
@@ -760,8 +762,53 @@ int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const flo
  *     dimension ldz); the columns N .. ldo - 1 of d_out are not written.  dgrad: d_out (M, K) = d_dz (M, N; ldz) d_w (K, N; ldw)^T,
  *     times [d_h > 0] when d_h (M, K) is given; s is taken over the K x N real entries of d_w.  K % 4 == 0 (wgrad), ldz % 4 == 0,
  *     ldw % 4 == 0, d_a, d_dz, d_w 16-byte aligned; M and N free.  d_status as for rpn_fc_forward_x3.
+ *
+ * Dropout after the two hidden layers of a trainable head (rpn_det_head_set_dropout; the default rate is 0, at which every kernel,
+ * launch and bit is what it is without this section).  Seeded and counter-based: the mask is a function of indices alone, there is
+ * no generator state and no mask tensor, and the backward evaluates no random number.
+ *   Generator: Philox4x32-10 as in Random123 and cuRAND.  Multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; key increments 0x9E3779B9,
+ *     0xBB67AE85; ten rounds, the key bumped between rounds; one round maps (c0, c1, c2, c3), (k0, k1) to
+ *     (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)).  Known answers (counter / key -> output):
+ *       0 0 0 0 / 0 0                                          -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *       ffffffff x 4 / ffffffff x 2                            -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *       243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   Which word belongs to which element: hidden layer l (0: fc1's output, 1: fc2's), flat row m = b R + r of the call, column n, the
+ *     head's dropout call number t.  Counter (n, m >> 2, l, t mod 2^32), key (seed & 0xffffffff, seed >> 32), the element's word is
+ *     output word m & 3.  (Both forward kernels' accumulator layouts give a thread four consecutive rows of one column starting at
+ *     a multiple of 4: one evaluation serves four stores.)
+ *   Mask and value: thr = min(llround(rate 2^32), 2^32 - 1), computed on the host in double.  An element is KEPT iff word >= thr, an
+ *     unsigned integer compare with no float conversion (a word equal to thr is kept).  scale = (float)(1.0 / (1.0 - rate)), a
+ *     double division rounded once.  The stored hidden activation is fl32(max(z, 0) * scale) where kept and exactly +0.0 where
+ *     dropped: Keras' Dropout / tf.nn.dropout, x * 1/(1 - rate) * mask.
+ *   When it applies: only on a forward whose activations are kept for a backward -- rpn_det_head_forward(keep = 1) on a trainable
+ *     head with rate > 0.  It is the identity in every other forward (keep = 0, rpn_det_head_forward_layer, any inference head), and
+ *     those do not advance t: validation runs with keep = 0.  t starts at 0 and increases by one per forward that applied dropout;
+ *     both hidden layers of that forward use the same t.
+ *   Backward: the stored activation is zero where the element was dropped, and scale >= 1 cannot take a positive value to zero, so
+ *     [a_stored > 0] is exactly [z > 0] AND kept.  The backward of a dropped layer is the backward above with one more factor:
+ *     d_pre = [a_stored > 0] ? fl32(d * scale) : 0, d being what the input-gradient product writes without dropout; in F16X3 the
+ *     factor comes after the two exact powers of two.  dW = in^T dZ reads the stored (dropped, scaled) activation: the correct
+ *     operand, unchanged.
+ *   What stays guaranteed: no floating-point atomics and fixed summation orders; the same bits on every run for the same (weights,
+ *     input, seed, t); the mask of flat row m is the same whether the call is shaped (1, 74) or (2, 37); at the same (seed, t) the
+ *     float32 head and the head that trains in F16X3 use the identical mask; at rate == 0 the dropout kernels (new kernels under
+ *     their own names) are never launched and no extra multiply happens.
+ *   rpn_det_head_set_dropout: 0 <= rate < 1 and finite, and a trainable = 1 head, otherwise RPN_ERR_INVALID.  Needs no device, drops
+ *     a kept forward, leaves t alone.  rpn_det_head_dropout_state reports rate, seed and t (the call number the NEXT dropped forward
+ *     will use); rpn_det_head_set_dropout_calls sets t, for resuming a run or repeating a call (trainable heads; it leaves a kept
+ *     forward alone, whose backward does not read t).
+ *   rpn_det_head_get_activation: copies the kept forward's stored hidden activation, "fc1" (M, H1) or "fc2" (M, H2), to d_out on the
+ *     device; RPN_ERR_INVALID for any other name or when no forward of M rows is kept.  It is what lets a caller see the mask.
+ *   rpn_dropout_forward: the contract's mask and scale on any tensor, d_out (M, N) = keep ? fl32(d_x * scale) : +0, no ReLU, out of
+ *     place, M and N free; `calls` is t, `layer` is l (>= 0).  rate as for set_dropout.
  * ---------------------------------------------------------------------------------- */
 typedef struct rpn_det_head rpn_det_head;
+int rpn_det_head_set_dropout(rpn_det_head *h, double rate, unsigned long long seed);
+int rpn_det_head_dropout_state(const rpn_det_head *h, double *rate, unsigned long long *seed, unsigned long long *calls);
+int rpn_det_head_set_dropout_calls(rpn_det_head *h, unsigned long long calls);
+int rpn_det_head_get_activation(rpn_det_head *h, const char *name, float *d_out, int M, void *stream);
+int rpn_dropout_forward(const float *d_x, int M, int N, double rate, unsigned long long seed, unsigned calls, int layer, float *d_out,
+                        void *stream);
 int rpn_det_head_set_train_precision(rpn_det_head *h, int precision);
 int rpn_det_head_train_precision(const rpn_det_head *h);
 int rpn_fc_wgrad_x3(const float *d_a, const float *d_dz, int M, int K, int N, int ldz, int ldo, float *d_out, unsigned *d_status,

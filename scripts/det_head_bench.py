@@ -20,11 +20,14 @@ widths 4096 and 1024:
     fc1 f16x3 (packed)  the first layer of the f16x3 head on its packed weights (rpn_det_head_forward_layer: bias and ReLU), events
                         around that one launch -- not the re-packing test entry rpn_fc_forward_x3
     fc1 torch.addmm     the same product through torch
+    head step dropout / head step f16x3 dropout   (--dropout RATE) the training step on two more heads of the same weights with
+                     DetectionHead(dropout=RATE): the dropout forward variants (one Philox evaluation per four stores) and the scaled
+                     masks of the backward, timed beside the rate-0 steps in the same rounds
     fc1 rpn_conv2d      the same product as a 1 x 1 conv on an (M, 1, 1, K) tensor: the library's way before rpn_fc_forward existed
                         (a single-layer test entry: every call allocates, packs the kernel for its tiles and synchronises)
 
 Also reports max |f16x3 - f32| of the logits and deltas and of the eight parameter gradients on the benchmark's inputs.  Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
-    python scripts/det_head_bench.py [--rounds 5] [--iters 3] [--json PATH]
+    python scripts/det_head_bench.py [--rounds 5] [--iters 3] [--dropout RATE] [--json PATH]
 """
 import argparse
 import json
@@ -62,7 +65,7 @@ def time_variants(variants, rounds, iters):
     return {n: (float(np.median(v)), float(np.min(v)), float(np.max(v))) for n, v in samples.items()}
 
 
-def bench_config(lib, channels, hidden, rounds, iters):
+def bench_config(lib, channels, hidden, rounds, iters, dropout=0.0):
     K1 = 7 * 7 * channels
     head = DetectionHead(C, pooling_size=(7, 7), channels=channels, hidden=(hidden, hidden), max_rois=M, seed=1)
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -145,6 +148,21 @@ def bench_config(lib, channels, hidden, rounds, iters):
     def step_t():
         fwd_t(), bwd_t(), adam_t()
 
+    # --dropout: two more trainable heads of the same weights, float32 and f16x3, at that rate
+    drop_steps = {}
+    if dropout > 0.0:
+        for name, precision in (("head step dropout", "f32"), ("head step f16x3 dropout", "f16x3")):
+            hd = DetectionHead(C, pooling_size=(7, 7), channels=channels, hidden=(hidden, hidden), max_rois=M, seed=1, dropout=dropout)
+            hd.compile(precision=precision)
+            lo, de = torch.empty_like(logits), torch.empty_like(deltas)
+
+            def step_d(hd=hd, lo=lo, de=de, name=name):
+                L.check(lib.rpn_det_head_forward(hd._h, L.ptr(pooled), M, 1, L.ptr(lo), L.ptr(de), stream), name)
+                L.check(lib.rpn_det_head_backward(hd._h, L.ptr(pooled), M, L.ptr(g_logits), L.ptr(g_deltas), L.ptr(g_pooled), stream), name)
+                L.check(lib.rpn_det_head_adam_step(hd._h, 1e-4, 0.9, 0.999, 1e-7, stream), name)
+
+            drop_steps[name] = step_d
+
     # the two new GEMMs alone at fc1's shape, and their float32 counterparts
     g_h1 = torch.randn((M, hidden), device="cuda", generator=gen) / M
     dw1, dx1 = torch.empty((K1, hidden), device="cuda"), torch.empty((M, K1), device="cuda")
@@ -192,6 +210,7 @@ def bench_config(lib, channels, hidden, rounds, iters):
                 "head adam + repack": adam_t, "head step": step, "head step f16x3": step_t, "fc1 wgrad f16x3": wgrad_x3,
                 "fc1 dgrad f16x3": dgrad_x3, "fc2 wgrad f32": wgrad2_f32, "fc2 wgrad f16x3": wgrad2_x3, "fc2 dgrad f32": dgrad2_f32,
                 "fc2 dgrad f16x3": dgrad2_x3}
+    variants.update(drop_steps)
     # the backward needs a kept forward; every timed backward reuses the last one, so in every round each head's forward comes before
     # its backward and its adam (which drops the kept forward) after it
     fwd()
@@ -206,7 +225,7 @@ def bench_config(lib, channels, hidden, rounds, iters):
     except (ValueError, RuntimeError) as e:
         conv_note = "rpn_conv2d refuses this shape: %s" % e
     order = ["head forward", "head forward f16x3", "head forward (training, f16x3)", "head backward", "head backward f16x3", "head adam",
-             "head adam + repack", "head step", "head step f16x3", "torch fwd+bwd+adam", "fc1 rpn_fc_forward", "fc1 f16x3 (packed)",
+             "head adam + repack", "head step", "head step dropout", "head step f16x3", "head step f16x3 dropout", "torch fwd+bwd+adam", "fc1 rpn_fc_forward", "fc1 f16x3 (packed)",
              "fc1 torch.addmm", "fc1 wgrad f16x3", "fc1 dgrad f16x3", "fc2 wgrad f32", "fc2 wgrad f16x3", "fc2 dgrad f32", "fc2 dgrad f16x3",
              "fc1 rpn_conv2d"]
     variants = {n: variants[n] for n in order if n in variants}
@@ -221,6 +240,9 @@ def bench_config(lib, channels, hidden, rounds, iters):
                  step_f16x3_over_torch=res["head step f16x3"][0] / res["torch fwd+bwd+adam"][0],
                  step_spread_f32=spread("head step"), step_spread_f16x3=spread("head step f16x3"), grad_max_abs_diff_and_max_abs=grad_diff,
                  grad_f16_range=grad_range, train_weights_bytes=head_t.memory_bytes()[0], train_workspace_bytes=head_t.memory_bytes()[1])
+    if drop_steps:
+        train.update(dropout_rate=dropout, step_dropout_over_rate0_f32=res["head step dropout"][0] / res["head step"][0],
+                     step_dropout_over_rate0_f16x3=res["head step f16x3 dropout"][0] / res["head step f16x3"][0])
     return dict(us_median_min=res, fc1_tflops=tf, f16x3_training=train, conv_note=conv_note, weights_bytes=w_bytes, workspace_bytes=ws_bytes,
                 f16x3_weights_bytes=x3_bytes[0], f16x3_workspace_bytes=x3_bytes[1], f16x3_minus_f32=diff,
                 f16x3_forward_speedup=res["head forward"][0] / res["head forward f16x3"][0],
@@ -231,6 +253,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--dropout", type=float, default=0.0, help="also time the training step at this dropout rate (0: no such leg)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     L.require_gpu()
@@ -239,7 +262,7 @@ def main():
     for backbone, channels in (("vgg16", 512), ("mobilenet_v2", 576)):
         for hidden in (4096, 1024):
             label = "%s K1=%d H=%d" % (backbone, 49 * channels, hidden)
-            results[label] = bench_config(lib, channels, hidden, args.rounds, args.iters)
+            results[label] = bench_config(lib, channels, hidden, args.rounds, args.iters, args.dropout)
             torch.cuda.empty_cache()
     print("%-32s %-30s %12s %12s %10s" % ("shape (M = %d)" % M, "variant", "median us", "min us", "TFLOP/s"))
     for label, row in results.items():
@@ -253,13 +276,16 @@ def main():
               "|f16x3 - f32| of the gradients, worst relative to max |g|: %s %.3e of %.3e; range flag %s; weights %.0f MB" % (
                   label, t["step_f32_over_f16x3"], 100 * t["step_spread_f32"], 100 * t["step_spread_f16x3"], t["step_f16x3_over_torch"],
                   worst[0], worst[1][0], worst[1][1], t["grad_f16_range"], t["train_weights_bytes"] / 1e6))
+        if "dropout_rate" in t:
+            print("%-32s training step at dropout %.2f / at rate 0: f32 %.3fx, f16x3 %.3fx" % (label, t["dropout_rate"], t["step_dropout_over_rate0_f32"],
+                                                                                       t["step_dropout_over_rate0_f16x3"]))
         d = row["f16x3_minus_f32"]
         print("%-32s f16x3 / f32: head forward %.2fx, fc1 %.2fx; max |f16x3 - f32| logits %.3e (max |logit| %.3e), deltas %.3e (max "
               "|delta| %.3e); range flag %s; f16x3 head weights %.0f MB" % (label, row["f16x3_forward_speedup"], row["f16x3_fc1_speedup"],
                                                                           d["logits"], d["max_abs_logits"], d["deltas"], d["max_abs_deltas"],
                                                                           d["f16_range"], row["f16x3_weights_bytes"] / 1e6))
     print("float32 matrix peak %.1f TFLOP/s; untuned LDS-tiled f32 MFMA GEMM (4096^3) %.1f TFLOP/s" % (PEAK_TF, GUIDE_TF))
-    line = json.dumps({"B": B, "R": R, "C": C, "rounds": args.rounds, "iters": args.iters, "peak_tflops": PEAK_TF, "guide_tflops": GUIDE_TF,
+    line = json.dumps({"B": B, "R": R, "C": C, "rounds": args.rounds, "iters": args.iters, "dropout": args.dropout, "peak_tflops": PEAK_TF, "guide_tflops": GUIDE_TF,
                        "results": results})
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)

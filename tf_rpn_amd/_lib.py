@@ -156,6 +156,12 @@ _SIGNATURES = {
     "rpn_det_head_train_precision": (ctypes.c_int, [vp]),
     "rpn_fc_wgrad_x3": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
     "rpn_fc_dgrad_x3": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp]),
+    "rpn_det_head_set_dropout": (ctypes.c_int, [vp, ctypes.c_double, ctypes.c_ulonglong]),
+    "rpn_det_head_dropout_state": (ctypes.c_int, [vp, c_double_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]),
+    "rpn_det_head_set_dropout_calls": (ctypes.c_int, [vp, ctypes.c_ulonglong]),
+    "rpn_det_head_get_activation": (ctypes.c_int, [vp, ctypes.c_char_p, vp, ctypes.c_int, vp]),
+    "rpn_dropout_forward": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_int,
+                                           vp, vp]),
     "rpn_evaluator_create": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, c_int_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                             ctypes.POINTER(vp)]),
     "rpn_evaluator_destroy": (None, [vp]),

@@ -10,6 +10,8 @@
 
 #include <cstddef>
 
+#include "dropout.h"
+
 namespace rpn {
 
 // out (M, N) = act(a (M, K) row-major . w (K, N) row-major with leading dimension ldw + bias (N) or nothing); relu != 0: max(., 0).
@@ -63,5 +65,25 @@ hipError_t launch_pack_pair_grad(const float *grad_logits, const float *grad_del
 
 // g (n floats, n % 4 == 0) <- g [h > 0], in place: the ReLU of the layer whose output h is
 hipError_t launch_relu_mask(float *g, const float *h, long long n, hipStream_t s);
+
+// ---- dropout after a hidden layer (dropout.h; contract in include/rpn_hip.h) -------------------------------------------------------------
+// New kernels under their own names: the kernels above are launched exactly as before whenever no dropout applies.
+// out (M, N) = keep ? fl32(max(a . w + bias, 0) * scale) : +0 -- launch_fc_forward with relu = 1 and split = N, dropped
+hipError_t launch_fc_forward_dropout(const float *a, const float *w, const float *bias, int M, int K, int N, int ldw,
+                                     const DropoutArgs &drop, float *out, hipStream_t s);
+
+// the same in split float16 with the scale in device memory (a training head's): launch_fc_forward_x3 with relu = 1 and split = N
+hipError_t launch_fc_forward_x3_dropout(const float *a, const void *packed, const float *bias, int M, int K, int N, int ld,
+                                        const float *dscale, const DropoutArgs &drop, float *out, unsigned *status, hipStream_t s);
+
+// g <- h > 0 ? fl32(g * scale) : 0, in place: the backward of a dropped layer whose STORED (dropped, scaled) output h is
+hipError_t launch_relu_scale_mask(float *g, const float *h, long long n, float scale, hipStream_t s);
+
+// launch_fc_dgrad_x3 with the dropped layer's factor after the two exact ones: out = h > 0 ? fl32(acc f1 f2 * scale) : 0 (h non-null)
+hipError_t launch_fc_dgrad_x3_dropout(const float *dz, const float *w, const float *h, int M, int K, int N, int ldz, int ldw,
+                                      const float *gscale, const float *wscale, float scale, float *out, unsigned *status, hipStream_t s);
+
+// out (M, N) = keep ? fl32(x * scale) : +0, out of place; M and N free
+hipError_t launch_dropout_forward(const float *x, int M, int N, const DropoutArgs &drop, float *out, hipStream_t s);
 
 }  // namespace rpn

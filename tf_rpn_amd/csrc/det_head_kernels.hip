@@ -5,6 +5,9 @@
 // (train_head.h) unchanged; after each input-gradient GEMM one in-place pass applies the ReLU mask (launch_relu_mask).  A trainable
 // head switched to split float16 (rpn_det_head_set_train_precision) runs the split forward and det_head_x3_kernels.hip's two backward
 // GEMMs instead, keeps the packed image beside its float32 master weights and refreshes it on the device (head_repack).
+// Dropout after the two hidden layers (dropout.h; rpn_det_head_set_dropout, rpn_dropout_forward) has kernels of its own, launched
+// only by a kept forward at rate > 0 and by that forward's backward: fc_forward_f32_dropout_kernel, relu_scale_mask_kernel,
+// dropout_forward_kernel here, the two split-float16 variants in det_head_x3_kernels.hip.
 #include <cstdint>
 #include <cstring>
 
@@ -41,15 +44,14 @@ constexpr int kFcBM = 128, kFcBN = 128, kFcBK = 32;
 constexpr long long kMaxGridY = 65535;
 constexpr long long kFcMaxRows = kMaxGridY * kFcBM, kHeadMaxRows = kMaxGridY * 64, kHeadMaxWidth = kMaxGridY * 64;
 
-__global__ void __launch_bounds__(256) fc_forward_f32_kernel(const float *__restrict__ A, const float *__restrict__ W,
-                                                            const float *__restrict__ bias, int M, int K, int N, int ldw, int relu,
-                                                            int split, float *__restrict__ out0, float *__restrict__ out1)
+// the main loop shared by fc_forward_f32_kernel and fc_forward_f32_dropout_kernel: acc <- the workgroup's tile of A W.  The thread's
+// indices come from the kernel, which needs them again in its epilogue.
+__device__ __forceinline__ void fc_forward_f32_mainloop(const float *__restrict__ A, const float *__restrict__ W, int M, int K, int ldw,
+                                                        const int tid, const int wm, const int wn, const int l32, const int kh,
+                                                        const int n0, const int m0, f32x16t (&acc)[2][2])
 {
     __shared__ __attribute__((aligned(16))) float As[2][kFcBK][kFcBM];
     __shared__ __attribute__((aligned(16))) float Bs[2][kFcBK][kFcBN];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, kh = lane >> 5;
-    const int n0 = blockIdx.x * kFcBN, m0 = blockIdx.y * kFcBM;
     const int nsteps = (K + kFcBK - 1) / kFcBK;
     const int ar = tid >> 3, akq = tid & 7, bk = tid >> 5, bq = tid & 31;
     float4 ra[4], rb[4];
@@ -75,7 +77,6 @@ __global__ void __launch_bounds__(256) fc_forward_f32_kernel(const float *__rest
             *reinterpret_cast<float4 *>(&Bs[buf][bk + 8 * i][4 * bq]) = rb[i];
         }
     };
-    f32x16t acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -104,6 +105,17 @@ __global__ void __launch_bounds__(256) fc_forward_f32_kernel(const float *__rest
         __syncthreads();
         cur ^= 1;
     }
+}
+
+__global__ void __launch_bounds__(256) fc_forward_f32_kernel(const float *__restrict__ A, const float *__restrict__ W,
+                                                            const float *__restrict__ bias, int M, int K, int N, int ldw, int relu,
+                                                            int split, float *__restrict__ out0, float *__restrict__ out1)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, kh = lane >> 5;
+    const int n0 = blockIdx.x * kFcBN, m0 = blockIdx.y * kFcBM;
+    f32x16t acc[2][2];
+    fc_forward_f32_mainloop(A, W, M, K, ldw, tid, wm, wn, l32, kh, n0, m0, acc);
     // accumulator element e: row 8 (e / 4) + 4 kh + e % 4, column lane % 32
     const int n1 = N - split;
 #pragma unroll
@@ -124,6 +136,58 @@ __global__ void __launch_bounds__(256) fc_forward_f32_kernel(const float *__rest
                     dst[(size_t)row * ld] = v;
                 }
             }
+    }
+}
+
+// The same product for a hidden layer that is dropped (dropout.h; contract in include/rpn_hip.h): out (M x N) =
+// keep ? fl32(max(A W + bias, 0) * scale) : +0.  An accumulator's elements 4 g .. 4 g + 3 are four consecutive rows of one column
+// starting at a multiple of 4, so one generator evaluation (counter (column, row / 4, layer, t)) serves four stores; it is made
+// inside the store loop, one group at a time, so that its state lives beside the 64 accumulators without scratch.
+__global__ void __launch_bounds__(256) fc_forward_f32_dropout_kernel(const float *__restrict__ A, const float *__restrict__ W,
+                                                                    const float *__restrict__ bias, int M, int K, int N, int ldw,
+                                                                    DropoutArgs drop, float *__restrict__ out)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l32 = lane & 31, kh = lane >> 5;
+    const int n0 = blockIdx.x * kFcBN, m0 = blockIdx.y * kFcBM;
+    f32x16t acc[2][2];
+    fc_forward_f32_mainloop(A, W, M, K, ldw, tid, wm, wn, l32, kh, n0, m0, acc);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int col = n0 + wn * 64 + 32 * j + l32;
+        if (col >= N) continue;
+        const float bv = bias ? bias[col] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int row0 = m0 + wm * 64 + 32 * i + 8 * g + 4 * kh;
+                if (row0 >= M) continue;
+                const unsigned keep = dropout_keep4(drop, (unsigned)col, (unsigned)row0 >> 2);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (row0 + r < M) {
+                        const float z = bias ? acc[i][j][4 * g + r] + bv : acc[i][j][4 * g + r];
+                        out[(size_t)(row0 + r) * N + col] = keep >> r & 1u ? fmaxf(z, 0.0f) * drop.scale : 0.0f;
+                    }
+            }
+    }
+}
+
+// out (M x N) = keep ? fl32(x * scale) : +0, out of place: the contract's mask and scale on any tensor.  One thread per four rows of
+// one column (one generator evaluation), the column running fastest: a wave reads and writes 256 contiguous bytes of each row.
+__global__ void __launch_bounds__(256) dropout_forward_kernel(const float *__restrict__ x, int M, int N, long long total, DropoutArgs drop,
+                                                             float *__restrict__ out)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long mq = i / N;
+        const int n = (int)(i - mq * N);
+        const unsigned keep = dropout_keep4(drop, (unsigned)n, (unsigned)mq);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const long long row = 4 * mq + r;
+            if (row < M) out[row * N + n] = keep >> r & 1u ? x[row * N + n] * drop.scale : 0.0f;
+        }
     }
 }
 
@@ -150,6 +214,22 @@ __global__ void __launch_bounds__(256) relu_mask_kernel(float4 *__restrict__ g, 
     }
 }
 
+// the mask of a DROPPED layer: g <- a > 0 ? fl32(g * scale) : 0.  The stored activation a is zero where the element was dropped and
+// positive where it was kept and z > 0 (scale >= 1 cannot take a positive value to zero), so no generator runs in the backward.
+__global__ void __launch_bounds__(256) relu_scale_mask_kernel(float4 *__restrict__ g, const float4 *__restrict__ h, long long n4,
+                                                             float scale)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        float4 v = g[i];
+        const float4 a = h[i];
+        v.x = a.x > 0.0f ? v.x * scale : 0.0f;
+        v.y = a.y > 0.0f ? v.y * scale : 0.0f;
+        v.z = a.z > 0.0f ? v.z * scale : 0.0f;
+        v.w = a.w > 0.0f ? v.w * scale : 0.0f;
+        g[i] = v;
+    }
+}
+
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 hipError_t launch_fc_forward(const float *a, const float *w, const float *bias, int M, int K, int N, int ldw, int relu, int split,
@@ -171,6 +251,28 @@ hipError_t launch_relu_mask(float *g, const float *h, long long n, hipStream_t s
 {
     hipLaunchKernelGGL(relu_mask_kernel, dim3(grid_1d(n / 4, kGridCap)), dim3(256), 0, s, reinterpret_cast<float4 *>(g),
                        reinterpret_cast<const float4 *>(h), n / 4);
+    return hipGetLastError();
+}
+
+hipError_t launch_fc_forward_dropout(const float *a, const float *w, const float *bias, int M, int K, int N, int ldw,
+                                     const DropoutArgs &drop, float *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(fc_forward_f32_dropout_kernel, dim3((N + kFcBN - 1) / kFcBN, (M + kFcBM - 1) / kFcBM), dim3(256), 0, s, a, w, bias,
+                       M, K, N, ldw, drop, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_relu_scale_mask(float *g, const float *h, long long n, float scale, hipStream_t s)
+{
+    hipLaunchKernelGGL(relu_scale_mask_kernel, dim3(grid_1d(n / 4, kGridCap)), dim3(256), 0, s, reinterpret_cast<float4 *>(g),
+                       reinterpret_cast<const float4 *>(h), n / 4, scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_dropout_forward(const float *x, int M, int N, const DropoutArgs &drop, float *out, hipStream_t s)
+{
+    const long long total = (long long)((M + 3) / 4) * N;
+    hipLaunchKernelGGL(dropout_forward_kernel, dim3(grid_1d(total, kGridCap)), dim3(256), 0, s, x, M, N, total, drop, out);
     return hipGetLastError();
 }
 
@@ -208,6 +310,11 @@ struct rpn_det_head {
     int train_precision = RPN_PRECISION_F32;
     unsigned *xmeta = nullptr;
     bool x_stale = false;
+    // Dropout after the two hidden layers (rpn_det_head_set_dropout; trainable heads): host state only.  drop_calls is the call
+    // number t of the NEXT dropped forward; kept_dropped: the kept forward applied dropout (at drop_rate: set_dropout drops it).
+    double drop_rate = 0.0;
+    unsigned long long drop_seed = 0, drop_calls = 0;
+    bool kept_dropped = false;
 };
 
 namespace {
@@ -374,12 +481,20 @@ bool head_trains_x3(const rpn_det_head *h) { return h->train_precision == RPN_PR
 // before a training head's image is read
 hipError_t head_fresh_image(rpn_det_head *h, hipStream_t s) { return head_trains_x3(h) && h->x_stale ? head_repack(h, s) : hipSuccess; }
 
-// one product of the head at its precision: layer 0 (fc1), 1 (fc2) or 2 (the cls | reg pair; out0 / out1)
-hipError_t head_launch_layer(rpn_det_head *h, int mat, const float *in, int M, float *out0, float *out1, hipStream_t s)
+// one product of the head at its precision: layer 0 (fc1), 1 (fc2) or 2 (the cls | reg pair; out0 / out1); `dropped`: a hidden
+// layer of a kept forward at rate > 0 -- the dropout variants, launched in no other case
+hipError_t head_launch_layer(rpn_det_head *h, int mat, const float *in, int M, float *out0, float *out1, hipStream_t s,
+                             bool dropped = false)
 {
     const int K = mat == 0 ? h->k1 : mat == 1 ? h->h1 : h->h2, N = mat == 0 ? h->h1 : mat == 1 ? h->h2 : 5 * h->c;
     const int ld = mat == 2 ? h->npad : N, relu = mat == 2 ? 0 : 1, split = mat == 2 ? h->c : N;
     const float *w = h->w + h->off[2 * mat], *b = h->w + h->off[2 * mat + 1];
+    if (dropped) {
+        const DropoutArgs drop = make_dropout_args(h->drop_rate, h->drop_seed, h->drop_calls, mat);
+        if (head_trains_x3(h))
+            return launch_fc_forward_x3_dropout(in, h->wx + h->xoff[mat], b, M, K, N, ld, head_scales(h, mat) + 1, drop, out0, h->status, s);
+        return launch_fc_forward_dropout(in, w, b, M, K, N, ld, drop, out0, s);
+    }
     if (head_trains_x3(h))
         return launch_fc_forward_x3(in, h->wx + h->xoff[mat], b, M, K, N, ld, relu, split, 1.0f, 1.0f, out0, out1, h->status, s,
                                     head_scales(h, mat) + 1, head_scales(h, mat == 2 ? 3 : mat) + 1);
@@ -509,6 +624,60 @@ extern "C" int rpn_det_head_set_train_precision(rpn_det_head *h, int precision)
 
 extern "C" int rpn_det_head_train_precision(const rpn_det_head *h) { return h ? h->train_precision : RPN_PRECISION_F32; }
 
+extern "C" int rpn_det_head_set_dropout(rpn_det_head *h, double rate, unsigned long long seed)
+{
+    const char *who = "rpn_det_head_set_dropout";
+    RPN_REQUIRE(h, "%s: null head", who);
+    RPN_REQUIRE(rate >= 0.0 && rate < 1.0, "%s: rate = %g must be finite and in [0, 1)", who, rate);      // (a NaN fails both compares)
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0 (dropout applies to kept forwards only)", who);
+    h->kept_rows = 0;            // a kept forward was made at the other rate or seed
+    h->drop_rate = rate, h->drop_seed = seed;
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_dropout_state(const rpn_det_head *h, double *rate, unsigned long long *seed, unsigned long long *calls)
+{
+    RPN_REQUIRE(h && rate && seed && calls, "rpn_det_head_dropout_state: null pointer");
+    *rate = h->drop_rate, *seed = h->drop_seed, *calls = h->drop_calls;
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_set_dropout_calls(rpn_det_head *h, unsigned long long calls)
+{
+    const char *who = "rpn_det_head_set_dropout_calls";
+    RPN_REQUIRE(h, "%s: null head", who);
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
+    h->drop_calls = calls;       // (a kept forward stays: its backward reads the stored activations, not t)
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_get_activation(rpn_det_head *h, const char *name, float *d_out, int M, void *stream)
+{
+    const char *who = "rpn_det_head_get_activation";
+    RPN_REQUIRE(h && name && d_out, "%s: null pointer", who);
+    const int i = layer_index(name);
+    RPN_REQUIRE(i == 0 || i == 1, "%s: layer '%s' is not a hidden layer (fc1, fc2)", who, name);
+    RPN_REQUIRE(M >= 1 && h->kept_rows == M, "%s: no kept forward of %d rows (the kept forward, if any, had %d rows)", who, M, h->kept_rows);
+    const size_t bytes = (size_t)M * (i == 0 ? h->h1 : h->h2) * sizeof(float);
+    RPN_HIP_CHECK(hipMemcpyAsync(d_out, i == 0 ? h->a1 : h->a2, bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
+    return RPN_OK;
+}
+
+extern "C" int rpn_dropout_forward(const float *d_x, int M, int N, double rate, unsigned long long seed, unsigned calls, int layer,
+                                   float *d_out, void *stream)
+{
+    const char *who = "rpn_dropout_forward";
+    RPN_REQUIRE(d_x && d_out, "%s: null pointer", who);
+    RPN_REQUIRE(M >= 1 && N >= 1, "%s: M = %d, N = %d", who, M, N);
+    RPN_REQUIRE(rate >= 0.0 && rate < 1.0, "%s: rate = %g must be finite and in [0, 1)", who, rate);
+    RPN_REQUIRE(layer >= 0, "%s: layer = %d", who, layer);
+    RPN_REQUIRE(d_x != d_out, "%s: the kernel is out of place", who);
+    RPN_REQUIRE_DEVICE();
+    const hipError_t e = launch_dropout_forward(d_x, M, N, make_dropout_args(rate, seed, calls, layer), d_out, as_stream(stream));
+    if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return RPN_OK;
+}
+
 extern "C" int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int M, int keep, float *d_logits, float *d_deltas,
                                     void *stream)
 {
@@ -522,12 +691,14 @@ extern "C" int rpn_det_head_forward(rpn_det_head *h, const float *d_pooled, int 
     if (st != RPN_OK) return st;
     const hipStream_t s = as_stream(stream);
     h->kept_rows = 0;                    // the activations of an earlier forward are overwritten from here on
+    const bool dropped = keep && h->drop_rate > 0.0;     // dropout is the identity in every forward that is not kept
     hipError_t e = head_fresh_image(h, s);
-    if (e == hipSuccess) e = head_launch_layer(h, 0, d_pooled, M, h->a1, nullptr, s);
-    if (e == hipSuccess) e = head_launch_layer(h, 1, h->a1, M, h->a2, nullptr, s);
+    if (e == hipSuccess) e = head_launch_layer(h, 0, d_pooled, M, h->a1, nullptr, s, dropped);
+    if (e == hipSuccess) e = head_launch_layer(h, 1, h->a1, M, h->a2, nullptr, s, dropped);
     if (e == hipSuccess) e = head_launch_layer(h, 2, h->a2, M, d_logits, d_deltas, s);
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
-    if (keep) h->kept_rows = M, h->kept_pooled = d_pooled;
+    if (keep) h->kept_rows = M, h->kept_pooled = d_pooled, h->kept_dropped = dropped;
+    if (dropped) h->drop_calls += 1;                     // both hidden layers of this forward used the same t
     return RPN_OK;
 }
 
@@ -576,6 +747,10 @@ extern "C" int rpn_det_head_backward(rpn_det_head *h, const float *d_pooled, int
     const hipStream_t s = as_stream(stream);
     const int K1 = h->k1, H1 = h->h1, H2 = h->h2, NP = h->npad;
     float *w = h->w, *g = h->g;
+    // a dropped kept forward: each hidden layer's mask also carries the factor 1 / (1 - rate); the stored activations are zero
+    // where an element was dropped, so the mask needs no generator
+    const bool dropped = h->kept_dropped;
+    const float dscale = make_dropout_args(h->drop_rate, 0, 0, 0).scale;
     if (head_trains_x3(h)) {
         // the same chain in split float16: each gradient tensor's max|.| (over its M rows and real columns) gives its shift, on the
         // device; the ReLU mask sits in the input-gradient product's epilogue; the bias sums stay float32
@@ -591,11 +766,15 @@ extern "C" int rpn_det_head_backward(rpn_det_head *h, const float *d_pooled, int
         if (e == hipSuccess) e = shift_of(h->dz, NC, NP, 0);
         if (e == hipSuccess) e = launch_fc_wgrad_x3(h->a2, h->dz, M, H2, NC, NP, NP, sdz, g + h->off[4], h->status, s);
         if (e == hipSuccess) e = launch_colsum(h->dz, M, NP, h->part, g + h->off[5], s);
-        if (e == hipSuccess) e = launch_fc_dgrad_x3(h->dz, w + h->off[4], h->a2, M, H2, NC, NP, NP, sdz, head_scales(h, 4), h->d2, h->status, s);
+        if (e == hipSuccess)
+            e = dropped ? launch_fc_dgrad_x3_dropout(h->dz, w + h->off[4], h->a2, M, H2, NC, NP, NP, sdz, head_scales(h, 4), dscale, h->d2, h->status, s)
+                        : launch_fc_dgrad_x3(h->dz, w + h->off[4], h->a2, M, H2, NC, NP, NP, sdz, head_scales(h, 4), h->d2, h->status, s);
         if (e == hipSuccess) e = shift_of(h->d2, H2, H2, 1);
         if (e == hipSuccess) e = launch_fc_wgrad_x3(h->a1, h->d2, M, H1, H2, H2, H2, sd2, g + h->off[2], h->status, s);
         if (e == hipSuccess) e = launch_colsum(h->d2, M, H2, h->part, g + h->off[3], s);
-        if (e == hipSuccess) e = launch_fc_dgrad_x3(h->d2, w + h->off[2], h->a1, M, H1, H2, H2, H2, sd2, head_scales(h, 1), h->d1, h->status, s);
+        if (e == hipSuccess)
+            e = dropped ? launch_fc_dgrad_x3_dropout(h->d2, w + h->off[2], h->a1, M, H1, H2, H2, H2, sd2, head_scales(h, 1), dscale, h->d1, h->status, s)
+                        : launch_fc_dgrad_x3(h->d2, w + h->off[2], h->a1, M, H1, H2, H2, H2, sd2, head_scales(h, 1), h->d1, h->status, s);
         if (e == hipSuccess) e = shift_of(h->d1, H1, H1, 2);
         if (e == hipSuccess) e = launch_fc_wgrad_x3(d_pooled, h->d1, M, K1, H1, H1, H1, sd1, g + h->off[0], h->status, s);
         if (e == hipSuccess) e = launch_colsum(h->d1, M, H1, h->part, g + h->off[1], s);
@@ -609,12 +788,12 @@ extern "C" int rpn_det_head_backward(rpn_det_head *h, const float *d_pooled, int
     if (e == hipSuccess) e = launch_conv1x1_wgrad(h->a2, h->dz, M, H2, NP, h->part, g + h->off[4], s);
     if (e == hipSuccess) e = launch_colsum(h->dz, M, NP, h->part, g + h->off[5], s);
     if (e == hipSuccess) e = launch_conv1x1_dgrad(h->dz, w + h->off[4], nullptr, M, H2, NP, h->d2, s);
-    if (e == hipSuccess) e = launch_relu_mask(h->d2, h->a2, (long long)M * H2, s);
+    if (e == hipSuccess) e = dropped ? launch_relu_scale_mask(h->d2, h->a2, (long long)M * H2, dscale, s) : launch_relu_mask(h->d2, h->a2, (long long)M * H2, s);
     // fc2: dW2 = a1^T d2, db2 = sum d2, d1 = (d2 W2^T) [a1 > 0]
     if (e == hipSuccess) e = launch_conv1x1_wgrad(h->a1, h->d2, M, H1, H2, h->part, g + h->off[2], s);
     if (e == hipSuccess) e = launch_colsum(h->d2, M, H2, h->part, g + h->off[3], s);
     if (e == hipSuccess) e = launch_conv1x1_dgrad(h->d2, w + h->off[2], nullptr, M, H1, H2, h->d1, s);
-    if (e == hipSuccess) e = launch_relu_mask(h->d1, h->a1, (long long)M * H1, s);
+    if (e == hipSuccess) e = dropped ? launch_relu_scale_mask(h->d1, h->a1, (long long)M * H1, dscale, s) : launch_relu_mask(h->d1, h->a1, (long long)M * H1, s);
     // fc1: dW1 = pooled^T d1, db1 = sum d1, grad_pooled = d1 W1^T when asked for
     if (e == hipSuccess) e = launch_conv1x1_wgrad(d_pooled, h->d1, M, K1, H1, h->part, g + h->off[0], s);
     if (e == hipSuccess) e = launch_colsum(h->d1, M, H1, h->part, g + h->off[1], s);

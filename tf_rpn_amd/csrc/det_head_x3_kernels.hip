@@ -25,18 +25,14 @@ namespace rpn {
 // Each accumulator takes, per step in k order, lo*hi, hi*lo, hi*hi: the order over K follows from K alone and a row's result reads
 // that row of A only.  Rows / columns beyond the matrix and k beyond K enter as zeros; stores are scalar and guarded, columns < split
 // to out0, the others to out1.
-__global__ void __launch_bounds__(256) fc_forward_x3_kernel(const float *__restrict__ A, const uint4 *__restrict__ Wp,
-                                                           const float *__restrict__ bias, int M, int K, int N, int ld, int relu,
-                                                           int split, float scale0, float scale1,
-                                                           const float *__restrict__ dscale0, const float *__restrict__ dscale1,
-                                                           float *__restrict__ out0, float *__restrict__ out1,
-                                                           unsigned *__restrict__ status)
+// the main loop shared by fc_forward_x3_kernel and fc_forward_x3_dropout_kernel: acc <- the workgroup's tile of A . W (unscaled).
+// The thread's indices come from the kernel, which needs them again in its epilogue.
+__device__ __forceinline__ void fc_forward_x3_mainloop(const float *__restrict__ A, const uint4 *__restrict__ Wp, int M, int K, int ld,
+                                                       unsigned *__restrict__ status, const int tid, const int wm, const int wn,
+                                                       const int l16, const int q, const int n0, const int m0, x3_f32x4 (&acc)[4][4])
 {
     __shared__ __attribute__((aligned(16))) uint4 As[2][kX3BM * 8];
     __shared__ __attribute__((aligned(16))) uint4 Bs[2][kX3BN * 8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, q = lane >> 4;
-    const int n0 = blockIdx.x * kX3BN, m0 = blockIdx.y * kX3BM;
     const int nsteps = (K + kX3BK - 1) / kX3BK;
     const int ar = tid >> 2, ao = tid & 3;                       // A: rows ar, ar + 64; k octet ao
     float4 ra[2][2];
@@ -73,7 +69,6 @@ __global__ void __launch_bounds__(256) fc_forward_x3_kernel(const float *__restr
 #pragma unroll
         for (int i = 0; i < 4; ++i) Bs[buf][tid + 256 * i] = rb[i];
     };
-    x3_f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -110,6 +105,20 @@ __global__ void __launch_bounds__(256) fc_forward_x3_kernel(const float *__restr
         __syncthreads();
         cur ^= 1;
     }
+}
+
+__global__ void __launch_bounds__(256) fc_forward_x3_kernel(const float *__restrict__ A, const uint4 *__restrict__ Wp,
+                                                           const float *__restrict__ bias, int M, int K, int N, int ld, int relu,
+                                                           int split, float scale0, float scale1,
+                                                           const float *__restrict__ dscale0, const float *__restrict__ dscale1,
+                                                           float *__restrict__ out0, float *__restrict__ out1,
+                                                           unsigned *__restrict__ status)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, q = lane >> 4;
+    const int n0 = blockIdx.x * kX3BN, m0 = blockIdx.y * kX3BM;
+    x3_f32x4 acc[4][4];
+    fc_forward_x3_mainloop(A, Wp, M, K, ld, status, tid, wm, wn, l16, q, n0, m0, acc);
     // accumulator element e of block (i, j): row 16 i + 4 (lane / 16) + e, column 16 j + lane % 16
     // (a training head's scales live in device memory: they follow the weights without a host round trip)
     if (dscale0) scale0 = *dscale0, scale1 = *dscale1;
@@ -134,6 +143,42 @@ __global__ void __launch_bounds__(256) fc_forward_x3_kernel(const float *__restr
                     dst[(size_t)row * ldo] = v;
                 }
             }
+    }
+}
+
+// The same product for a hidden layer of a training head that is dropped (dropout.h; contract in include/rpn_hip.h): out (M x N) =
+// keep ? fl32(max(acc * *dscale + bias, 0) * scale) : +0, the 2^-s read from device memory.  Block (i, j)'s four elements are four
+// consecutive rows of one column starting at a multiple of 4: one generator evaluation (counter (column, row / 4, layer, t)) per
+// block, made inside the store loop.
+__global__ void __launch_bounds__(256) fc_forward_x3_dropout_kernel(const float *__restrict__ A, const uint4 *__restrict__ Wp,
+                                                                   const float *__restrict__ bias, int M, int K, int N, int ld,
+                                                                   const float *__restrict__ dscale, DropoutArgs drop,
+                                                                   float *__restrict__ out, unsigned *__restrict__ status)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, q = lane >> 4;
+    const int n0 = blockIdx.x * kX3BN, m0 = blockIdx.y * kX3BM;
+    x3_f32x4 acc[4][4];
+    fc_forward_x3_mainloop(A, Wp, M, K, ld, status, tid, wm, wn, l16, q, n0, m0, acc);
+    const float sc = *dscale;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = n0 + wn * 64 + 16 * j + l16;
+        if (col >= N) continue;
+        const float bv = bias ? bias[col] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row0 = m0 + wm * 64 + 16 * i + 4 * q;
+            if (row0 >= M) continue;
+            const unsigned keep = dropout_keep4(drop, (unsigned)col, (unsigned)row0 >> 2);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (row0 + e < M) {
+                    float v = acc[i][j][e] * sc;
+                    if (bias) v += bv;
+                    out[(size_t)(row0 + e) * N + col] = keep >> e & 1u ? fmaxf(v, 0.0f) * drop.scale : 0.0f;
+                }
+        }
     }
 }
 
@@ -283,15 +328,14 @@ __global__ void __launch_bounds__(256) fc_wgrad_x3_kernel(const float *__restric
 // 8 consecutive floats of a row, splits them and writes the two pieces -- W from the master weights, no transposed image.  The range
 // probe sits on DZ.  Columns >= N of both are read (inside ld) and dropped.  gscale {2^t, 2^-t}, wscale {2^s, 2^-s}: device memory.
 // A row's result reads that row of DZ, W and the two scales only.
-__global__ void __launch_bounds__(256) fc_dgrad_x3_kernel(const float *__restrict__ DZ, const float *__restrict__ W,
-                                                         const float *__restrict__ H, int M, int K, int N, int ldz, int ldw,
-                                                         const float *__restrict__ gscale, const float *__restrict__ wscale,
-                                                         float *__restrict__ out, unsigned *__restrict__ status)
+// the main loop shared by fc_dgrad_x3_kernel and fc_dgrad_x3_dropout_kernel: acc <- the workgroup's tile of (2^t DZ) (2^s W)^T
+__device__ __forceinline__ void fc_dgrad_x3_mainloop(const float *__restrict__ DZ, const float *__restrict__ W, int M, int K, int N,
+                                                     int ldz, int ldw, const float *__restrict__ gscale,
+                                                     const float *__restrict__ wscale, unsigned *__restrict__ status, const int tid,
+                                                     const int wm, const int wn, const int l16, const int q, const int k0,
+                                                     const int m0, x3_f32x4 (&acc)[4][4])
 {
     __shared__ __attribute__((aligned(16))) uint4 S[2][2][kX3BM * 8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, q = lane >> 4;
-    const int k0 = blockIdx.x * kX3BN, m0 = blockIdx.y * kX3BM;
     const int nsteps = (N + kX3BK - 1) / kX3BK;
     const int ar = tid >> 2, ao = tid & 3;                       // rows ar, ar + 64 of either operand; octet ao of the step
     const float gmul = gscale[0], wmul = wscale[0];
@@ -336,7 +380,6 @@ __global__ void __launch_bounds__(256) fc_dgrad_x3_kernel(const float *__restric
             S[buf][1][r * 8 + ((4 + ao) ^ sw)] = lo;
         }
     };
-    x3_f32x4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -356,6 +399,18 @@ __global__ void __launch_bounds__(256) fc_dgrad_x3_kernel(const float *__restric
         __syncthreads();
         cur ^= 1;
     }
+}
+
+__global__ void __launch_bounds__(256) fc_dgrad_x3_kernel(const float *__restrict__ DZ, const float *__restrict__ W,
+                                                         const float *__restrict__ H, int M, int K, int N, int ldz, int ldw,
+                                                         const float *__restrict__ gscale, const float *__restrict__ wscale,
+                                                         float *__restrict__ out, unsigned *__restrict__ status)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, q = lane >> 4;
+    const int k0 = blockIdx.x * kX3BN, m0 = blockIdx.y * kX3BM;
+    x3_f32x4 acc[4][4];
+    fc_dgrad_x3_mainloop(DZ, W, M, K, N, ldz, ldw, gscale, wscale, status, tid, wm, wn, l16, q, k0, m0, acc);
     // acc * 2^-(t + s) as two exact multiplications (x3_unscale_factors, x3_tile.h)
     float f1, f2;
     x3_unscale_factors(gscale[1], wscale[1], f1, f2);
@@ -373,6 +428,35 @@ __global__ void __launch_bounds__(256) fc_dgrad_x3_kernel(const float *__restric
                     if (H) v = H[(size_t)row * K + col] > 0.0f ? v : 0.0f;
                     out[(size_t)row * K + col] = v;
                 }
+            }
+    }
+}
+
+// the input gradient of a DROPPED layer: out = H > 0 ? fl32(acc f1 f2 * scale) : 0, H the stored (dropped, scaled) activation -- the
+// factor 1 / (1 - rate) after the two exact powers of two; no generator runs here
+__global__ void __launch_bounds__(256) fc_dgrad_x3_dropout_kernel(const float *__restrict__ DZ, const float *__restrict__ W,
+                                                                 const float *__restrict__ H, int M, int K, int N, int ldz, int ldw,
+                                                                 const float *__restrict__ gscale, const float *__restrict__ wscale,
+                                                                 float scale, float *__restrict__ out, unsigned *__restrict__ status)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l16 = lane & 15, q = lane >> 4;
+    const int k0 = blockIdx.x * kX3BN, m0 = blockIdx.y * kX3BM;
+    x3_f32x4 acc[4][4];
+    fc_dgrad_x3_mainloop(DZ, W, M, K, N, ldz, ldw, gscale, wscale, status, tid, wm, wn, l16, q, k0, m0, acc);
+    // acc * 2^-(t + s) as two exact multiplications (x3_unscale_factors, x3_tile.h)
+    float f1, f2;
+    x3_unscale_factors(gscale[1], wscale[1], f1, f2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = k0 + wn * 64 + 16 * j + l16;
+        if (col >= K) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = m0 + wm * 64 + 16 * i + 4 * q + e;
+                if (row < M) out[(size_t)row * K + col] = H[(size_t)row * K + col] > 0.0f ? acc[i][j][e] * f1 * f2 * scale : 0.0f;
             }
     }
 }
@@ -428,6 +512,22 @@ hipError_t launch_fc_dgrad_x3(const float *dz, const float *w, const float *h, i
 {
     hipLaunchKernelGGL(fc_dgrad_x3_kernel, dim3((K + kX3BN - 1) / kX3BN, (M + kX3BM - 1) / kX3BM), dim3(256), 0, s, dz, w, h, M, K, N, ldz,
                        ldw, gscale, wscale, out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_fc_forward_x3_dropout(const float *a, const void *packed, const float *bias, int M, int K, int N, int ld,
+                                        const float *dscale, const DropoutArgs &drop, float *out, unsigned *status, hipStream_t s)
+{
+    hipLaunchKernelGGL(fc_forward_x3_dropout_kernel, dim3((N + kX3BN - 1) / kX3BN, (M + kX3BM - 1) / kX3BM), dim3(256), 0, s, a,
+                       reinterpret_cast<const uint4 *>(packed), bias, M, K, N, ld, dscale, drop, out, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_fc_dgrad_x3_dropout(const float *dz, const float *w, const float *h, int M, int K, int N, int ldz, int ldw,
+                                      const float *gscale, const float *wscale, float scale, float *out, unsigned *status, hipStream_t s)
+{
+    hipLaunchKernelGGL(fc_dgrad_x3_dropout_kernel, dim3((K + kX3BN - 1) / kX3BN, (M + kX3BM - 1) / kX3BM), dim3(256), 0, s, dz, w, h, M, K,
+                       N, ldz, ldw, gscale, wscale, scale, out, status);
     return hipGetLastError();
 }
 

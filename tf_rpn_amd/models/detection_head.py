@@ -8,8 +8,16 @@ Fast R-CNN head), as the thresholds of ``calculate_roi_targets`` are:
     fc1: h1 = relu(x  W1 + b1)     fc2: h2 = relu(h1 W2 + b2)
     cls: logits = h2 Wc + bc  -> (B,R,C)  LOGITS         reg: deltas = h2 Wr + br  -> (B,R,4C)  class-specific
 
-Kernels are Keras ``Dense`` kernels, (in, out).  There is no dropout: every training entry point of this library gives the same
-bits on every run, and so does this one.  Exact float32; a RoI's outputs do not depend on the batch it is part of.
+Kernels are Keras ``Dense`` kernels, (in, out).  Every training entry point of this library gives the same bits on every run,
+and so does this one -- with dropout too (below).  Exact float32; a RoI's outputs do not depend on the batch it is part of.
+
+``dropout=rate`` (trainable heads; default 0: nothing changes) drops the two hidden activations of every GRAD-MODE call the way
+Keras' ``Dropout`` does, ``h * 1/(1 - rate) * mask``, with a seeded counter-based generator (Philox4x32-10; the contract is in
+``include/rpn_hip.h``): an element is kept iff its 32-bit word, a function of ``(dropout_seed, call number, layer, row, column)``
+alone, is ``>= min(llround(rate * 2^32), 2^32 - 1)``.  There is no generator state and no mask tensor: the same
+``(weights, input, seed, call number)`` gives the same bits on every run, in float32 and in ``f16x3`` (which use the identical
+mask), whatever the batch is shaped like.  Dropout is the identity under ``torch.no_grad()``, in ``detect`` and in every
+inference head, and such calls do not advance the call number: VALIDATION THEREFORE RUNS UNDER ``torch.no_grad()``.
 
 ``precision="f16x3"`` (inference heads only) runs the three products on the float16 matrix cores with every float32 operand
 carried as hi + lo float16 halves (``hi*hi + hi*lo + lo*hi``, float32 accumulation; the contract is in ``include/rpn_hip.h``):
@@ -19,8 +27,9 @@ float32 weights are kept beside their packed image).  Features or activations be
 
 A trainable head is created in float32 and may TRAIN in split float16: ``compile(..., precision="f16x3")`` runs every product
 of the forward and of the backward in ``f16x3`` (the output gradients carried as the split of ``dZ * 2^t``, one power of two per
-gradient tensor found on the device) while the master weights, the gradients, the bias sums and Adam stay float32.  Its forward
-is bit for bit the ``f16x3`` inference head's on the same weights; the packed image (a fifth copy of the weights: 2.4 GB in all
+gradient tensor found on the device) while the master weights, the gradients, the bias sums and Adam stay float32.  Every forward
+that is not kept (``torch.no_grad()``, ``detect``), and every grad-mode forward at dropout rate 0, is bit for bit the ``f16x3``
+inference head's on the same weights; the packed image (a fifth copy of the weights: 2.4 GB in all
 at 25 088 x 4096 x 4096) is refreshed on the device after every ``apply_gradients()``.
 """
 import ctypes
@@ -33,6 +42,21 @@ from ..utils import roi_utils
 
 LAYERS = ("fc1", "fc2", "cls", "reg")
 PRECISIONS = ("f32", "f16x3")
+
+
+def dropout(x, rate, seed, calls=0, layer=0):
+    """The head's dropout on any 2-D float32 tensor (``rpn_dropout_forward``): ``keep ? x * 1/(1 - rate) : +0`` with the mask of
+    hidden layer ``layer`` at call number ``calls`` -- element (m, n) is kept iff output word ``m & 3`` of Philox4x32-10 at counter
+    ``(n, m >> 2, layer, calls mod 2^32)``, key ``(seed & 0xffffffff, seed >> 32)`` is ``>= min(llround(rate * 2^32), 2^32 - 1)``.
+    No ReLU, out of place; returns a new CUDA tensor."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("dropout takes a 2-D torch tensor (M, N)")
+    x = L.to_device(x)[0]
+    out = torch.empty_like(x)
+    st = L.lib().rpn_dropout_forward(L.ptr(x), int(x.shape[0]), int(x.shape[1]), float(rate), int(seed) & (2 ** 64 - 1),
+                                     int(calls) & 0xffffffff, int(layer), L.ptr(out), L.stream_ptr())
+    L.check(st, "rpn_dropout_forward")
+    return out
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -77,6 +101,10 @@ class DetectionHead(object):
     another call's activations.  Each backward REPLACES the stored parameter gradients; they do not accumulate over calls, so
     it is one forward, one backward, one ``apply_gradients``.  Under ``torch.no_grad()`` nothing is kept.  ``trainable=False`` is the inference head: weights and the two hidden activations only.
 
+    ``dropout``, ``dropout_seed``: the rate in [0, 1) and the 64-bit seed of the dropout after the two hidden layers (module
+    docstring; ``set_dropout``, ``dropout_state``).  ``dropout_seed=None`` means ``seed``, or 0 when ``seed`` is None.
+    ``dropout > 0`` needs ``trainable=True``.  It applies to grad-mode calls only: run validation under ``torch.no_grad()``.
+
     ``precision``: ``"f32"`` (exact float32, the default) or ``"f16x3"`` (split float16 on the 16-bit matrix cores; needs
     ``trainable=False``).  ``head.precision`` reports it.  A trainable head is always constructed in float32; the precision it
     TRAINS in is ``compile``'s ``precision`` (``head.train_precision``).
@@ -85,11 +113,15 @@ class DetectionHead(object):
     none (every layer must then be given with ``set_weights`` before the first call)."""
 
     def __init__(self, total_labels, pooling_size=(7, 7), channels=512, hidden=(4096, 4096), max_rois=8 * 300, trainable=True,
-                 seed=0, precision="f32"):
+                 seed=0, precision="f32", dropout=0.0, dropout_seed=None):
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %r, got %r" % (PRECISIONS, precision))
         if precision == "f16x3" and trainable:
             raise ValueError("precision 'f16x3' is the inference head's: pass trainable=False (training stays exact float32)")
+        if not 0.0 <= float(dropout) < 1.0:                  # (a NaN fails both compares)
+            raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
+        if float(dropout) > 0.0 and not trainable:
+            raise ValueError("dropout applies to the kept (grad-mode) forwards of a trainable head: pass trainable=True")
         self.precision = precision
         self.total_labels = int(total_labels)
         self.pooling_size = tuple(int(v) for v in pooling_size)
@@ -108,8 +140,11 @@ class DetectionHead(object):
                        "reg": (self.hidden[1], 4 * C)}
         self._opt = None
         self._token = None
-        self._serial = 0                         # counts what invalidates a kept forward: calls, set_weights, apply_gradients
+        self._serial = 0                         # counts what invalidates a kept forward: calls, set_weights, apply_gradients, set_dropout
+        self._kept_rows = 0                      # rows of the most recent call when it was kept
         self.compile()
+        if self.trainable:
+            self.set_dropout(dropout, seed=dropout_seed if dropout_seed is not None else (seed if seed is not None else 0))
         if torch.cuda.is_available() and seed is not None:   # (without a device the object still answers shape and memory questions;
             # seed=None: the caller sets every layer itself)
             self.set_weights(self.initial_weights(seed))
@@ -188,6 +223,37 @@ class DetectionHead(object):
         head.set_weights(weights)
         return head
 
+    # ---- dropout ------------------------------------------------------------------------
+    def set_dropout(self, rate, seed=None, calls=None):
+        """The dropout rate in [0, 1) of the grad-mode calls from here on; ``seed`` (None: unchanged) and ``calls``, the call number
+        the next dropped call will use (None: unchanged; it starts at 0 and counts the calls that applied dropout), are what a resumed
+        run restores from ``dropout_state()``.  A kept forward is dropped: its backward raises ``ValueError``."""
+        if not self.trainable:
+            raise ValueError("set_dropout needs a trainable head (dropout applies to kept forwards only)")
+        state = self.dropout_state()
+        self._serial += 1
+        L.check(L.lib().rpn_det_head_set_dropout(self._h, float(rate), int(state["seed"] if seed is None else seed) & (2 ** 64 - 1)),
+                "rpn_det_head_set_dropout")
+        if calls is not None:
+            L.check(L.lib().rpn_det_head_set_dropout_calls(self._h, int(calls)), "rpn_det_head_set_dropout_calls")
+
+    def dropout_state(self):
+        """{"rate", "seed", "calls"}: with the weights and the optimiser's state, what reproduces the next dropped call"""
+        rate, seed, calls = ctypes.c_double(0.0), ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        L.check(L.lib().rpn_det_head_dropout_state(self._h, ctypes.byref(rate), ctypes.byref(seed), ctypes.byref(calls)),
+                "rpn_det_head_dropout_state")
+        return {"rate": float(rate.value), "seed": int(seed.value), "calls": int(calls.value)}
+
+    def kept_activation(self, name):
+        """the hidden activation ``"fc1"`` (M, H1) or ``"fc2"`` (M, H2) the most recent grad-mode call stored for its backward (dropped
+        and scaled when dropout applied), as a new torch tensor; ``ValueError`` when no forward is kept"""
+        if name not in ("fc1", "fc2"):
+            raise ValueError("kept_activation: %r is not a hidden layer (fc1, fc2)" % (name,))
+        rows = self._kept_rows
+        out = torch.empty((max(rows, 1), self.shapes[name][1]), dtype=torch.float32, device="cuda")
+        L.check(L.lib().rpn_det_head_get_activation(self._h, name.encode(), L.ptr(out), rows, L.stream_ptr()), "rpn_det_head_get_activation")
+        return out
+
     def status(self, reset=False):
         """Sticky flags raised on the device by the forwards so far -> {"f16_range": bool}.  ``f16_range`` (``precision="f16x3"``
         or a head compiled with it; a float32 head always reports False): a pooled feature or a hidden activation did not fit
@@ -220,6 +286,7 @@ class DetectionHead(object):
         self._serial += 1
         st = L.lib().rpn_det_head_forward(self._h, L.ptr(pooled), B * R, int(keep), L.ptr(logits), L.ptr(deltas), L.stream_ptr())
         L.check(st, "DetectionHead forward")
+        self._kept_rows = B * R if keep else 0
         return logits, deltas
 
     def __call__(self, pooled):
