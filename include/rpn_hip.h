@@ -896,6 +896,69 @@ int rpn_evaluator_result(rpn_evaluator *e, double *d_ap, double *d_ap11, int32_t
 int rpn_evaluator_pr_curve(rpn_evaluator *e, int c, float *d_scores, int32_t *d_tp, int32_t *d_slots, int cap, int32_t *d_n,
                            void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Evaluation, COCO style: AP over several IoU thresholds and object sizes, AR at several numbers of detections, accumulated on the
+ * device.  A second handle beside rpn_evaluator, which keeps its rules.  The rules are pycocotools' COCOeval in bbox mode AS
+ * RECALLED (pycocotools is not a dependency and parity with it is not pinned); where a rule is THIS PROJECT'S choice it is marked
+ * (*).  update enqueues on `stream` and returns: no copy to the host, no synchronisation.  No floating-point atomics; every float64
+ * sum has an order fixed by the counts alone, so result gives the same bits on every run.
+ *
+ * create: C, max_images, M with rpn_evaluator_create's limits (2 <= C <= 65535, 1 <= M <= 4096, max_images * M <= 2^30).  HOST arrays:
+ *   iou_thresholds (T), 1 <= T <= 10, each in (0, 1]; NULL: the ten float32 values nearest to the doubles 0.5 + 0.05 i.
+ *   area_ranges (A,2) of [lo, hi] in pixels^2, 1 <= A <= 4, 0 <= lo <= hi, finite; NULL: [0, 1e10], [0, 32^2], [32^2, 96^2],
+ *     [96^2, 1e10].  Index 0 is "all" by convention only.
+ *   max_dets (K), 1 <= K <= 4, strictly ascending, 1 <= max_dets[0], max_dets[K-1] <= M; NULL: (1, 10, 100).
+ *   height, width: the default image size in float32, finite and > 0.  Boxes are normalised [y1, x1, y2, x2].
+ *   All device memory -- 20 bytes of record (score, class and rank, 2 bits per (a, t)) and the two 8-byte halves of the sort
+ *   workspace: 36 bytes per detection row of max_images * M in all, plus the counters -- is ONE allocation owned by the handle, made
+ *   at creation (without a device, where create, memory_bytes and every argument check still work: by the first call that finds one).
+ * update: one batch.  The detection inputs are exactly rpn_evaluator_update's; d_gt_boxes (B,G,4), d_gt_labels (B,G) int32,
+ *   d_gt_difficult (B,G) bytes or NULL; 1 <= G <= 2048.  d_image_sizes (B,2) float32 [height, width] or NULL (the handle's size).
+ *   Live detections: row m of image b counts iff m < valid[b], its class is an integer in [1, C) and its score is finite and > 0.
+ *     Every other row is dropped and never indexes memory.
+ *   Ground truth: a row counts iff its label is >= 1 (labels >= C are not counted).
+ *   IoU: float32 generate_iou_map arithmetic, every operation rounded on its own.  A NaN IoU never matches (*).
+ *   Pixel area of a box = fl32(fl32((y2 - y1) * height) * fl32((x2 - x1) * width)), every operation rounded on its own (*):
+ *     pycocotools reads an `area` field, a box-only dataset has only the box.
+ *   Per (image b, class c): D = the live detections of class c in (score descending, m ascending) order, cut to the first
+ *     max_dets[K-1]; a detection's position in D is its RANK; rows beyond the cut are counted nowhere.  ndet[c] counts the ranked rows.
+ *   Per area range a, a gt of label c is IGNORED iff it is difficult or its area is < lo_a or > hi_a (both ends inclusive: a 32 x 32
+ *     box is small and medium).  npig[c, a] counts the others.
+ *   Matching per (b, c, a, t) with its own `taken` set, the detections of D in order.  Among the untaken, non-ignored gts with
+ *     iou >= thr_t the match is the one of highest IoU, the LAST in input order on ties (*) (pycocotools' `if ious[d,g] < iou:
+ *     continue`; rpn_evaluator takes the first); if there is none, the same rule among the untaken ignored gts.  A matched gt is
+ *     taken, an ignored one too; there are no crowd boxes, every gt matches at most once.
+ *       matched to a non-ignored gt                                      -> TP (1)
+ *       matched to an ignored gt                                         -> ignored (-1)
+ *       unmatched, the detection's own area outside [lo_a, hi_a]         -> ignored (-1)
+ *       unmatched otherwise                                              -> FP (0)
+ *   d_flags (B,M,A,T) int8 or NULL: 1 / 0 / -1, and -2 for a row that is not counted (not live, or beyond the cut).
+ *   Slot of a row = (images before this batch + b) * M + m.  images + B > max_images or a bad size: RPN_ERR_INVALID, nothing is
+ *   enqueued, nothing changes.
+ * result: per class, the ranked rows ordered by score descending, ties to the lower slot (a stable sort: rpn_evaluator's ranking).
+ *   For (c, a, t) and cut-off k: walk the rows with rank < max_dets[k], skip those whose flag at (a, t) is -1, accumulate tp_i, fp_i.
+ *   d_ar (C,A,T,K) = tp_total / npig[c, a], one float64 division.
+ *   d_ap (C,A,T), at the last cut-off: prec_i = tp_i / (fl64(tp_i + fp_i) + 2^-52) (np.spacing(1)), made non-increasing from the
+ *     right; for q = 0..100, p_q = the precision at the first rank with 100 tp_i >= q npig, compared IN INTEGERS (*), 0 if there is
+ *     none; ap = (sum of p_q) / 101 in float64.
+ *   npig == 0: ap and ar NaN (class 0 always); npig > 0 and no rows: 0.  d_npig (C,A), d_ndet (C,) int32.  Device pointers, any may
+ *   be NULL; result synchronises nothing and may be called any number of times, between updates too.
+ * reset: counters and the image count to zero, on `stream`.  images: images counted so far (a host counter).
+ * d_boxes, d_gt_boxes 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+typedef struct rpn_coco_evaluator rpn_coco_evaluator;
+int rpn_coco_evaluator_create(int C, int max_images, int M, const float *iou_thresholds, int T, const float *area_ranges, int A,
+                              const int *max_dets, int K, float height, float width, rpn_coco_evaluator **out);
+void rpn_coco_evaluator_destroy(rpn_coco_evaluator *e);
+int rpn_coco_evaluator_memory_bytes(const rpn_coco_evaluator *e, size_t *bytes);
+int rpn_coco_evaluator_reset(rpn_coco_evaluator *e, void *stream);
+int rpn_coco_evaluator_images(const rpn_coco_evaluator *e);
+int rpn_coco_evaluator_update(rpn_coco_evaluator *e, const float *d_boxes, const float *d_scores, const float *d_classes,
+                              const int32_t *d_valid, const float *d_gt_boxes, const int32_t *d_gt_labels,
+                              const unsigned char *d_gt_difficult, const float *d_image_sizes, int B, int G, signed char *d_flags,
+                              void *stream);
+int rpn_coco_evaluator_result(rpn_coco_evaluator *e, double *d_ap, double *d_ar, int32_t *d_npig, int32_t *d_ndet, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

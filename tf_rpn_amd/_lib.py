@@ -172,6 +172,14 @@ _SIGNATURES = {
     "rpn_evaluator_update_proposals": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
     "rpn_evaluator_result": (ctypes.c_int, [vp] * 8),
     "rpn_evaluator_pr_curve": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, vp]),
+    "rpn_coco_evaluator_create": (ctypes.c_int, [ctypes.c_int] * 3 + [c_float_p, ctypes.c_int, c_float_p, ctypes.c_int, c_int_p,
+                                                 ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.POINTER(vp)]),
+    "rpn_coco_evaluator_destroy": (None, [vp]),
+    "rpn_coco_evaluator_memory_bytes": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_size_t)]),
+    "rpn_coco_evaluator_reset": (ctypes.c_int, [vp, vp]),
+    "rpn_coco_evaluator_images": (ctypes.c_int, [vp]),
+    "rpn_coco_evaluator_update": (ctypes.c_int, [vp] * 9 + [ctypes.c_int] * 2 + [vp, vp]),
+    "rpn_coco_evaluator_result": (ctypes.c_int, [vp] * 6),
 }
 
 _lib = None

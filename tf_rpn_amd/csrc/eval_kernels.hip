@@ -15,7 +15,8 @@
 //   eval_recall_kernel  : one 256-thread workgroup per image, a thread per gt: the running maximum IoU over the RoIs in order (the
 //                         RoI address is the same in every lane: one scalar load), read at the cut-offs in ascending order.
 //                         HBM per image: 16 min(max k, valid) + 21 G read; <= 64 integer atomics per workgroup.
-//   eval_class_kernel   : one 1024-thread workgroup per class.  (1) the class's live records, compacted in slot order into the
+//   eval_class_kernel   : one 1024-thread workgroup per class ((1) and (2) are eval_sort.h's, shared with eval_coco_kernels.hip).
+//                         (1) the class's live records, compacted in slot order into the
 //                         workspace as (~orderable(score), slot << 1 | tp) pairs (eight records per thread, a workgroup scan of the
 //                         counts, no atomics); (2) a stable LSD radix sort, four 8-bit passes over a ping-pong pair -- all four
 //                         histograms from one read, a pass whose digit is the same in every key is skipped, tiles of 4096 keys, ranks
@@ -32,6 +33,7 @@
 #include <new>
 
 #include "bbox_core.h"
+#include "eval_sort.h"
 #include "rpn_common.h"
 
 namespace rpn {
@@ -40,13 +42,8 @@ constexpr int kEvMaxG = 2048;              // as rpn_roi_targets
 constexpr int kEvMaxM = 4096;
 constexpr int kEvMaxCut = 8;               // cut-offs and thresholds of the proposal recall
 constexpr int kEvMaxC = 65535;
-constexpr int kEvThreads = 1024;
-constexpr int kEvWaves = kEvThreads / 64;
 constexpr int kEvRows = kEvMaxM / kEvThreads;              // detection rows per thread of the match kernel
 constexpr int kEvRecallThreads = 256;
-constexpr int kEvSortItems = 4;                         // keys per thread and tile of its sort passes
-constexpr int kEvSortTile = kEvThreads * kEvSortItems;
-constexpr int kEvScanItems = 8;                         // records per thread and tile of the class kernel's compaction
 
 // ---- matching ---------------------------------------------------------------------------------------------------------------
 struct EvalMatchArgs {
@@ -205,182 +202,29 @@ struct EvalClassArgs {
     double *ap, *ap11;             // (C,) or null
 };
 
-// lanes of this wave whose 8-bit digit equals mine (invalid lanes match nobody)
-__device__ __forceinline__ unsigned long long wave_match8(unsigned d, bool valid)
-{
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-        const bool on = (d >> bit) & 1u;
-        const unsigned long long m = __ballot(on);
-        peers &= on ? m : ~m;
-    }
-    return peers;
-}
-
-__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
-// exclusive prefix of a per-thread count over the workgroup, in thread order; *total = the workgroup's sum.  wsum: kEvWaves ints of LDS.
-__device__ __forceinline__ int block_scan(int v, int *wsum, int *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kEvWaves; ++i) {
-        const int s = wsum[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-
 __global__ void __launch_bounds__(kEvThreads)
 eval_class_kernel(EvalClassArgs p)
 {
-    __shared__ int hist[4][256];
-    __shared__ int base[256];
-    __shared__ int wcnt[kEvWaves][256];
-    __shared__ int wsum[kEvWaves];
-    __shared__ int skip;
+    __shared__ EvSortLds sort_lds;
     __shared__ double wmax[kEvWaves];
     __shared__ double p11[11];
     __shared__ double red[kEvThreads];
+    int *const wsum = sort_lds.wsum;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int c = p.c0 + blockIdx.x;
     const int n = p.ndet[c], npos = p.npos[c];
     long long off = 0;
     for (int i = 0; i < c; ++i) off += p.ndet[i];
 
-    // (1) this class's live records, in slot order: kEvScanItems consecutive records per thread (64 bytes, four 16-byte loads in
-    // flight per lane), so thread order then item order is slot order
+    // (1) this class's live records, in slot order, as (~orderable(score), slot << 1 | tp)
     uint2 *cur = p.buf[0] + off, *alt = p.buf[1] + off;
-    {
-        int run = 0;
-        for (long long s0 = 0; s0 < p.n_rec; s0 += (long long)kEvThreads * kEvScanItems) {
-            const long long first = s0 + (long long)tid * kEvScanItems;
-            int2 r[kEvScanItems];
-            if (first + kEvScanItems <= p.n_rec) {
-                const int4 *q = reinterpret_cast<const int4 *>(p.rec + first);       // 64-byte aligned: the buffer is, first % 8 == 0
-#pragma unroll
-                for (int u = 0; u < kEvScanItems / 2; ++u) {
-                    const int4 v = q[u];
-                    r[2 * u] = make_int2(v.x, v.y);
-                    r[2 * u + 1] = make_int2(v.z, v.w);
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < kEvScanItems; ++u) r[u] = first + u < p.n_rec ? p.rec[first + u] : make_int2(0, 0);
-            }
-            unsigned mine = 0u;
-#pragma unroll
-            for (int u = 0; u < kEvScanItems; ++u)
-                if (r[u].y != 0 && (r[u].y >> 1) == c) mine |= 1u << u;
-            int total;
-            int pos = run + block_scan(__popc(mine), wsum, &total);
-            // (pos < n always: ndet counts exactly these records; the test keeps a torn counter from writing past the segment)
-#pragma unroll
-            for (int u = 0; u < kEvScanItems; ++u) {
-                if (((mine >> u) & 1u) && pos < n) {
-                    cur[pos] = make_uint2(~orderable(__int_as_float(r[u].x)), ((unsigned)(first + u) << 1) | (unsigned)(r[u].y & 1));
-                    ++pos;
-                }
-            }
-            run += total;
-        }
-    }
+    ev_compact(
+        p.rec, p.n_rec, cur, n, wsum, [c](const int2 &r) { return r.y != 0 && (r.y >> 1) == c; },
+        [](const int2 &r, long long slot) {
+            return make_uint2(~orderable(__int_as_float(r.x)), ((unsigned)slot << 1) | (unsigned)(r.y & 1));
+        });
     // (2) stable LSD radix sort by the key, ascending: score descending, ties in slot order
-    for (int i = tid; i < 4 * 256; i += kEvThreads) (&hist[0][0])[i] = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < n; i0 += kEvThreads) {
-        const int i = i0 + tid;
-        const bool valid = i < n;
-        const unsigned key = valid ? cur[i].x : 0u;
-#pragma unroll
-        for (int ps = 0; ps < 4; ++ps) {
-            const unsigned d = (key >> (8 * ps)) & 255u;
-            const unsigned long long peers = wave_match8(d, valid);
-            if (valid && (peers & lanes_below(lane)) == 0ull) atomicAdd(&hist[ps][d], __popcll(peers));
-        }
-    }
-    __syncthreads();
-    int par = 0;
-    for (int ps = 0; ps < 4; ++ps) {
-        if (tid == 0) skip = 0;
-        __syncthreads();
-        if (tid < 256 && hist[ps][tid] == n) skip = 1;      // every key has this digit: the pass would be the identity
-        // exclusive scan of the 256 bins -> where each digit's run starts
-        int incl = tid < 256 ? hist[ps][tid] : 0;
-        const int mine = incl;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        if (tid < 256) {
-            int b0 = 0;
-            for (int i = 0; i < w; ++i) b0 += wsum[i];
-            base[tid] = b0 + incl - mine;
-        }
-        const bool skipped = skip != 0;
-        __syncthreads();
-        if (skipped || n == 0) continue;
-        // tiles of kEvSortTile keys; wave w owns kEvSortItems runs of 64 consecutive keys, so (wave, round, lane) order is key order
-        for (int i0 = 0; i0 < n; i0 += kEvSortTile) {
-            uint2 kv[kEvSortItems];
-            int rank[kEvSortItems];
-            const int first = i0 + w * (64 * kEvSortItems) + lane;
-#pragma unroll
-            for (int u = 0; u < kEvSortItems; ++u) {
-                kv[u] = make_uint2(0u, 0u);
-                if (first + 64 * u < n) kv[u] = cur[first + 64 * u];
-            }
-            for (int k = tid; k < kEvWaves * 256; k += kEvThreads) (&wcnt[0][0])[k] = 0;
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < kEvSortItems; ++u) {
-                const bool valid = first + 64 * u < n;
-                const unsigned d = (kv[u].x >> (8 * ps)) & 255u;
-                const unsigned long long peers = wave_match8(d, valid);
-                const int r = __popcll(peers & lanes_below(lane));
-                const int before = wcnt[w][d];                  // this wave's keys of digit d in its earlier rounds
-                rank[u] = before + r;
-                __builtin_amdgcn_wave_barrier();                // every peer has read the count before the first of them raises it
-                if (valid && r == 0) wcnt[w][d] = before + __popcll(peers);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            __syncthreads();
-            if (tid < 256) {                                // this tile's keys of digit `tid`, wave by wave
-                int run = base[tid];
-                for (int k = 0; k < kEvWaves; ++k) {
-                    const int t = wcnt[k][tid];
-                    wcnt[k][tid] = run;
-                    run += t;
-                }
-                base[tid] = run;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < kEvSortItems; ++u)
-                if (first + 64 * u < n) alt[wcnt[w][(kv[u].x >> (8 * ps)) & 255u] + rank[u]] = kv[u];
-            __syncthreads();
-        }
-        uint2 *t = cur;
-        cur = alt;
-        alt = t;
-        par ^= 1;
-    }
+    const int par = ev_radix_sort(cur, alt, n, sort_lds);
     if (tid == 0) p.parity[c] = par;
     if (!p.ap) return;
 
