@@ -836,6 +836,79 @@ int rpn_fc_forward(const float *d_a, const float *d_w, const float *d_bias, int 
                    void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Optimizers: SGD momentum, L2 weight decay, clipping by the global norm, and the optimizer's state
+ *   (tf_rpn_amd/csrc/optim_kernels.hip; no reference counterpart: its trainer.py compiles with Adam(1e-5) and nothing else).
+ *   Both handles -- rpn_head_trainer and a trainable rpn_det_head -- start as they always were: Adam, no decay, no clip norm, and
+ *   in that configuration a step launches exactly what it launched before these entries existed (adam_kernel, no norm pass).
+ *
+ * set_optimizer(kind, momentum, nesterov, weight_decay, global_clipnorm)
+ *   kind: RPN_OPT_ADAM or RPN_OPT_SGD.  momentum in [0, 1) (SGD's; Adam ignores it), nesterov 0 | 1, weight_decay >= 0 and
+ *   global_clipnorm >= 0, both finite, 0 = off.  A bad value is RPN_ERR_INVALID with a message, before any device work.  The step
+ *   entries (rpn_head_trainer_step / _backward, rpn_det_head_adam_step) keep their arguments: under SGD beta_1, beta_2 and epsilon
+ *   are ignored and lr is SGD's.  SWITCHING kind ZEROES m, v AND THE STEP COUNT; setting the same kind again keeps them.
+ *   Drops a pending / kept forward.
+ *
+ * One step over the flat buffer of everything the handle trains, per element, float32, EVERY OPERATION ROUNDED ON ITS OWN:
+ *     g1 = g * c                         c: the clip scale below; g itself when no clip norm is configured
+ *     g2 = g1 + weight_decay * w         on a DECAYED element; g1 elsewhere
+ *     SGD  (Keras / TF 2.0 ApplyKerasMomentum, restated as recalled):  a = momentum * a - lr * g2;  w += a
+ *          nesterov: w += momentum * a - lr * g2 with the new a.  momentum = 0 runs the same formula.  a lives in slot 0 (m); slot 1
+ *          (v) is not touched.
+ *     Adam (ApplyAdam): the arithmetic of the default step on g2; alpha in double on the device from t.
+ *   So the clip acts on the LOSS gradient alone -- what get_gradient returns -- and the decay is added after the clip: Caffe's
+ *   order, and py-faster-rcnn's.  (The decay is L2, inside the gradient; not AdamW's decoupled form.)
+ *   DECAYED elements are the kernels only: never a bias, a BatchNorm's gamma or beta, the bias row of the trainer's fused
+ *   513 x 5K head matrix, an alignment gap or a padding column of the detection head's cls | reg pair.  The set is a sorted table
+ *   of [begin, end) index ranges derived from the handle's layout and uploaded once (decay_ranges reads it: up to `cap` pairs
+ *   into `ranges`, which may be NULL; returns the number of pairs, or -1 for a null handle).  Gaps and padding hold w = 0 and g = 0 and stay exactly zero under every rule.
+ *
+ * The global norm (global_clipnorm = C > 0 only): S = sum g[i]^2 over the whole gradient buffer in float64 (a float32 square is
+ *   exact there), per-workgroup partials in a fixed order and one finishing workgroup; the grid, and with it the order, depends on
+ *   the buffer's size alone: the same bits on every run, no floating-point atomics.  The finishing workgroup writes S and
+ *   c = sqrt(S) > C ? (float)(C / sqrt(S)) : exactly 1.0f to device memory, where the update reads c: NOTHING IS READ BACK BY A STEP.
+ *   A NON-FINITE S (a NaN or an infinite gradient) GIVES c = NaN AND THE STEP CARRIES IT INTO EVERY WEIGHT, as
+ *   tf.clip_by_global_norm does: clipping bounds a large step, it does not hide a broken one.
+ *   grad_norm: *norm = sqrt(S), the pre-clip global norm, and *scale = c of the last applied step; synchronises `stream`.
+ *   RPN_ERR_INVALID when no clip norm is configured or no step has run under it.
+ *
+ * The optimizer's state, HOST arrays in get_layer's layout: slot 0 is m (Adam's first moment / SGD's accumulator), slot 1 is v.
+ *   get_slot / set_slot: kernel + bias of a trained layer (bias NULL for a trained MobileNetV2 conv, and only for it);
+ *   get_bn_slot / set_bn_slot: gamma + beta of a trained MobileNetV2 BatchNorm.  A frozen or unknown layer and a slot other than
+ *   0 or 1 are RPN_ERR_INVALID.  These entries need the device (the state lives there only).  set_* drops a pending / kept forward,
+ *   as set_layer does.  set_steps sets the step count t (>= 0) that Adam's alpha and the next step's number follow.  To resume a
+ *   run: create, set_optimizer, set_layer ..., set_slot ..., set_steps.
+ *
+ * The two kernels on caller buffers (tests, scripts/optimizer_bench.py); every pointer a device pointer:
+ *   rpn_grad_sq_norm: d_g (n) float32, 16-byte aligned -> *d_S, *d_scale as above with C = clipnorm (0: the scale is 1).  d_ws:
+ *     rpn_grad_sq_norm_workspace_bytes(n) bytes.
+ *   rpn_optimizer_apply: one step t (from 1) of `kind` on w, g, m, v (n floats each, 16-byte aligned; d_v may be NULL under SGD).
+ *     d_decay_ranges: n_ranges sorted, disjoint, non-empty [begin, end) pairs inside [0, n), 16-byte aligned (the caller's to get
+ *     right: the values are only ever compared with element indices); d_scale: the device float c, or NULL for none.  kind = RPN_OPT_ADAM without ranges (or with weight_decay = 0) and without d_scale IS the default
+ *     step: it launches adam_kernel.
+ * ---------------------------------------------------------------------------------- */
+#define RPN_OPT_ADAM 0
+#define RPN_OPT_SGD 1
+int rpn_head_trainer_set_optimizer(rpn_head_trainer *t, int kind, float momentum, int nesterov, float weight_decay, float global_clipnorm);
+int rpn_det_head_set_optimizer(rpn_det_head *h, int kind, float momentum, int nesterov, float weight_decay, float global_clipnorm);
+int rpn_head_trainer_grad_norm(rpn_head_trainer *t, double *norm, float *scale, void *stream);
+int rpn_det_head_grad_norm(rpn_det_head *h, double *norm, float *scale, void *stream);
+int rpn_head_trainer_decay_ranges(const rpn_head_trainer *t, long long *ranges, int cap);
+int rpn_det_head_decay_ranges(const rpn_det_head *h, long long *ranges, int cap);
+int rpn_head_trainer_get_slot(rpn_head_trainer *t, const char *name, int slot, float *kernel, float *bias, void *stream);
+int rpn_head_trainer_set_slot(rpn_head_trainer *t, const char *name, int slot, const float *kernel, const float *bias);
+int rpn_head_trainer_get_bn_slot(rpn_head_trainer *t, const char *name, int slot, float *gamma, float *beta, void *stream);
+int rpn_head_trainer_set_bn_slot(rpn_head_trainer *t, const char *name, int slot, const float *gamma, const float *beta);
+int rpn_det_head_get_slot(rpn_det_head *h, const char *name, int slot, float *kernel, float *bias, void *stream);
+int rpn_det_head_set_slot(rpn_det_head *h, const char *name, int slot, const float *kernel, const float *bias);
+int rpn_head_trainer_set_steps(rpn_head_trainer *t, long long steps);
+int rpn_det_head_set_steps(rpn_det_head *h, long long steps);
+size_t rpn_grad_sq_norm_workspace_bytes(long long n);
+int rpn_grad_sq_norm(const float *d_g, long long n, float clipnorm, double *d_S, float *d_scale, void *d_ws, size_t ws_bytes, void *stream);
+int rpn_optimizer_apply(int kind, float *d_w, const float *d_g, float *d_m, float *d_v, long long n, const long long *d_decay_ranges,
+                        int n_ranges, long long t, float lr, float beta_1, float beta_2, float epsilon, float momentum, int nesterov,
+                        float weight_decay, const float *d_scale, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Evaluation: PASCAL VOC average precision of the detections and the recall of the proposals, accumulated on the device (no
  * reference counterpart: its training script stops at val_loss).  The rules are VOCdevkit's VOCevaldet; where the devkit is loose
  * the choice is THIS PROJECT'S and is marked (*).  update / update_proposals enqueue on `stream` and return: no copy to the host,

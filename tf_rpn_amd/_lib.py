@@ -162,6 +162,24 @@ _SIGNATURES = {
     "rpn_det_head_get_activation": (ctypes.c_int, [vp, ctypes.c_char_p, vp, ctypes.c_int, vp]),
     "rpn_dropout_forward": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_int,
                                            vp, vp]),
+    "rpn_head_trainer_set_optimizer": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_float]),
+    "rpn_det_head_set_optimizer": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_float]),
+    "rpn_head_trainer_grad_norm": (ctypes.c_int, [vp, c_double_p, c_float_p, vp]),
+    "rpn_det_head_grad_norm": (ctypes.c_int, [vp, c_double_p, c_float_p, vp]),
+    "rpn_head_trainer_decay_ranges": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
+    "rpn_det_head_decay_ranges": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]),
+    "rpn_head_trainer_get_slot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, c_float_p, vp]),
+    "rpn_head_trainer_set_slot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, c_float_p]),
+    "rpn_head_trainer_get_bn_slot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, c_float_p, vp]),
+    "rpn_head_trainer_set_bn_slot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, c_float_p]),
+    "rpn_det_head_get_slot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, c_float_p, vp]),
+    "rpn_det_head_set_slot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_int, c_float_p, c_float_p]),
+    "rpn_head_trainer_set_steps": (ctypes.c_int, [vp, ctypes.c_longlong]),
+    "rpn_det_head_set_steps": (ctypes.c_int, [vp, ctypes.c_longlong]),
+    "rpn_grad_sq_norm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "rpn_grad_sq_norm": (ctypes.c_int, [vp, ctypes.c_longlong, ctypes.c_float, vp, vp, vp, ctypes.c_size_t, vp]),
+    "rpn_optimizer_apply": (ctypes.c_int, [ctypes.c_int, vp, vp, vp, vp, ctypes.c_longlong, vp, ctypes.c_int,
+                                           ctypes.c_longlong] + [ctypes.c_float] * 5 + [ctypes.c_int, ctypes.c_float, vp, vp]),
     "rpn_evaluator_create": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_float, c_int_p, ctypes.c_int, c_float_p, ctypes.c_int,
                                             ctypes.POINTER(vp)]),
     "rpn_evaluator_destroy": (None, [vp]),

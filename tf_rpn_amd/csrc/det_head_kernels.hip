@@ -10,6 +10,7 @@
 // dropout_forward_kernel here, the two split-float16 variants in det_head_x3_kernels.hip.
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "conv_kernels.h"
 #include "det_head.h"
@@ -315,6 +316,9 @@ struct rpn_det_head {
     double drop_rate = 0.0;
     unsigned long long drop_seed = 0, drop_calls = 0;
     bool kept_dropped = false;
+    // The update rule (rpn_det_head_set_optimizer; default: Adam alone = launch_adam)
+    rpn::OptimConfig opt;
+    rpn::OptimDevice optdev;
 };
 
 namespace {
@@ -365,6 +369,7 @@ void head_free(rpn_det_head *h)
     if (h->status) (void)hipFree(h->status);
     if (h->xmeta) (void)hipFree(h->xmeta);
     h->wx = nullptr, h->status = nullptr, h->xmeta = nullptr;
+    optim_free(&h->optdev);
     h->loaded = 0;               // the weights went with the buffers
     h->kept_rows = 0;
 }
@@ -477,6 +482,22 @@ hipError_t head_repack(rpn_det_head *h, hipStream_t s)
 }
 
 bool head_trains_x3(const rpn_det_head *h) { return h->train_precision == RPN_PRECISION_F16X3; }
+
+// The decayed elements of the parameter layout, as sorted disjoint [begin, end) pairs: W1, W2 and the real columns [0, 5 C) of every
+// row of Wp -- one range per row when the pair is padded (npad > 5 C), so that no bias and no padding column is ever decayed.
+std::vector<long long> head_decay_ranges(const rpn_det_head *h)
+{
+    std::vector<long long> out;
+    auto add = [&](size_t b, size_t e) { out.push_back((long long)b), out.push_back((long long)e); };
+    add(h->off[0], h->off[0] + (size_t)h->k1 * h->h1);
+    add(h->off[2], h->off[2] + (size_t)h->h1 * h->h2);
+    if (h->npad == 5 * h->c) {
+        add(h->off[4], h->off[4] + (size_t)h->h2 * h->npad);
+    } else {
+        for (int r = 0; r < h->h2; ++r) add(h->off[4] + (size_t)r * h->npad, h->off[4] + (size_t)r * h->npad + 5 * (size_t)h->c);
+    }
+    return out;
+}
 
 // before a training head's image is read
 hipError_t head_fresh_image(rpn_det_head *h, hipStream_t s) { return head_trains_x3(h) && h->x_stale ? head_repack(h, s) : hipSuccess; }
@@ -807,17 +828,93 @@ extern "C" int rpn_det_head_adam_step(rpn_det_head *h, float lr, float beta_1, f
     const char *who = "rpn_det_head_adam_step";
     RPN_REQUIRE(h, "%s: null head", who);
     RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
-    RPN_REQUIRE(beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f && epsilon > 0.0f, "%s: beta_1 = %g, beta_2 = %g, epsilon = %g",
-                who, (double)beta_1, (double)beta_2, (double)epsilon);
+    RPN_REQUIRE(h->opt.kind == RPN_OPT_SGD || (beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f && epsilon > 0.0f),
+                "%s: beta_1 = %g, beta_2 = %g, epsilon = %g", who, (double)beta_1, (double)beta_2, (double)epsilon);
     RPN_REQUIRE(h->loaded == 15u, "%s: set_layer has not been called for every layer (fc1, fc2, cls, reg)", who);
     const int st = head_ensure_device(h);
     if (st != RPN_OK) return st;
     h->kept_rows = 0;            // a kept forward was made with the weights this step changes
-    hipError_t e = launch_adam(h->w, h->g, h->m, h->v, (long long)h->n, h->t + 1, lr, beta_1, beta_2, epsilon, as_stream(stream));
+    hipError_t e = hipSuccess;
+    if (h->opt.is_default()) {
+        e = launch_adam(h->w, h->g, h->m, h->v, (long long)h->n, h->t + 1, lr, beta_1, beta_2, epsilon, as_stream(stream));
+    } else {                     // another rule, a decay or a clip norm (under SGD beta_1, beta_2 and epsilon are ignored, lr is SGD's)
+        const std::vector<long long> ranges = h->optdev.buf ? std::vector<long long>() : head_decay_ranges(h);
+        const int so = optim_step(who, h->opt, &h->optdev, ranges.data(), (int)(ranges.size() / 2), h->w, h->g, h->m, h->v, (long long)h->n,
+                                  h->t + 1, lr, beta_1, beta_2, epsilon, as_stream(stream));
+        if (so != RPN_OK) return so;
+    }
     h->x_stale = true;
     if (e == hipSuccess) e = head_fresh_image(h, as_stream(stream));          // split float16: repacked here, without a synchronisation
     if (e != hipSuccess) return fail(RPN_ERR_NO_DEVICE, "%s: %s", who, hipGetErrorString(e));
     h->t += 1;
+    return RPN_OK;
+}
+
+// ---- C ABI: the update rule and the optimizer's state (include/rpn_hip.h, "Optimizers") -------------------------------------------------
+extern "C" int rpn_det_head_set_optimizer(rpn_det_head *h, int kind, float momentum, int nesterov, float weight_decay, float global_clipnorm)
+{
+    const char *who = "rpn_det_head_set_optimizer";
+    RPN_REQUIRE(h, "%s: null head", who);
+    const int st = optim_check_config(who, kind, momentum, nesterov, weight_decay, global_clipnorm);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0", who);
+    h->kept_rows = 0;
+    if (kind != h->opt.kind) {   // the other rule's m and v mean nothing to this one
+        if (h->m) {
+            RPN_HIP_CHECK(hipMemset(h->m, 0, h->n * sizeof(float)));
+            RPN_HIP_CHECK(hipMemset(h->v, 0, h->n * sizeof(float)));
+        }
+        h->t = 0;
+    }
+    h->opt.kind = kind, h->opt.momentum = momentum, h->opt.nesterov = nesterov, h->opt.weight_decay = weight_decay;
+    h->opt.clipnorm = global_clipnorm;
+    h->optdev.stepped = false;
+    return RPN_OK;
+}
+
+extern "C" int rpn_det_head_grad_norm(rpn_det_head *h, double *norm, float *scale, void *stream)
+{
+    RPN_REQUIRE(h, "rpn_det_head_grad_norm: null head");
+    return optim_grad_norm("rpn_det_head_grad_norm", h->opt, h->optdev, norm, scale, as_stream(stream));
+}
+
+extern "C" int rpn_det_head_decay_ranges(const rpn_det_head *h, long long *ranges, int cap)
+{
+    if (!h) return -1;
+    const std::vector<long long> r = head_decay_ranges(h);
+    const int n = (int)(r.size() / 2);
+    for (int i = 0; ranges && i < std::min(n, cap); ++i) ranges[2 * i] = r[2 * i], ranges[2 * i + 1] = r[2 * i + 1];
+    return n;
+}
+
+static int head_slot_access(rpn_det_head *h, const char *who, const char *name, int slot, float *kernel, float *bias, bool write, void *stream)
+{
+    RPN_REQUIRE(h && name && kernel && bias, "%s: null pointer", who);
+    RPN_REQUIRE(layer_index(name) >= 0, "%s: unknown layer '%s' (fc1, fc2, cls, reg)", who, name);
+    RPN_REQUIRE(slot == 0 || slot == 1, "%s: slot %d (0: m, 1: v)", who, slot);
+    RPN_REQUIRE(h->trainable, "%s: the head was created with trainable = 0: it has no optimizer state", who);
+    const int st = head_ensure_device(h);
+    if (st != RPN_OK) return st;
+    if (write) h->kept_rows = 0;
+    return head_copy_layer(h, slot == 0 ? h->m : h->v, name, kernel, bias, write, as_stream(stream));
+}
+
+extern "C" int rpn_det_head_get_slot(rpn_det_head *h, const char *name, int slot, float *kernel, float *bias, void *stream)
+{
+    return head_slot_access(h, "rpn_det_head_get_slot", name, slot, kernel, bias, false, stream);
+}
+
+extern "C" int rpn_det_head_set_slot(rpn_det_head *h, const char *name, int slot, const float *kernel, const float *bias)
+{
+    return head_slot_access(h, "rpn_det_head_set_slot", name, slot, const_cast<float *>(kernel), const_cast<float *>(bias), true, nullptr);
+}
+
+extern "C" int rpn_det_head_set_steps(rpn_det_head *h, long long steps)
+{
+    RPN_REQUIRE(h && steps >= 0, "rpn_det_head_set_steps: null head or steps = %lld < 0", steps);
+    RPN_REQUIRE(h->trainable, "rpn_det_head_set_steps: the head was created with trainable = 0");
+    h->kept_rows = 0;
+    h->t = steps;
     return RPN_OK;
 }
 

@@ -49,4 +49,44 @@ hipError_t launch_head_backward(const float *graw_reg, const float *graw_cls, co
 hipError_t launch_adam(float *w, const float *g, float *m, float *v, long long n, long long t, float lr, float b1, float b2, float eps,
                        hipStream_t s);
 
+// ---- the configurable update (optim_kernels.hip): SGD momentum, L2 weight decay, clipping by the global norm ---------------------
+// Per element, float32, every operation rounded on its own (c: the clip scale, 1 without a clip norm; wd: the decay):
+//   g1 = g c;  g2 = g1 + wd w on a decayed element, g1 elsewhere
+//   SGD (Keras / TF 2.0 ApplyKerasMomentum, restated as recalled): a = mu a - lr g2;  w += a  (nesterov: w += mu a - lr g2, the new a);
+//     a lives in m, v is not touched
+//   Adam: launch_adam's arithmetic on g2
+// So the clip acts on the loss gradient alone (what get_gradient returns) and the decay joins after it: Caffe's order and
+// py-faster-rcnn's.  A non-finite squared norm gives c = NaN and the step propagates it into every weight, as tf.clip_by_global_norm does.
+struct OptimConfig {
+    int kind = 0;                                // RPN_OPT_ADAM / RPN_OPT_SGD
+    float momentum = 0.0f, weight_decay = 0.0f, clipnorm = 0.0f;
+    int nesterov = 0;
+    // what both handles launch today: launch_adam, no norm pass
+    bool is_default() const { return kind == 0 && weight_decay == 0.0f && clipnorm == 0.0f; }
+};
+// RPN_ERR_INVALID with a message for a bad value, before any device work
+int optim_check_config(const char *who, int kind, float momentum, int nesterov, float weight_decay, float clipnorm);
+
+// the update's own device memory: S (double) | c (float) | the norm's partials | the decayed ranges; allocated at the first step that
+// needs it.  ranges: sorted, disjoint [begin, end) pairs of element indices into the flat buffer.
+struct OptimDevice {
+    char *buf = nullptr;
+    int n_ranges = 0;
+    bool stepped = false;                        // a step has written S and c under the current configuration
+};
+void optim_free(OptimDevice *d);
+
+// S = sum g[i]^2 in float64 (a float32 square is exact there): per-workgroup partials in a fixed order, then one finishing workgroup;
+// the grid, and so the order, depends on n alone.  Writes S and c = clipnorm > 0 && sqrt(S) > clipnorm ? (float)(clipnorm / sqrt(S)) : 1
+// (NaN when S is not finite).  g 16-byte aligned; part: grad_norm_ws_bytes(n) bytes.
+size_t grad_norm_ws_bytes(long long n);
+hipError_t launch_grad_sq_norm(const float *g, long long n, float clipnorm, double *part, double *S, float *scale, hipStream_t s);
+
+// one update of the flat buffer under cfg: the norm pass when a clip norm is set, then one launch.  t: the number of this step, from 1.
+// Never called with cfg.is_default(): that step is launch_adam.
+int optim_step(const char *who, const OptimConfig &cfg, OptimDevice *d, const long long *ranges, int n_ranges, float *w, const float *g,
+               float *m, float *v, long long n, long long t, float lr, float b1, float b2, float eps, hipStream_t s);
+// the pre-clip global norm and the scale of the last step (synchronises s)
+int optim_grad_norm(const char *who, const OptimConfig &cfg, const OptimDevice &d, double *norm, float *scale, hipStream_t s);
+
 }  // namespace rpn

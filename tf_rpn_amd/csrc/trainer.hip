@@ -94,6 +94,9 @@ struct rpn_head_trainer {
     TrainerDevice d{};
     std::vector<void *> allocs;                 // what d points into: every hipMalloc of this trainer
     PackedShape ps_conv{}, ps_head{};
+    // ---- the update rule (rpn_head_trainer_set_optimizer; default: Adam alone = launch_adam) ----
+    OptimConfig opt;
+    OptimDevice optdev;
     // ---- the VGG16 backbone (rpn_model_trainer_create; backbone_*) ----
     // bb_from: the first trained conv (index into kVgg), -1 on a head-only trainer
     int bb_from = -1, img = 0;
@@ -212,12 +215,13 @@ float *store_dev(const rpn_head_trainer *t, int store)
 float *param_dev(const rpn_head_trainer *t, int i) { return store_dev(t, t->params[i].store) + t->params[i].off; }
 float *param_grad(const rpn_head_trainer *t, int i) { return t->d.g + t->params[i].off; }
 
-// One slice between the caller's dense HOST array and its store: the device buffer once the trainer has one (grad: the gradient
-// buffer instead), the host copy before.  On the device a slice moves as the span it lies in, staged on the host.
-int param_copy(rpn_head_trainer *t, const Param &p, float *user, bool write, bool grad, hipStream_t s)
+// One slice between the caller's dense HOST array and its store: the device buffer once the trainer has one (other: a device buffer
+// of kMaster's layout instead -- the gradients, Adam's m or v), the host copy before.  On the device a slice moves as the span it
+// lies in, staged on the host.
+int param_copy(rpn_head_trainer *t, const Param &p, float *user, bool write, float *other, hipStream_t s)
 {
     const size_t span = (size_t)(p.rows - 1) * p.stride + p.len;
-    float *dev = t->d.w ? (grad ? t->d.g : store_dev(t, p.store)) + p.off : nullptr;
+    float *dev = t->d.w ? (other ? other : store_dev(t, p.store)) + p.off : nullptr;
     std::vector<float> staged(dev ? span : 0);
     float *h = dev ? staged.data() : t->host[p.store].data() + p.off;
     if (dev && (!write || p.rows > 1)) {        // (a strided write keeps what lies between its rows)
@@ -232,16 +236,22 @@ int param_copy(rpn_head_trainer *t, const Param &p, float *user, bool write, boo
     return RPN_OK;
 }
 
+int trainer_device(rpn_head_trainer *t);
+
 // The C ABI's parameter access in one place.  Layer `name` (bn: a BatchNorm, named by its conv, "<conv>_BN" or its Keras name) ->
 // its table entries, with every refusal; then user[k] <-> the layer's k-th entry.  user: {kernel, bias} (a MobileNetV2 conv has no
 // bias: NULL) or, bn, {gamma, beta, mean, var}; written only by kGet / kGrad.  kGrad reads the gradients of the last update step
-// (kMaster entries only: a BatchNorm's moving statistics have none).
-enum Access { kSet, kGet, kGrad };
+// (kMaster entries only: a BatchNorm's moving statistics have none).  kSlotGet / kSlotSet: the optimizer's m (slot 0) or v (slot 1)
+// of the same entries as kGrad; the state lives on the device only, which these two allocate.
+enum Access { kSet, kGet, kGrad, kSlotGet, kSlotSet };
 
-int param_access(rpn_head_trainer *t, const char *what, const char *name, bool bn, Access acc, const float *const (&user)[4], void *stream)
+int param_access(rpn_head_trainer *t, const char *what, const char *name, bool bn, Access acc, const float *const (&user)[4], void *stream,
+                 int slot = 0)
 {
-    RPN_REQUIRE(t && name && user[0] && (!bn || (user[1] && (acc == kGrad || (user[2] && user[3])))), "%s: null argument", what);
-    if (acc == kSet) t->pending_B = 0;          // new parameters: a pending forward no longer matches them
+    RPN_REQUIRE(t && name && user[0] && (!bn || (user[1] && (acc >= kGrad || (user[2] && user[3])))), "%s: null argument", what);
+    RPN_REQUIRE(acc < kSlotGet || slot == 0 || slot == 1, "%s: slot %d (0: m, 1: v)", what, slot);
+    if (acc == kSet || acc == kSlotSet) t->pending_B = 0;          // new parameters: a pending forward no longer matches them
+    const bool write = acc == kSet || acc == kSlotSet;
     const char *from = t->mn_from >= 0 ? mn_table()[t->mn_from].name.c_str() : (t->bb_from >= 0 ? kVgg[t->bb_from].name : "");
     const int mi = t->mn_from >= 0 ? mn_index(name, bn) : -1;
     int first, count;
@@ -252,7 +262,7 @@ int param_access(rpn_head_trainer *t, const char *what, const char *name, bool b
                     bn || acc == kSet ? "" : "layer ", name, from);
         RPN_REQUIRE(bn || !user[1], "%s: '%s' has no bias (pass NULL)", what, name);
         first = mn_param(t, mi) + (bn ? kGamma : kKernel);
-        count = bn ? (acc == kGrad ? 2 : 4) : 1;
+        count = bn ? (acc >= kGrad ? 2 : 4) : 1;
     } else {
         const int li = layer_index(name);
         const int bi = t->bb_from >= 0 ? vgg_index(name) : -1;
@@ -269,15 +279,25 @@ int param_access(rpn_head_trainer *t, const char *what, const char *name, bool b
         count = 2;
     }
     Param *p = &t->params[first];
-    if (acc != kSet) {
+    if (acc == kGet || acc == kGrad) {
         for (int k = 0; k < count; ++k)
             RPN_REQUIRE(p[k].loaded, bn ? "%s: BatchNorm '%s' was never set" : "%s: layer '%s' was never set", what, name);
         RPN_REQUIRE(acc != kGrad || p->store == kMaster, "%s: layer '%s' is frozen (training starts at %s): it has no gradient", what, name,
                     from);
         RPN_REQUIRE(acc != kGrad || t->t > 0, "%s: no update step has run", what);
     }
+    float *other = nullptr;
+    if (acc >= kSlotGet) {
+        RPN_REQUIRE(p->store == kMaster, "%s: layer '%s' is frozen (training starts at %s): it has no optimizer state", what, name, from);
+        const int st = trainer_device(t);
+        if (st != RPN_OK) return st;
+        other = slot == 0 ? t->d.m : t->d.v;
+    } else if (acc == kGrad) {
+        RPN_REQUIRE(t->d.w, "%s: no update step has run", what);      // (a step count given by set_steps is no step)
+        other = t->d.g;
+    }
     for (int k = 0; k < count; ++k) {
-        const int st = param_copy(t, p[k], const_cast<float *>(user[k]), acc == kSet, acc == kGrad, as_stream(stream));
+        const int st = param_copy(t, p[k], const_cast<float *>(user[k]), write, other, as_stream(stream));
         if (st != RPN_OK) return st;
         if (acc == kSet) p[k].loaded = true;
     }
@@ -309,6 +329,7 @@ void trainer_free(rpn_head_trainer *t)
     for (void *p : t->allocs) (void)hipFree(p);
     t->allocs.clear();
     t->d = TrainerDevice{};
+    optim_free(&t->optdev);
 }
 
 // pixels per image of layer i's input / output
@@ -660,6 +681,28 @@ void trainer_host_stores(rpn_head_trainer *t)
     for (int s = 0; s < kBnStep; ++s) t->host[s].assign(t->size[s], 0.0f);
 }
 
+// The decayed elements of kMaster, as sorted disjoint [begin, end) pairs: every trained kernel -- rpn_conv's, rows 0 .. 511 of the fused
+// head matrix (the rpn_reg and rpn_cls columns together; row 512 is its bias), each trained backbone conv's -- and nothing else: no
+// bias, gamma or beta and no alignment gap.  Host arithmetic on the table.
+std::vector<long long> trainer_decay_ranges(const rpn_head_trainer *t)
+{
+    std::vector<int> idx = {kConvK, kHeadK, kClsK};
+    for (int i = std::max(t->bb_from, 0); t->bb_from >= 0 && i < 13; ++i) idx.push_back(vgg_param(i) + kKernel);
+    for (int i = std::max(t->mn_from, 0); t->mn_from >= 0 && i < kMnLayers; ++i) idx.push_back(mn_param(t, i) + kKernel);
+    std::vector<std::pair<long long, long long>> spans;
+    for (int i : idx) {
+        const Param &p = t->params[i];
+        spans.push_back({(long long)p.off, (long long)(p.off + (size_t)(p.rows - 1) * p.stride + p.len)});
+    }
+    std::sort(spans.begin(), spans.end());
+    std::vector<long long> out;
+    for (const auto &sp : spans) {
+        if (!out.empty() && sp.first <= out.back()) out.back() = std::max(out.back(), sp.second);
+        else out.push_back(sp.first), out.push_back(sp.second);
+    }
+    return out;
+}
+
 }  // namespace
 
 // ---- C ABI: creation ----------------------------------------------------------------------------------------------------------------
@@ -834,8 +877,12 @@ static int trainer_check_forward(const rpn_head_trainer *t, const char *what, co
     return RPN_OK;
 }
 
-static int trainer_check_adam(const char *what, float lr, float beta_1, float beta_2, float epsilon)
+static int trainer_check_adam(const rpn_head_trainer *t, const char *what, float lr, float beta_1, float beta_2, float epsilon)
 {
+    if (t->opt.kind == RPN_OPT_SGD) {           // beta_1, beta_2 and epsilon are ignored
+        RPN_REQUIRE(std::isfinite(lr) && lr >= 0.0f, "%s: bad SGD learning rate", what);
+        return RPN_OK;
+    }
     RPN_REQUIRE(std::isfinite(lr) && lr >= 0.0f && beta_1 >= 0.0f && beta_1 < 1.0f && beta_2 >= 0.0f && beta_2 < 1.0f &&
                     std::isfinite(epsilon) && epsilon >= 0.0f,
                 "%s: bad Adam hyper-parameters", what);
@@ -914,6 +961,12 @@ static int trainer_backward(rpn_head_trainer *t, const char *what, const float *
     if (e == hipSuccess) e = launch_colsum(t->d.dS, P, 512, t->d.part, param_grad(t, kConvB), s);
     if (e == hipSuccess && t->bb_from >= 0) e = backbone_backward(t, B, d_feature_grad, s);
     if (e == hipSuccess && t->mn_from >= 0) e = mn_backward(t, d_imgs, B, d_feature_grad, s);
+    if (e == hipSuccess && !t->opt.is_default()) {          // another rule, a decay or a clip norm: the norm pass (if any) + one launch
+        ++t->t;
+        const std::vector<long long> ranges = t->optdev.buf ? std::vector<long long>() : trainer_decay_ranges(t);
+        return optim_step(what, t->opt, &t->optdev, ranges.data(), (int)(ranges.size() / 2), t->d.w, t->d.g, t->d.m, t->d.v,
+                          (long long)t->size[kMaster], t->t, lr, beta_1, beta_2, epsilon, s);
+    }
     if (e == hipSuccess) {
         ++t->t;
         e = launch_adam(t->d.w, t->d.g, t->d.m, t->d.v, (long long)t->size[kMaster], t->t, lr, beta_1, beta_2, epsilon, s);
@@ -930,7 +983,7 @@ extern "C" int rpn_head_trainer_step(rpn_head_trainer *t, const float *d_imgs, i
     int st = trainer_check_forward(t, what, d_imgs, B, d_bbox_deltas, d_bbox_labels, d_losses);
     if (st != RPN_OK) return st;
     RPN_REQUIRE(update == 0 || update == 1, "rpn_head_trainer_step: update must be 0 or 1");
-    if (update && (st = trainer_check_adam(what, lr, beta_1, beta_2, epsilon)) != RPN_OK) return st;
+    if (update && (st = trainer_check_adam(t, what, lr, beta_1, beta_2, epsilon)) != RPN_OK) return st;
     if ((st = trainer_check_loaded(t, what)) != RPN_OK) return st;
     st = trainer_forward(t, what, d_imgs, B, d_bbox_deltas, d_bbox_labels, update, d_losses, stream);
     if (st != RPN_OK || !update) return st;
@@ -967,7 +1020,7 @@ extern "C" int rpn_head_trainer_backward(rpn_head_trainer *t, const float *d_img
                 "rpn_head_trainer_backward: d_feature_grad given to a trainer with a frozen backbone: nothing below the feature tap trains "
                 "(create the trainer with rpn_model_trainer_create and a train_from layer)");
     RPN_REQUIRE(d_imgs, "rpn_head_trainer_backward: null argument");
-    const int st = trainer_check_adam(what, lr, beta_1, beta_2, epsilon);
+    const int st = trainer_check_adam(t, what, lr, beta_1, beta_2, epsilon);
     if (st != RPN_OK) return st;
     RPN_REQUIRE(t->pending_B > 0, "rpn_head_trainer_backward: no pending rpn_head_trainer_forward with train = 1 on this trainer");
     RPN_REQUIRE(B == t->pending_B, "rpn_head_trainer_backward: batch %d, the pending forward ran %d images", B, t->pending_B);
@@ -977,6 +1030,73 @@ extern "C" int rpn_head_trainer_backward(rpn_head_trainer *t, const float *d_img
 }
 
 extern "C" long long rpn_head_trainer_steps(const rpn_head_trainer *t) { return t ? t->t : -1; }
+
+// ---- C ABI: the update rule and the optimizer's state (include/rpn_hip.h, "Optimizers") -------------------------------------------------
+extern "C" int rpn_head_trainer_set_optimizer(rpn_head_trainer *t, int kind, float momentum, int nesterov, float weight_decay,
+                                              float global_clipnorm)
+{
+    const char *who = "rpn_head_trainer_set_optimizer";
+    RPN_REQUIRE(t, "%s: null argument", who);
+    const int st = optim_check_config(who, kind, momentum, nesterov, weight_decay, global_clipnorm);
+    if (st != RPN_OK) return st;
+    t->pending_B = 0;
+    t->pending_imgs = nullptr;
+    if (kind != t->opt.kind) {                  // the other rule's m and v mean nothing to this one
+        if (t->d.w) {
+            RPN_HIP_CHECK(hipMemset(t->d.m, 0, t->size[kMaster] * sizeof(float)));
+            RPN_HIP_CHECK(hipMemset(t->d.v, 0, t->size[kMaster] * sizeof(float)));
+        }
+        t->t = 0;
+    }
+    t->opt.kind = kind, t->opt.momentum = momentum, t->opt.nesterov = nesterov, t->opt.weight_decay = weight_decay;
+    t->opt.clipnorm = global_clipnorm;
+    t->optdev.stepped = false;
+    return RPN_OK;
+}
+
+extern "C" int rpn_head_trainer_grad_norm(rpn_head_trainer *t, double *norm, float *scale, void *stream)
+{
+    RPN_REQUIRE(t, "rpn_head_trainer_grad_norm: null argument");
+    return optim_grad_norm("rpn_head_trainer_grad_norm", t->opt, t->optdev, norm, scale, as_stream(stream));
+}
+
+extern "C" int rpn_head_trainer_decay_ranges(const rpn_head_trainer *t, long long *ranges, int cap)
+{
+    if (!t) return -1;
+    const std::vector<long long> r = trainer_decay_ranges(t);
+    const int n = (int)(r.size() / 2);
+    for (int i = 0; ranges && i < std::min(n, cap); ++i) ranges[2 * i] = r[2 * i], ranges[2 * i + 1] = r[2 * i + 1];
+    return n;
+}
+
+extern "C" int rpn_head_trainer_get_slot(rpn_head_trainer *t, const char *name, int slot, float *kernel, float *bias, void *stream)
+{
+    return param_access(t, "rpn_head_trainer_get_slot", name, false, kSlotGet, {kernel, bias}, stream, slot);
+}
+
+extern "C" int rpn_head_trainer_set_slot(rpn_head_trainer *t, const char *name, int slot, const float *kernel, const float *bias)
+{
+    return param_access(t, "rpn_head_trainer_set_slot", name, false, kSlotSet, {kernel, bias}, nullptr, slot);
+}
+
+extern "C" int rpn_head_trainer_get_bn_slot(rpn_head_trainer *t, const char *name, int slot, float *gamma, float *beta, void *stream)
+{
+    return param_access(t, "rpn_head_trainer_get_bn_slot", name, true, kSlotGet, {gamma, beta}, stream, slot);
+}
+
+extern "C" int rpn_head_trainer_set_bn_slot(rpn_head_trainer *t, const char *name, int slot, const float *gamma, const float *beta)
+{
+    return param_access(t, "rpn_head_trainer_set_bn_slot", name, true, kSlotSet, {gamma, beta}, nullptr, slot);
+}
+
+extern "C" int rpn_head_trainer_set_steps(rpn_head_trainer *t, long long steps)
+{
+    RPN_REQUIRE(t && steps >= 0, "rpn_head_trainer_set_steps: null trainer or steps = %lld < 0", steps);
+    t->pending_B = 0;
+    t->pending_imgs = nullptr;
+    t->t = steps;
+    return RPN_OK;
+}
 
 // ---- C ABI: the arithmetic of the backbone's backward products ---------------------------------------------------------------------------
 extern "C" int rpn_head_trainer_set_backward_precision(rpn_head_trainer *t, int precision)

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from . import _optimizer as O
 
 
 class FeatureExtractor(object):
@@ -63,7 +64,7 @@ MOBILENET_V2_CONVS = (("Conv1", "expanded_conv_depthwise", "expanded_conv_projec
 BN_KEYS = ("gamma", "beta", "mean", "var")
 
 
-class RPNModel(object):
+class RPNModel(O.OptimizerMixin):
     _t = None
     _h = None
 
@@ -366,7 +367,8 @@ class RPNModel(object):
 
     # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
     def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None,
-                train_backbone=False, backward_precision="f32"):
+                train_backbone=False, backward_precision="f32", optimizer="adam", momentum=0.0, nesterov=False, weight_decay=0.0,
+                global_clipnorm=None):
         """``rpn_model.compile(optimizer=tf.optimizers.Adam(learning_rate), loss=[reg_loss, cls_loss])`` (trainer.py:54-56).
 
         ``train_backbone_from=None`` (default) trains the RPN head (``rpn_conv``, ``rpn_cls``, ``rpn_reg``) on a frozen backbone,
@@ -399,7 +401,14 @@ class RPNModel(object):
         Adam is TF 2.0's ApplyAdam (as recalled from its sources): alpha = lr sqrt(1 - beta_2^t) / (1 - beta_1^t),
         m += (g - m)(1 - beta_1), v += (g^2 - v)(1 - beta_2), w -= alpha m / (sqrt(v) + epsilon), m = v = 0 at compile, t = the
         number of applied steps.  The trainer starts from the weights last given to ``set_weights`` / ``load_weights`` (or from
-        the trained ones when compiled again)."""
+        the trained ones when compiled again).
+
+        ``optimizer``: ``"adam"`` (default) or ``"sgd"`` with ``momentum`` in [0, 1) and ``nesterov``; ``weight_decay``: L2 decay of
+        every trained kernel (never a bias, gamma or beta), added to the gradient after the clip; ``global_clipnorm``: clip the whole
+        gradient by its global norm (None / 0: off; NOT Keras' per-tensor ``clipnorm``).  The defaults launch exactly the Adam step
+        this method always compiled.  ``learning_rate``: a float or a callable ``f(applied_steps) -> float`` evaluated with
+        ``train_steps()`` before every update; ``model.learning_rate`` reads and sets it.  Every ``compile`` builds a new trainer
+        with zero optimizer state: ``set_optimizer_state`` / ``load_optimizer_state`` come AFTER it.  README, "Optimizers"."""
         if isinstance(trainable, str) or set(trainable) != set(HEAD_LAYERS):
             raise ValueError("trainable=%r: trainable names the RPN head, which trains on a frozen backbone -- it must be exactly %s; "
                              "to train backbone convs too use train_backbone_from=<first trained conv>" % (trainable, HEAD_LAYERS))
@@ -428,7 +437,10 @@ class RPNModel(object):
                              + ("the %s backward has no such kernels" % self.backbone if self.backbone != "vgg16" else
                                 "this compile trains the head only, so there is no backbone backward (give train_backbone_from or "
                                 "train_backbone=True)"))
-        self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
+        cfg = O.check_config(optimizer, momentum, nesterov, weight_decay, global_clipnorm)
+        lr = O.check_learning_rate(learning_rate)
+        self._lr = lr
+        self._opt = (0.0 if callable(lr) else lr, float(beta_1), float(beta_2), float(epsilon))
         if self._t:
             self._sync_head()       # layers the new trainer freezes run on the handle: they keep what the old one trained
             got = self.get_weights()
@@ -451,6 +463,9 @@ class RPNModel(object):
         self._t = t
         self._pending = None
         self._train_from = train_backbone_from
+        self._opt_cfg = cfg
+        if cfg != O.OptimizerMixin._opt_cfg:
+            self._apply_optimizer_config()
         L.check(L.lib().rpn_head_trainer_set_backward_precision(t, L.PRECISIONS[backward_precision]),
                 "rpn_head_trainer_set_backward_precision")
         for name in self._head:
@@ -501,6 +516,28 @@ class RPNModel(object):
         kernel, bias = self._head[name] if name in HEAD_LAYERS else self._backbone[name]
         L.check(L.lib().rpn_head_trainer_set_layer(self._t, name.encode(), kernel.ctypes.data_as(L.c_float_p),
                                                    bias.ctypes.data_as(L.c_float_p)), "rpn_head_trainer_set_layer(%s)" % name)
+
+    # what OptimizerMixin asks for
+    def _opt_target(self):
+        return (self._t if self._t else None), "rpn_head_trainer"
+
+    def _opt_entries(self):
+        out = []
+        trained = self.trained_layers()
+        for layer in self.layers:
+            name = layer["name"]
+            if name not in trained:
+                continue
+            if self._is_mn(name):
+                C = layer["shape"][2] if layer["kind"] == 2 else layer["shape"][3]
+                out.append((name, name, False, {"kernel": tuple(layer["shape"])}))
+                out.append((layer["bn_name"], name, True, {"gamma": (C,), "beta": (C,)}))
+            else:
+                out.append((name, name, False, {"kernel": tuple(layer["shape"]), "bias": (layer["shape"][3],)}))
+        return out
+
+    def _opt_touch(self):
+        self._pending = None
 
     def get_gradients(self):
         """{layer: {"kernel", "bias"}}: the gradient of the total loss at the last ``train_on_batch`` (test hook).  A trained
@@ -619,7 +656,7 @@ class RPNModel(object):
         imgs, deltas, labels, B = self._batch_args(x, y)
         self._pending = None                    # the library's forward replaces a pending one
         losses = torch.empty((3,), dtype=torch.float32, device="cuda")
-        lr, b1, b2, eps = self._opt
+        lr, b1, b2, eps = self._step_opt() if update else self._opt
         L.check(L.lib().rpn_head_trainer_step(self._t, L.ptr(imgs), B, L.ptr(deltas), L.ptr(labels), 1 if update else 0, lr, b1,
                                               b2, eps, L.ptr(losses), L.stream_ptr()), "rpn_head_trainer_step")
         if update:
@@ -687,7 +724,7 @@ class RPNModel(object):
                                "test_on_batch replace it)")
         imgs, B = pend
         self._pending = None
-        lr, b1, b2, eps = self._opt
+        lr, b1, b2, eps = self._step_opt()
         L.check(L.lib().rpn_head_trainer_backward(self._t, L.ptr(imgs), B, L.ptr(feature_grad), lr, b1, b2, eps, L.stream_ptr()),
                 "rpn_head_trainer_backward")
         self._head_dirty = True

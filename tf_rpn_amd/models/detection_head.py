@@ -39,6 +39,7 @@ import torch
 
 from .. import _lib as L
 from ..utils import roi_utils
+from . import _optimizer as O
 
 LAYERS = ("fc1", "fc2", "cls", "reg")
 PRECISIONS = ("f32", "f16x3")
@@ -88,7 +89,7 @@ class _HeadFunction(torch.autograd.Function):
         return gp, None, None
 
 
-class DetectionHead(object):
+class DetectionHead(O.OptimizerMixin):
     """``head(pooled) -> (cls_logits (B,R,C), reg_pred (B,R,4C))`` on torch CUDA tensors; ``pooled`` (B,R,ph,pw,Cf) is what
     ``roi_utils.roi_pooling`` returns, B*R <= ``max_rois``.
 
@@ -308,8 +309,16 @@ class DetectionHead(object):
         return self._forward(x.detach(), keep=False)
 
     # ---- optimiser ----------------------------------------------------------------------
-    def compile(self, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7, precision="f32"):
+    def compile(self, learning_rate=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-7, precision="f32", optimizer="adam", momentum=0.0,
+                nesterov=False, weight_decay=0.0, global_clipnorm=None):
         """Adam's parameters (Keras' defaults but for the learning rate); the moments live in the head from its creation.
+
+        ``optimizer``: ``"adam"`` (default) or ``"sgd"`` with ``momentum`` in [0, 1) and ``nesterov``; ``weight_decay``: L2 decay of
+        the four kernels (never the biases), added to the gradient after the clip; ``global_clipnorm``: clip the whole gradient by
+        its global norm (None / 0: off; NOT Keras' per-tensor ``clipnorm``).  The defaults launch exactly the Adam step the head
+        always ran.  ``learning_rate``: a float or a callable ``f(applied_steps) -> float`` evaluated with ``train_steps()`` before
+        every ``apply_gradients()``; ``head.learning_rate`` reads and sets it.  Compiling again with the same ``optimizer`` keeps
+        the state; the other one zeroes ``m``, ``v`` and the step count.  README, "Optimizers".
 
         ``precision``: what a trainable head computes in from here on -- ``"f32"`` (exact float32) or ``"f16x3"`` (every product of the
         forward and the backward in split float16; master weights, gradients, bias sums and Adam stay float32).  Compiling again
@@ -318,10 +327,28 @@ class DetectionHead(object):
             raise ValueError("precision must be one of %r, got %r" % (PRECISIONS, precision))
         if precision == "f16x3" and not self.trainable:
             raise ValueError("compile(precision='f16x3') needs a trainable head; an inference head takes its precision at construction")
+        cfg = O.check_config(optimizer, momentum, nesterov, weight_decay, global_clipnorm)
+        lr = O.check_learning_rate(learning_rate)
+        if cfg != (0, cfg[1], cfg[2], 0.0, 0.0) and not self.trainable:
+            raise ValueError("optimizer, weight_decay and global_clipnorm need a trainable head")
         if self.trainable:
             self._serial += 1
             L.check(L.lib().rpn_det_head_set_train_precision(self._h, L.PRECISIONS[precision]), "rpn_det_head_set_train_precision")
-        self._opt = (float(learning_rate), float(beta_1), float(beta_2), float(epsilon))
+        self._lr = lr
+        self._opt = (0.0 if callable(lr) else lr, float(beta_1), float(beta_2), float(epsilon))
+        if self.trainable:
+            self._opt_cfg = cfg
+            self._apply_optimizer_config()
+
+    # what OptimizerMixin asks for
+    def _opt_target(self):
+        return (self._h if self.trainable else None), "rpn_det_head"
+
+    def _opt_entries(self):
+        return [(name, name, False, {"kernel": tuple(self.shapes[name]), "bias": (self.shapes[name][1],)}) for name in LAYERS]
+
+    def _opt_touch(self):
+        self._serial += 1
 
     @property
     def train_precision(self):
@@ -331,9 +358,9 @@ class DetectionHead(object):
         return "f16x3" if int(L.lib().rpn_det_head_train_precision(self._h)) == L.PRECISIONS["f16x3"] else "f32"
 
     def apply_gradients(self):
-        """one Adam step (one launch) from the gradients the last backward left"""
+        """one step of the compiled optimizer (Adam by default: one launch) from the gradients the last backward left"""
         self._serial += 1
-        L.check(L.lib().rpn_det_head_adam_step(self._h, *(self._opt + (L.stream_ptr(),))), "rpn_det_head_adam_step")
+        L.check(L.lib().rpn_det_head_adam_step(self._h, *(self._step_opt() + (L.stream_ptr(),))), "rpn_det_head_adam_step")
 
     def train_steps(self):
         return int(L.lib().rpn_det_head_steps(self._h))
