@@ -596,6 +596,51 @@ int rpn_model_roi_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, 
                        void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * RoI Align (no reference counterpart; the pooling operator of Mask R-CNN and of every Faster R-CNN since): every output bin is
+ * the average of s x s bilinear samples spread evenly over the bin, in pixel-centre coordinates.  The arithmetic is Detectron2's
+ * aligned=True form as this project restates it; torchvision is not a dependency and bit parity with torchvision.ops.roi_align
+ * is NOT pinned -- the pinned oracle is the float32 restatement of tests/test_roi_align_host.py.  Beside rpn_roi_pool, which keeps
+ * its bits.
+ *   d_x (B,H,W,C) NHWC float32, d_rois (B,R,4) normalised [y1,x1,y2,x2], d_out (B,R,ph,pw,C); RoI r of image b samples image b.
+ *   s = sampling_ratio, 1..4.  (extent_y, extent_x) = (Sy, Sx): the image's height and width measured in feature pixels, float32,
+ *   finite and > 0: (H, W) maps the box [0,1] onto the whole map; a stride-16 backbone on 500 pixels has exactly 500 / 16 = 31.25.
+ *   d_valid (B,) int32 or NULL: rows r >= valid[b] are written as zeros.
+ *   float32, every operation rounded on its own, in exactly this order (y axis; x likewise with x1, x2, Sx, pw, W):
+ *     start = y1 * Sy - 0.5;  end = y2 * Sy - 0.5;  bin = (end - start) / (float)ph;  step = bin / (float)s    (no clamp of the size)
+ *     sample k (0 <= k < s) of bin i:  y = (start + (float)i * bin) + ((float)k + 0.5) * step
+ *     ok = y >= -1 && y <= (float)H                                     (false for NaN)
+ *     if (y < 0) y = 0;  lo = (int)y;  if (lo >= H - 1) { lo = hi = H - 1; y = (float)lo; } else hi = lo + 1;
+ *     l = y - (float)lo;  h = 1 - l
+ *   sample (ky, kx) = ((hy*hx * x[lo_y,lo_x] + hy*lx * x[lo_y,hi_x]) + ly*hx * x[hi_y,lo_x]) + ly*lx * x[hi_y,hi_x]
+ *     (the four weights are rounded products, each term a rounded product, added left to right)
+ *   acc = +0;  for ky in 0..s-1, for kx in 0..s-1: if (ok_y(ky) && ok_x(kx)) acc = acc + sample(ky, kx);
+ *   out[b,r,i,j,c] = acc / (float)(s * s)                  (a sample that is not ok adds nothing, but still counts in s * s)
+ *   Unlike rpn_roi_pool the result is continuous in the box: for a box inside [0, 1] at the default extent every sample lies in
+ *   [-0.5, H - 0.5], a whole half pixel away from the ok thresholds -1 and H, so no rounding of a coordinate can switch a sample
+ *   off (there is no "last sample rounds past H - 1" case), and a coordinate that rounds across a pixel centre moves weight l ~ 0
+ *   from one neighbour to the other.
+ * rpn_roi_align_backward: d_dx (B,H,W,C) = the adjoint with respect to the feature map, applied to d_dy (B,R,ph,pw,C).  Writes
+ *   every element of d_dx.  A gather without floating-point atomics, bit-identical from run to run; image b's dx depends on image
+ *   b's RoIs, valid count and dy alone.  The weights are separable:
+ *     Ay(i, py) = +0, then for k in 0..s-1 with ok(k): Ay = Ay + w_k,  w_k = (lo == py ? h : 0) + (hi == py ? l : 0);  Ax(j, px) likewise
+ *     acc = +0;  for r < valid[b], i, j in that order, where Ay(i, py) != 0 and Ax(j, px) != 0:
+ *         acc[c] = acc[c] + dy[b,r,i,j,c] * (Ay(i, py) * Ax(j, px))
+ *     dx[b,py,px,c] = acc[c] / (float)(s * s)
+ *   There is no gradient with respect to the boxes.
+ * rpn_model_roi_align: rpn_roi_align of the feature tap where the handle's last forward left it -- float32, or the hi / lo 16-bit
+ *   split form under BF16X3 / F16X3, no float32 copy -- bit-identical to rpn_roi_align applied to rpn_model_get_activation of that
+ *   tap.  Ordered on `stream` like a forward; fails before the first forward and for B > max_batch.
+ * C % 4 == 0; pointers 16-byte aligned; B, R, ph, pw, H, W >= 1; RPN_ERR_INVALID for sampling_ratio outside 1..4 and for an extent
+ * that is not finite and > 0, before any device use.
+ * ---------------------------------------------------------------------------------- */
+int rpn_roi_align(const float *d_x, int B, int H, int W, int C, const float *d_rois, int R, int ph, int pw, int sampling_ratio,
+                  float extent_y, float extent_x, const int *d_valid, float *d_out, void *stream);
+int rpn_roi_align_backward(const float *d_dy, const float *d_rois, const int *d_valid, int B, int H, int W, int C, int R, int ph,
+                           int pw, int sampling_ratio, float extent_y, float extent_x, float *d_dx, void *stream);
+int rpn_model_roi_align(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, int sampling_ratio, float extent_y,
+                        float extent_x, const int *d_valid, float *d_out, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Second stage around RoI pooling: targets, losses, detections (no reference counterpart: the reference stops at the proposals;
  * thresholds and sampling rule are this project's choice).  The counterparts of rpn_rpn_targets / rpn_rpn_losses / rpn_decode_nms.
  * Everything on `stream`, no host synchronisation, no floating-point atomics: bit-identical from run to run.

@@ -6,10 +6,13 @@ round by round (median and minimum over the rounds):
       backward           rpn_roi_pool_backward
       torch gather       the same bilinear arithmetic written with torch advanced indexing, same device
       zero_ fill         torch.Tensor.zero_() on an output-sized tensor: the store-bound floor the forward is judged against
+      align s=N ...      rpn_roi_align / rpn_roi_align_backward at sampling ratio N = 1, 2 and the default extent (same boxes, same
+                         output bytes; 4 N^2 corner loads per store instead of 4)
     per backbone at precision f16x3, 500 x 500 images, after one forward (the tap as the graph leaves it in the arena):
       model pool         rpn_model_roi_pool (VGG16: the split hi / lo form; MobileNetV2's tap is float32 in every precision)
       tap copy           rpn_model_get_activation of the tap (VGG16: the split_to_f32 launch the split instantiation replaces)
       forward f32        rpn_roi_pool on that copy
+      align s=N model    rpn_model_roi_align (the split form where the tap is kept in it)
 
 Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
     python scripts/roi_pool_bench.py [--rounds 20] [--iters 20] [--json PATH]
@@ -28,6 +31,7 @@ from tf_rpn_amd import _lib as L  # noqa: E402
 from tf_rpn_amd.utils import roi_utils  # noqa: E402
 
 B, R, PH, PW = 8, 300, 7, 7
+ALIGN_S = (1, 2)            # RoI Align's sampling ratios timed beside the pool
 
 
 def torch_gather_pool(x, rois, ph, pw):
@@ -102,6 +106,11 @@ def main():
             "torch gather": lambda: torch_gather_pool(x, rois, PH, PW),
             "zero_ fill": lambda: fill.zero_(),
         }
+        for s in ALIGN_S:          # (s=s: each lambda keeps its own sampling ratio)
+            variants["align s=%d forward f32" % s] = lambda s=s: lib.rpn_roi_align(
+                L.ptr(x), B, H, W, C, L.ptr(rois), R, PH, PW, s, float(H), float(W), L.ptr(valid), L.ptr(out), stream)
+            variants["align s=%d backward" % s] = lambda s=s: lib.rpn_roi_align_backward(
+                L.ptr(dy), L.ptr(rois), L.ptr(valid), B, H, W, C, R, PH, PW, s, float(H), float(W), L.ptr(dx), stream)
         results[label] = dict(time_variants(variants, args.rounds, args.iters), out_bytes=out.numel() * 4)
         del x, out, dy, dx, fill, want
     from tf_rpn_amd.predictor import Proposer
@@ -121,15 +130,20 @@ def main():
             "tap copy": lambda: lib.rpn_model_get_activation(h, name, L.ptr(tap), tap.numel() * 4, None, stream),
             "forward f32": lambda: lib.rpn_roi_pool(L.ptr(tap), B, H, W, C, L.ptr(rois), R, PH, PW, L.ptr(valid), L.ptr(out), stream),
         }
+        for s in ALIGN_S:
+            assert torch.equal(fe.roi_align(rois, (PH, PW), s, valid=valid), roi_utils.roi_align(tap, rois, (PH, PW), s, valid=valid))
+            variants["align s=%d model" % s] = lambda s=s: lib.rpn_model_roi_align(
+                h, L.ptr(rois), B, R, PH, PW, s, float(H), float(W), L.ptr(valid), L.ptr(out), stream)
         results["%s f16x3 handle %dx%dx%d" % (backbone, H, W, C)] = dict(time_variants(variants, args.rounds, args.iters),
                                                                           out_bytes=out.numel() * 4)
         del prop, out, tap
-    print("%-36s %-14s %10s %10s %9s" % ("shape", "variant", "median us", "min us", "GB/s out"))
+    print("%-36s %-22s %10s %10s %9s" % ("shape", "variant", "median us", "min us", "GB/s out"))
     for label, row in results.items():
         for name, v in row.items():
             if name != "out_bytes":
-                rate = "%9.0f" % (row["out_bytes"] / v[0] / 1e3) if name in ("forward f32", "model pool", "zero_ fill", "torch gather") else ""
-                print("%-36s %-14s %10.1f %10.1f %s" % (label, name, v[0], v[1], rate))
+                writes_out = name in ("forward f32", "model pool", "zero_ fill", "torch gather") or name.endswith(("forward f32", "model"))
+                rate = "%9.0f" % (row["out_bytes"] / v[0] / 1e3) if writes_out else ""
+                print("%-36s %-22s %10.1f %10.1f %s" % (label, name, v[0], v[1], rate))
     line = json.dumps({"B": B, "R": R, "pool": [PH, PW], "rounds": args.rounds, "iters": args.iters, "us_median_min": results})
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)

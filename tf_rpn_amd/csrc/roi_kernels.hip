@@ -19,6 +19,12 @@
 //
 // Backward: dx = the adjoint of the forward (each sample adds dy times its four corner weights), as a GATHER -- no float atomics,
 // so two runs give the same bits, and image b's dx is a function of image b's rois, valid count and dy alone.
+//
+// RoI Align (roi_align_kernel, roi_align_backward_kernel, below the pooling kernels) is the second operator of this file: every
+// output bin is the average of s x s bilinear samples spread over the bin, in pixel-centre coordinates (Detectron2's aligned=True
+// form; include/rpn_hip.h states the arithmetic operation by operation).  Same layout, same launch shape, same rules: float32,
+// every operation rounded on its own, the backward a gather in (r, i, j) order.
+#include <cmath>
 #include <cstdint>
 
 #include "roi_kernels.h"
@@ -207,6 +213,186 @@ roi_pool_backward_kernel(const float *__restrict__ dy, const float *__restrict__
     if (active) *reinterpret_cast<float4 *>(dx + pix * C + c) = acc;
 }
 
+// ---- RoI Align ------------------------------------------------------------------------------------------------------------------
+// one axis of a box in feature pixels: first bin's start, bin size, distance between two samples of a bin
+struct RoiAlignAxis {
+    float start, bin, step;
+};
+
+__device__ __forceinline__ RoiAlignAxis roi_align_axis(float c1, float c2, float extent, int n, int s)
+{
+    const float start = c1 * extent - 0.5f, end = c2 * extent - 0.5f;
+    const float bin = (end - start) / (float)n;
+    return {start, bin, bin / (float)s};
+}
+
+// coordinate of sample k of bin i
+__device__ __forceinline__ float roi_align_coord(const RoiAlignAxis &a, int i, int k)
+{
+    return (a.start + (float)i * a.bin) + ((float)k + 0.5f) * a.step;
+}
+
+// the two pixels a sample at `y` reads along an axis of `size` pixels and the weight `l` of the second (the first has 1 - l);
+// false when the sample is further than one pixel outside (or NaN): it then contributes nothing
+__device__ __forceinline__ bool roi_align_corners(float y, int size, int *lo, int *hi, float *l)
+{
+    *lo = *hi = 0;
+    *l = 0.0f;
+    if (!(y >= -1.0f && y <= (float)size)) return false;
+    if (y < 0.0f) y = 0.0f;
+    int p = (int)y;
+    if (p >= size - 1) {
+        p = size - 1;
+        *hi = p;
+        y = (float)p;
+    } else {
+        *hi = p + 1;
+    }
+    *lo = p;
+    *l = y - (float)p;
+    return true;
+}
+
+// A(i, pos): the weight pixel `pos` of that axis has in bin i, summed over the bin's s samples in order
+__device__ __forceinline__ float roi_align_axis_weight(const RoiAlignAxis &a, int i, int s, int size, int pos)
+{
+    float sum = 0.0f;
+    for (int k = 0; k < s; ++k) {
+        int lo, hi;
+        float l;
+        if (!roi_align_corners(roi_align_coord(a, i, k), size, &lo, &hi, &l)) continue;
+        float w = 0.0f;
+        if (lo == pos) w = 1.0f - l;
+        if (hi == pos) w += l;
+        sum += w;
+    }
+    return sum;
+}
+
+constexpr int kRoiAlignMaxSamples = 4;   // sampling_ratio <= 4: the sample columns of a bin are kept in registers
+
+// Forward.  The launch shape of roi_pool_kernel: workgroup (roi, tile of kRoiSampleTile bins), a wave owns kRoiSamplesPerWave
+// consecutive bins, the lanes run over the channels, 16 bytes each, one float4 store per output.  The s x s samples of a bin are
+// accumulated in registers; a bin's s sample columns (pixels and weights) are computed once per bin, its sample rows once per
+// channel pass; all of that is wave-uniform.  4 s^2 corner loads per store.
+template <int SRC>
+__global__ void __launch_bounds__(64 * kRoiWaves)
+roi_align_kernel(const void *__restrict__ x, int H, int W, int C, const float *__restrict__ rois, int R, int ph, int pw, int s,
+                 float extent_y, float extent_x, const int *__restrict__ valid, float *__restrict__ out)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const long long roi = blockIdx.x;
+    const int b = (int)(roi / R), r = (int)(roi - (long long)b * R);
+    const int nbins = ph * pw;
+    const bool live = valid == nullptr || r < valid[b];
+    const float *box = rois + roi * 4;
+    const RoiAlignAxis ay = roi_align_axis(box[0], box[2], extent_y, ph, s), ax = roi_align_axis(box[1], box[3], extent_x, pw, s);
+    const float count = (float)(s * s);
+#pragma unroll
+    for (int k = 0; k < kRoiSamplesPerWave; ++k) {
+        const int q = (int)blockIdx.y * kRoiSampleTile + wave * kRoiSamplesPerWave + k;
+        if (q >= nbins) break;
+        const int i = q / pw, j = q - i * pw;
+        int xlo[kRoiAlignMaxSamples], xhi[kRoiAlignMaxSamples];
+        float lx[kRoiAlignMaxSamples];
+        bool okx[kRoiAlignMaxSamples];
+#pragma unroll
+        for (int kx = 0; kx < kRoiAlignMaxSamples; ++kx)
+            okx[kx] = roi_align_corners(roi_align_coord(ax, j, kx), W, &xlo[kx], &xhi[kx], &lx[kx]) && kx < s && live;
+        float *o = out + (roi * nbins + q) * C;
+        for (int c = lane * 4; c < C; c += kRoiChannelTile) {
+            float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            for (int ky = 0; ky < s; ++ky) {
+                int ylo, yhi;
+                float ly;
+                if (!roi_align_corners(roi_align_coord(ay, i, ky), H, &ylo, &yhi, &ly)) continue;
+                const float hy = 1.0f - ly;
+                const long long row_lo = ((long long)b * H + ylo) * W, row_hi = ((long long)b * H + yhi) * W;
+#pragma unroll
+                for (int kx = 0; kx < kRoiAlignMaxSamples; ++kx) {
+                    if (!okx[kx]) continue;
+                    const float hx = 1.0f - lx[kx];
+                    const float w1 = hy * hx, w2 = hy * lx[kx], w3 = ly * hx, w4 = ly * lx[kx];
+                    const float4 v1 = roi_load4<SRC>(x, row_lo + xlo[kx], C, c), v2 = roi_load4<SRC>(x, row_lo + xhi[kx], C, c);
+                    const float4 v3 = roi_load4<SRC>(x, row_hi + xlo[kx], C, c), v4 = roi_load4<SRC>(x, row_hi + xhi[kx], C, c);
+                    acc.x += ((w1 * v1.x + w2 * v2.x) + w3 * v3.x) + w4 * v4.x;
+                    acc.y += ((w1 * v1.y + w2 * v2.y) + w3 * v3.y) + w4 * v4.y;
+                    acc.z += ((w1 * v1.z + w2 * v2.z) + w3 * v3.z) + w4 * v4.z;
+                    acc.w += ((w1 * v1.w + w2 * v2.w) + w3 * v3.w) + w4 * v4.w;
+                }
+            }
+            *reinterpret_cast<float4 *>(o + c) = make_float4(acc.x / count, acc.y / count, acc.z / count, acc.w / count);
+        }
+    }
+}
+
+// Backward, the gather of roi_pool_backward_kernel with separable bin weights: one wave per (feature-map pixel, tile of
+// kRoiChannelTile channels).  The wave walks its image's RoIs in index order, 64 at a time: each lane tests ONE RoI (has any bin
+// row a weight on pixel row y, any bin column on pixel column x), the ballot lists the RoIs that do; for each of those, in order,
+// the lanes compute Ay(i, py) of the ph bin rows (one per lane) and Ax(j, px) of the pw bin columns, and the non-zero (i, j) pairs
+// are accumulated in (r, i, j) order: acc += dy * (Ay * Ax); dx = acc / (s * s).
+__global__ void __launch_bounds__(64)
+roi_align_backward_kernel(const float *__restrict__ dy, const float *__restrict__ rois, const int *__restrict__ valid, int H, int W,
+                          int C, int R, int ph, int pw, int s, float extent_y, float extent_x, int ctiles, float *__restrict__ dx)
+{
+    const int lane = threadIdx.x;
+    const long long pix = blockIdx.x / (unsigned)ctiles;
+    const int ct = (int)(blockIdx.x - (unsigned)pix * (unsigned)ctiles);
+    const int px = (int)(pix % W), py = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
+    const int c = ct * kRoiChannelTile + lane * 4;
+    const bool active = c < C;
+    int nr = R;
+    if (valid) nr = min(max(valid[b], 0), R);
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int r0 = 0; r0 < nr; r0 += 64) {
+        const int r = r0 + lane;
+        float4 box = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        bool hit = false;
+        if (r < nr) {
+            box = *reinterpret_cast<const float4 *>(rois + ((long long)b * R + r) * 4);
+            const RoiAlignAxis ay = roi_align_axis(box.x, box.z, extent_y, ph, s), ax = roi_align_axis(box.y, box.w, extent_x, pw, s);
+            bool hy = false, hx = false;
+            for (int i = 0; i < ph; ++i) hy = hy || roi_align_axis_weight(ay, i, s, H, py) != 0.0f;
+            if (hy)
+                for (int j = 0; j < pw; ++j) hx = hx || roi_align_axis_weight(ax, j, s, W, px) != 0.0f;
+            hit = hy && hx;
+        }
+        unsigned long long hits = __ballot(hit);
+        while (hits) {
+            const int k = __builtin_ctzll(hits);
+            hits &= hits - 1;
+            const RoiAlignAxis ay = roi_align_axis(roi_lane_value(box.x, k), roi_lane_value(box.z, k), extent_y, ph, s);
+            const RoiAlignAxis ax = roi_align_axis(roi_lane_value(box.y, k), roi_lane_value(box.w, k), extent_x, pw, s);
+            const long long roi = (long long)b * R + (r0 + k);
+            for (int i0 = 0; i0 < ph; i0 += 64) {
+                const float wy = i0 + lane < ph ? roi_align_axis_weight(ay, i0 + lane, s, H, py) : 0.0f;
+                unsigned long long rows = __ballot(wy != 0.0f);
+                while (rows) {
+                    const int li = __builtin_ctzll(rows);
+                    rows &= rows - 1;
+                    const float wyi = roi_lane_value(wy, li);
+                    const long long row = (roi * ph + (i0 + li)) * pw;
+                    for (int j0 = 0; j0 < pw; j0 += 64) {
+                        const float wx = j0 + lane < pw ? roi_align_axis_weight(ax, j0 + lane, s, W, px) : 0.0f;
+                        unsigned long long cols = __ballot(wx != 0.0f);
+                        while (cols) {
+                            const int lj = __builtin_ctzll(cols);
+                            cols &= cols - 1;
+                            const float w = wyi * roi_lane_value(wx, lj);
+                            if (active) {
+                                const float4 g = *reinterpret_cast<const float4 *>(dy + (row + (j0 + lj)) * C + c);
+                                acc.x += g.x * w; acc.y += g.y * w; acc.z += g.z * w; acc.w += g.w * w;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const float count = (float)(s * s);
+    if (active) *reinterpret_cast<float4 *>(dx + pix * C + c) = make_float4(acc.x / count, acc.y / count, acc.z / count, acc.w / count);
+}
+
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // the checks every entry shares; B R and B H W ctiles are grid dimensions, ph pw / kRoiSampleTile is one
@@ -243,6 +429,39 @@ int roi_pool_forward(const char *who, const void *d_x, int src, int B, int H, in
     return RPN_OK;
 }
 
+// sampling_ratio and extent: checked with the geometry, before any device use
+static int roi_align_check(const char *who, int s, float extent_y, float extent_x)
+{
+    RPN_REQUIRE(s >= 1 && s <= kRoiAlignMaxSamples, "%s: sampling_ratio %d outside [1, %d]", who, s, kRoiAlignMaxSamples);
+    RPN_REQUIRE(std::isfinite(extent_y) && std::isfinite(extent_x) && extent_y > 0.0f && extent_x > 0.0f,
+                "%s: the extent must be finite and > 0 (got %g x %g)", who, (double)extent_y, (double)extent_x);
+    return RPN_OK;
+}
+
+int roi_align_forward(const char *who, const void *d_x, int src, int B, int H, int W, int C, const float *d_rois, int R, int ph,
+                      int pw, int sampling_ratio, float extent_y, float extent_x, const int *d_valid, float *d_out, hipStream_t s)
+{
+    RPN_REQUIRE(d_x && d_rois && d_out, "%s: null pointer", who);
+    int st = roi_check(who, B, H, W, C, R, ph, pw);
+    if (st == RPN_OK) st = roi_align_check(who, sampling_ratio, extent_y, extent_x);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(src == ROI_SRC_F32 || C % 8 == 0, "%s: a split-form feature map needs C %% 8 == 0 (got %d)", who, C);
+    RPN_REQUIRE(aligned16(d_x) && aligned16(d_out), "%s: the feature map and the output must be 16-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const dim3 grid((unsigned)((long long)B * R), (unsigned)((ph * pw + kRoiSampleTile - 1) / kRoiSampleTile)), block(64 * kRoiWaves);
+    if (src == ROI_SRC_F32)
+        hipLaunchKernelGGL(roi_align_kernel<ROI_SRC_F32>, grid, block, 0, s, d_x, H, W, C, d_rois, R, ph, pw, sampling_ratio, extent_y,
+                           extent_x, d_valid, d_out);
+    else if (src == ROI_SRC_SPLIT_BF16)
+        hipLaunchKernelGGL(roi_align_kernel<ROI_SRC_SPLIT_BF16>, grid, block, 0, s, d_x, H, W, C, d_rois, R, ph, pw, sampling_ratio,
+                           extent_y, extent_x, d_valid, d_out);
+    else
+        hipLaunchKernelGGL(roi_align_kernel<ROI_SRC_SPLIT_F16>, grid, block, 0, s, d_x, H, W, C, d_rois, R, ph, pw, sampling_ratio,
+                           extent_y, extent_x, d_valid, d_out);
+    RPN_CHECK_LAUNCH();
+    return RPN_OK;
+}
+
 }  // namespace rpn
 
 using namespace rpn;
@@ -265,6 +484,30 @@ extern "C" int rpn_roi_pool_backward(const float *d_dy, const float *d_rois, con
     const int ctiles = (C + kRoiChannelTile - 1) / kRoiChannelTile;
     hipLaunchKernelGGL(roi_pool_backward_kernel, dim3((unsigned)((long long)B * H * W * ctiles)), dim3(64), 0, as_stream(stream), d_dy,
                        d_rois, d_valid, H, W, C, R, ph, pw, ctiles, d_dx);
+    RPN_CHECK_LAUNCH();
+    return RPN_OK;
+}
+
+extern "C" int rpn_roi_align(const float *d_x, int B, int H, int W, int C, const float *d_rois, int R, int ph, int pw,
+                             int sampling_ratio, float extent_y, float extent_x, const int *d_valid, float *d_out, void *stream)
+{
+    return roi_align_forward("rpn_roi_align", d_x, ROI_SRC_F32, B, H, W, C, d_rois, R, ph, pw, sampling_ratio, extent_y, extent_x,
+                             d_valid, d_out, as_stream(stream));
+}
+
+extern "C" int rpn_roi_align_backward(const float *d_dy, const float *d_rois, const int *d_valid, int B, int H, int W, int C, int R,
+                                      int ph, int pw, int sampling_ratio, float extent_y, float extent_x, float *d_dx, void *stream)
+{
+    const char *who = "rpn_roi_align_backward";
+    RPN_REQUIRE(d_dy && d_rois && d_dx, "%s: null pointer", who);
+    int st = roi_check(who, B, H, W, C, R, ph, pw);
+    if (st == RPN_OK) st = roi_align_check(who, sampling_ratio, extent_y, extent_x);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(aligned16(d_dy) && aligned16(d_dx) && aligned16(d_rois), "%s: dy, dx and rois must be 16-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const int ctiles = (C + kRoiChannelTile - 1) / kRoiChannelTile;
+    hipLaunchKernelGGL(roi_align_backward_kernel, dim3((unsigned)((long long)B * H * W * ctiles)), dim3(64), 0, as_stream(stream), d_dy,
+                       d_rois, d_valid, H, W, C, R, ph, pw, sampling_ratio, extent_y, extent_x, ctiles, d_dx);
     RPN_CHECK_LAUNCH();
     return RPN_OK;
 }

@@ -45,6 +45,13 @@ class FeatureExtractor(object):
             raise ValueError("roi_pool reads the model's feature tap %r, not %r" % (self._model.tap_layer, self.name))
         return self._model.roi_pool(rois, pooling_size, valid, out)
 
+    def roi_align(self, rois, pooling_size=(7, 7), sampling_ratio=2, extent=None, valid=None, out=None):
+        """RoI Align of this layer's output as the model's last forward left it (``roi_utils.roi_align`` states the operator):
+        read straight from the arena like ``roi_pool``, bit-identical to ``roi_utils.roi_align(self.output()[:B], ...)``."""
+        if self.name != self._model.tap_layer:
+            raise ValueError("roi_align reads the model's feature tap %r, not %r" % (self._model.tap_layer, self.name))
+        return self._model.roi_align(rois, pooling_size, sampling_ratio, extent, valid, out)
+
 
 # the layers a training step updates (models/rpn_vgg16.py:18-20, models/rpn_mobilenet_v2.py:18-20)
 HEAD_LAYERS = ("rpn_conv", "rpn_cls", "rpn_reg")
@@ -345,6 +352,24 @@ class RPNModel(O.OptimizerMixin):
     def roi_pool(self, rois, pooling_size=(7, 7), valid=None, out=None):
         """``FeatureExtractor.roi_pool``: rpn_model_roi_pool of the tap layer after a forward.  ``out``: a preallocated contiguous
         CUDA float32 (B, R, ph, pw, C) tensor to fill (no allocation, as ``forward_into``)."""
+        rois, valid, out, (B, R, ph, pw) = self._roi_args(rois, pooling_size, valid, out)
+        L.check(L.lib().rpn_model_roi_pool(self._h, L.ptr(rois), B, R, ph, pw, L.ptr(valid), L.ptr(out), L.stream_ptr()),
+                "rpn_model_roi_pool")
+        return out
+
+    def roi_align(self, rois, pooling_size=(7, 7), sampling_ratio=2, extent=None, valid=None, out=None):
+        """``FeatureExtractor.roi_align``: rpn_model_roi_align of the tap layer after a forward; ``extent`` defaults to the tap's
+        (H, W).  ``out`` as in ``roi_pool``."""
+        from ..utils import roi_utils
+        s = roi_utils._sampling_ratio(sampling_ratio)
+        sy, sx = roi_utils._extent(extent, *self.activation_shape(self.tap_layer)[1:3])
+        rois, valid, out, (B, R, ph, pw) = self._roi_args(rois, pooling_size, valid, out)
+        L.check(L.lib().rpn_model_roi_align(self._h, L.ptr(rois), B, R, ph, pw, s, sy, sx, L.ptr(valid), L.ptr(out), L.stream_ptr()),
+                "rpn_model_roi_align")
+        return out
+
+    def _roi_args(self, rois, pooling_size, valid, out):
+        """the argument checks ``roi_pool`` and ``roi_align`` share -> (rois, valid, out (allocated when None), (B, R, ph, pw))"""
         ph, pw = (int(v) for v in pooling_size)
         C = self.activation_shape(self.tap_layer)[3]
         for t, dtype, what in ((rois, torch.float32, "rois"), (valid, torch.int32, "valid")):
@@ -361,9 +386,7 @@ class RPNModel(O.OptimizerMixin):
         elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
                   and tuple(out.shape) == shape):
             raise ValueError("out must be a contiguous CUDA float32 tensor of shape %s" % (shape,))
-        L.check(L.lib().rpn_model_roi_pool(self._h, L.ptr(rois), B, R, ph, pw, L.ptr(valid), L.ptr(out), L.stream_ptr()),
-                "rpn_model_roi_pool")
-        return out
+        return rois, valid, out, (B, R, ph, pw)
 
     # ---- training of the head (trainer.py:54-69) ----------------------------------------------------------------------------
     def compile(self, learning_rate=1e-5, beta_1=0.9, beta_2=0.999, epsilon=1e-7, trainable=HEAD_LAYERS, train_backbone_from=None,

@@ -194,12 +194,17 @@ class Proposer(object):
         # before trusting the proposals of weights that may leave the float16 range)
         return ob, osc, ov, oi
 
-    def propose_features(self, imgs, pooling_size=(7, 7)):
+    def propose_features(self, imgs, pooling_size=(7, 7), pooling="crop", sampling_ratio=2, extent=None):
         """imgs -> (boxes (B,300,4), scores (B,300), valid (B,) int32, pooled (B,300,ph,pw,C)): the proposals of ``propose`` and the
         feature tap pooled under them (``FeatureExtractor.roi_pool``; rows beyond ``valid`` are zeros) -- what a Faster R-CNN
         detection head consumes.  Forward, decode + NMS and the pool run in that order on the current stream, without a host
         synchronisation.  Always the non-overlapped sequence, also with ``overlap_nms=True`` (the pipelined ``propose_async`` is
-        not involved).  ``pooled`` is a buffer of this object, overwritten by the next call with the same pooling size."""
+        not involved).  ``pooled`` is a buffer of this object, overwritten by the next call with the same pooling size.
+
+        ``pooling="crop"`` (default) is ``crop_and_resize``, one sample per cell; ``pooling="align"`` is RoI Align
+        (``FeatureExtractor.roi_align`` with ``sampling_ratio`` and ``extent``, which "crop" ignores).  Both modes share the buffer."""
+        if pooling not in ("crop", "align"):
+            raise ValueError("pooling must be \"crop\" or \"align\", got %r" % (pooling,))
         B = self._check_imgs(imgs)
         ph, pw = (int(v) for v in pooling_size)
         deltas, scores = self.forward(imgs)
@@ -209,15 +214,20 @@ class Proposer(object):
         if (ph, pw) not in bufs:
             C = self.feature_extractor.output_shape[3]
             bufs[(ph, pw)] = torch.empty((self.max_batch, self.topn, ph, pw, C), dtype=torch.float32, device="cuda")
-        pooled = self.feature_extractor.roi_pool(ob, (ph, pw), valid=ov, out=bufs[(ph, pw)][:B])
+        if pooling == "align":
+            pooled = self.feature_extractor.roi_align(ob, (ph, pw), sampling_ratio, extent, valid=ov, out=bufs[(ph, pw)][:B])
+        else:
+            pooled = self.feature_extractor.roi_pool(ob, (ph, pw), valid=ov, out=bufs[(ph, pw)][:B])
         return ob, osc, ov, pooled
 
-    def detect(self, imgs, head, **nms_kwargs):
+    def detect(self, imgs, head, pooling="crop", sampling_ratio=2, extent=None, **nms_kwargs):
         """imgs -> (boxes (B,M,4) clipped to [0, 1], scores (B,M), classes (B,M), valid_detections (B,) int32), M =
         ``max_total_size`` (300 unless given): ``propose_features`` at the head's pooling size, then ``head.detect`` (a
         ``models.DetectionHead``: its layers, ``roi_utils.roi_detections``) with this model's variances.  Everything on the current
-        stream, no host synchronisation in between.  ``nms_kwargs`` go to ``roi_detections``."""
-        rois, _scores, valid, pooled = self.propose_features(imgs, pooling_size=head.pooling_size)
+        stream, no host synchronisation in between.  ``pooling``, ``sampling_ratio`` and ``extent`` go to ``propose_features``
+        (a head detects with the pooling it was trained on), ``nms_kwargs`` to ``roi_detections``."""
+        rois, _scores, valid, pooled = self.propose_features(imgs, pooling_size=head.pooling_size, pooling=pooling,
+                                                             sampling_ratio=sampling_ratio, extent=extent)
         return head.detect(rois, pooled, self.hyper_params["variances"], valid=valid, **nms_kwargs)
 
     def propose_async(self, imgs):

@@ -10,7 +10,13 @@ with ``box_indices`` fixed to "RoI r of image b samples image b" (the shape ``Pr
 
     roi_pooling(feature_map, rois, pooling_size=(7, 7), valid=None)   -> rpn_roi_pool (+ rpn_roi_pool_backward under autograd)
 
-and, around it, what a second stage trains on and how its outputs become detections (the counterparts of the RPN's
+beside it RoI Align, the pooling of Mask R-CNN and later Faster R-CNNs (each bin the average of s x s bilinear samples, pixel-centre
+coordinates: every feature pixel under a box is read, whatever the size of the box):
+
+    roi_align(feature_map, rois, pooling_size=(7, 7), sampling_ratio=2, extent=None, valid=None)
+                                                                      -> rpn_roi_align (+ rpn_roi_align_backward under autograd)
+
+and, around them, what a second stage trains on and how its outputs become detections (the counterparts of the RPN's
 ``calculate_rpn_actual_outputs`` / ``reg_loss`` + ``cls_loss`` / ``decode_and_nms``; thresholds and sampling rule are this project's
 choice):
 
@@ -108,6 +114,98 @@ def roi_pooling(feature_map, rois, pooling_size=(7, 7), valid=None):
     if needs_grad:
         return _RoIPooling.apply(x, r, v, ph, pw)
     return L.from_device(_forward(x.detach(), r, v, ph, pw), was_np)
+
+
+# ---- RoI Align ------------------------------------------------------------------------------------------------------------------
+def _sampling_ratio(sampling_ratio):
+    s = int(sampling_ratio)
+    if s != sampling_ratio or not 1 <= s <= 4:
+        raise ValueError("sampling_ratio must be an integer in 1..4 (the adaptive form, <= 0, is not implemented), got %r"
+                         % (sampling_ratio,))
+    return s
+
+
+def _extent(extent, H, W):
+    """(Sy, Sx): the image's size in feature pixels; None -> (H, W)"""
+    sy, sx = (float(H), float(W)) if extent is None else (float(v) for v in extent)
+    if not (np.isfinite(sy) and np.isfinite(sx) and sy > 0.0 and sx > 0.0):
+        raise ValueError("extent must be two finite positive numbers, got %r" % (extent,))
+    return sy, sx
+
+
+def _align_forward(x, rois, valid, ph, pw, s, sy, sx):
+    B, H, W, C = (int(v) for v in x.shape)
+    R = int(rois.shape[1])
+    out = torch.empty((B, R, ph, pw, C), dtype=torch.float32, device="cuda")
+    st = L.lib().rpn_roi_align(L.ptr(x), B, H, W, C, L.ptr(rois), R, ph, pw, s, sy, sx, L.ptr(valid), L.ptr(out), L.stream_ptr())
+    L.check(st, "roi_align")
+    return out
+
+
+def roi_align_backward(grad_out, rois, feature_shape, sampling_ratio=2, extent=None, valid=None):
+    """Gradient of ``roi_align`` with respect to the feature map: ``grad_out`` (B, R, ph, pw, C) -> (B, H, W, C), the exact adjoint
+    of the forward (``rpn_roi_align_backward``).  A gather without floating-point atomics: the same bits on every run, and image b's
+    gradient depends on image b's RoIs alone.  There is no gradient with respect to the boxes."""
+    s = _sampling_ratio(sampling_ratio)
+    B, H, W, C = (int(v) for v in feature_shape)
+    sy, sx = _extent(extent, H, W)
+    g, was_np = L.to_device(grad_out)
+    r, _ = L.to_device(rois)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+    if g.dim() != 5 or int(g.shape[0]) != B or int(g.shape[4]) != C:
+        raise ValueError("grad_out must be (%d, R, ph, pw, %d), got %s" % (B, C, tuple(g.shape)))
+    if tuple(r.shape) != (B, int(g.shape[1]), 4):
+        raise ValueError("rois must be (%d, %d, 4), got %s" % (B, int(g.shape[1]), tuple(r.shape)))
+    if v is not None and tuple(v.shape) != (B,):
+        raise ValueError("valid must be (%d,) int32, got %s" % (B, tuple(v.shape)))
+    dx = torch.empty((B, H, W, C), dtype=torch.float32, device="cuda")
+    st = L.lib().rpn_roi_align_backward(L.ptr(g), L.ptr(r), L.ptr(v), B, H, W, C, int(g.shape[1]), int(g.shape[2]), int(g.shape[3]),
+                                        s, sy, sx, L.ptr(dx), L.stream_ptr())
+    L.check(st, "roi_align_backward")
+    return L.from_device(dx, was_np)
+
+
+class _RoIAlign(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rois, valid, ph, pw, s, sy, sx):
+        ctx.save_for_backward(rois, valid if valid is not None else torch.empty(0))
+        ctx.has_valid = valid is not None
+        ctx.feature_shape = tuple(x.shape)
+        ctx.sampling = (s, (sy, sx))
+        return _align_forward(x, rois, valid, ph, pw, s, sy, sx)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rois, valid = ctx.saved_tensors
+        s, extent = ctx.sampling
+        dx = roi_align_backward(grad_out.contiguous(), rois, ctx.feature_shape, s, extent, valid if ctx.has_valid else None)
+        return dx, None, None, None, None, None, None, None
+
+
+def roi_align(feature_map, rois, pooling_size=(7, 7), sampling_ratio=2, extent=None, valid=None):
+    """RoI Align: feature_map (B, H, W, C) NHWC, rois (B, R, [y1, x1, y2, x2]) normalised -> (B, R, ph, pw, C), every bin the
+    average of ``sampling_ratio`` x ``sampling_ratio`` bilinear samples spread over the bin, in pixel-centre coordinates
+    (``rpn_roi_align``; Detectron2's ``aligned=True`` arithmetic, stated in ``include/rpn_hip.h``).
+
+    ``sampling_ratio``: 1..4.  ``extent`` (Sy, Sx): the image's height and width in feature pixels, default (H, W); the
+    stride-exact value of a stride-16 backbone on 500 pixels is (500 / 16, 500 / 16).  ``valid`` (B,) int32, optional: rows
+    ``r >= valid[b]`` come back as zeros.
+
+    A CUDA ``feature_map`` that requires grad gets its gradient through ``rpn_roi_align_backward``; ``rois`` and ``valid`` get none."""
+    ph, pw = _pool_size(pooling_size)
+    s = _sampling_ratio(sampling_ratio)
+    shape = tuple(int(v) for v in (feature_map.shape if hasattr(feature_map, "shape") else np.shape(feature_map)))
+    if len(shape) != 4:
+        raise ValueError("feature_map must be (B, H, W, C) NHWC, got %s" % (shape,))
+    sy, sx = _extent(extent, shape[1], shape[2])
+    needs_grad = isinstance(feature_map, torch.Tensor) and feature_map.requires_grad and torch.is_grad_enabled()
+    x, was_np = L.to_device(feature_map)
+    r, _ = L.to_device(rois.detach() if isinstance(rois, torch.Tensor) else rois)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+    _check(x, r, v)
+    if needs_grad:
+        return _RoIAlign.apply(x, r, v, ph, pw, s, sy, sx)
+    return L.from_device(_align_forward(x.detach(), r, v, ph, pw, s, sy, sx), was_np)
 
 
 # ---- second stage: targets, losses, detections ------------------------------------------------------------------------------
