@@ -641,6 +641,50 @@ int rpn_model_roi_align(rpn_model *m, const float *d_rois, int B, int R, int ph,
                         float extent_x, const int *d_valid, float *d_out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * RoI max pooling (no reference counterpart; Fast R-CNN's RoIPool, the pooling of the VGG16 Faster R-CNN recipe): every output bin
+ * is the MAXIMUM over a quantised block of feature pixels.  The arithmetic is Caffe's ROIPooling / torchvision.ops.roi_pool on this
+ * project's normalised boxes; neither is a dependency and parity with them is NOT pinned -- where they differ from each other or
+ * from this text, this text is the contract, and the pinned oracle is its restatement in tests/test_roi_max_host.py.  Beside
+ * rpn_roi_pool and rpn_roi_align, which keep their bits.
+ *   d_x (B,H,W,C) NHWC float32, d_rois (B,R,4) normalised [y1,x1,y2,x2], d_out (B,R,ph,pw,C) float32, d_argmax (B,R,ph,pw,C) int32
+ *   or NULL (then it is not written: inference); RoI r of image b pools image b.  d_valid (B,) int32 or NULL.
+ *   (extent_y, extent_x) = (Sy, Sx): the box scale in feature pixels, float32, finite and > 0.  (H - 1, W - 1) makes the box
+ *   [0,0,1,1] exactly the pixels 0 .. H - 1, the convention of rpn_roi_pool (and NOT rpn_roi_align's (H, W), which measures
+ *   pixel cells, not pixel centres); a stride-16 backbone on 500 pixels has exactly 500 / 16 = 31.25.
+ *   float32, every operation rounded on its own, per axis (y shown; x likewise with x1, x2, Sx, pw, W):
+ *     a = y1 * Sy;  e = y2 * Sy.  If any of the box's four products is NaN the RoI is DEAD.  Otherwise each product is clamped to
+ *     [-2^20, 2^20];  p1 = (int)roundf(a);  p2 = (int)roundf(e)   (half away from zero);  n = max(p2 - p1 + 1, 1)  (a flipped or
+ *     zero-size box is one pixel wide);  bin = (float)n / (float)ph
+ *     bin i covers the pixel rows [hs, he):  hs = min(max((int)floorf((float)i * bin) + p1, 0), H)
+ *                                            he = min(max((int)ceilf((float)(i + 1) * bin) + p1, 0), H)
+ *   A bin with he <= hs or we <= ws is EMPTY: its output is +0.0 in every channel and its argmax -1.  A non-empty bin scans its
+ *   pixels in (row, column) order: m = the first pixel's value, idx = its y * W + x; a later pixel v replaces them iff
+ *   v > m || v != v  (torch.max_pool2d's rule: the first maximum wins a tie, a NaN in the bin reaches the output).
+ *   out = m, a bit-exact copy of an input value (the sign of zero kept); argmax = idx.
+ *   Rows r >= valid[b] and dead RoIs: every output +0.0, every argmax -1.
+ *   So: an all-negative bin gives its negative maximum, not 0; an all -inf bin gives -inf; on a post-ReLU map most ties are
+ *   between zeros and the bin's first pixel wins them; bins overlap (he(i) can exceed hs(i + 1)), and when the RoI is smaller than
+ *   the grid (n < ph) one pixel lies in several bins of the same RoI.
+ * rpn_roi_max_pool_backward: d_dx[b,y,x,c] = the sum of d_dy[b,r,i,j,c] over the (r, i, j) with d_argmax[b,r,i,j,c] == y * W + x,
+ *   accumulated in float32 in (r, i, j) order from +0.0, r < valid[b], dead RoIs skipped.  Writes every element of d_dx.  A gather
+ *   without floating-point atomics, bit-identical from run to run; image b's dx depends on image b's RoIs, valid count, argmax
+ *   and dy alone.  d_argmax must be what the forward wrote for these boxes, extent and valid (the bins a pixel can lie in are
+ *   recomputed from the boxes; an argmax entry is only ever compared, never used as an address).  No gradient with respect to
+ *   the boxes.
+ * rpn_model_roi_max_pool: rpn_roi_max_pool of the feature tap where the handle's last forward left it -- float32, or the hi / lo
+ *   16-bit split form under BF16X3 / F16X3, no float32 copy -- bit-identical to rpn_roi_max_pool applied to
+ *   rpn_model_get_activation of that tap.  Ordered on `stream` like a forward; fails before the first forward and for B > max_batch.
+ * C % 4 == 0; pointers 16-byte aligned; B, R, ph, pw, H, W >= 1; RPN_ERR_INVALID for an extent that is not finite and > 0, before
+ * any device use.
+ * ---------------------------------------------------------------------------------- */
+int rpn_roi_max_pool(const float *d_x, int B, int H, int W, int C, const float *d_rois, int R, int ph, int pw, float extent_y,
+                     float extent_x, const int *d_valid, float *d_out, int32_t *d_argmax /* may be NULL */, void *stream);
+int rpn_roi_max_pool_backward(const float *d_dy, const int32_t *d_argmax, const float *d_rois, const int *d_valid, int B, int H, int W,
+                              int C, int R, int ph, int pw, float extent_y, float extent_x, float *d_dx, void *stream);
+int rpn_model_roi_max_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, float extent_y, float extent_x,
+                           const int *d_valid, float *d_out, int32_t *d_argmax, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Second stage around RoI pooling: targets, losses, detections (no reference counterpart: the reference stops at the proposals;
  * thresholds and sampling rule are this project's choice).  The counterparts of rpn_rpn_targets / rpn_rpn_losses / rpn_decode_nms.
  * Everything on `stream`, no host synchronisation, no floating-point atomics: bit-identical from run to run.

@@ -8,11 +8,18 @@ round by round (median and minimum over the rounds):
       zero_ fill         torch.Tensor.zero_() on an output-sized tensor: the store-bound floor the forward is judged against
       align s=N ...      rpn_roi_align / rpn_roi_align_backward at sampling ratio N = 1, 2 and the default extent (same boxes, same
                          output bytes; 4 N^2 corner loads per store instead of 4)
+      max forward f32    rpn_roi_max_pool without the argmax (inference: the same output bytes; a bin of a large box reads
+                         about 20 pixels per store where the bilinear pool reads 4), at the default extent (H - 1, W - 1)
+      max forward+argmax the same with the int32 argmax stored beside it (training: twice the bytes written)
+      max backward       rpn_roi_max_pool_backward with that argmax
+      crop14 + max2x2    rpn_roi_pool at 14 x 14 followed by torch.nn.functional.max_pool2d(2): what a user had to do for
+                         max-pooled RoI features before (writes and re-reads a 4x larger intermediate)
     per backbone at precision f16x3, 500 x 500 images, after one forward (the tap as the graph leaves it in the arena):
       model pool         rpn_model_roi_pool (VGG16: the split hi / lo form; MobileNetV2's tap is float32 in every precision)
       tap copy           rpn_model_get_activation of the tap (VGG16: the split_to_f32 launch the split instantiation replaces)
       forward f32        rpn_roi_pool on that copy
       align s=N model    rpn_model_roi_align (the split form where the tap is kept in it)
+      max model          rpn_model_roi_max_pool, no argmax
 
 Prints one table and, last, one JSON line.  Needs a GPU (there is no CPU path).
     python scripts/roi_pool_bench.py [--rounds 20] [--iters 20] [--json PATH]
@@ -111,8 +118,27 @@ def main():
                 L.ptr(x), B, H, W, C, L.ptr(rois), R, PH, PW, s, float(H), float(W), L.ptr(valid), L.ptr(out), stream)
             variants["align s=%d backward" % s] = lambda s=s: lib.rpn_roi_align_backward(
                 L.ptr(dy), L.ptr(rois), L.ptr(valid), B, H, W, C, R, PH, PW, s, float(H), float(W), L.ptr(dx), stream)
+        argmax = torch.empty((B, R, PH, PW, C), dtype=torch.int32, device="cuda")
+        out14 = torch.empty((B, R, 2 * PH, 2 * PW, C), dtype=torch.float32, device="cuda")
+        nchw14 = out14.view(B * R, 2 * PH, 2 * PW, C).permute(0, 3, 1, 2)           # (a channels-last view: no copy)
+        ey, ex = float(H - 1), float(W - 1)
+
+        def crop14_then_max():
+            lib.rpn_roi_pool(L.ptr(x), B, H, W, C, L.ptr(rois), R, 2 * PH, 2 * PW, L.ptr(valid), L.ptr(out14), stream)
+            return torch.nn.functional.max_pool2d(nchw14, 2)
+
+        L.check(lib.rpn_roi_max_pool(L.ptr(x), B, H, W, C, L.ptr(rois), R, PH, PW, ey, ex, L.ptr(valid), L.ptr(out), L.ptr(argmax),
+                                     stream), "rpn_roi_max_pool")
+        assert tuple(crop14_then_max().shape) == (B * R, C, PH, PW) and int(argmax.min()) >= 0
+        variants["max forward f32"] = lambda: lib.rpn_roi_max_pool(
+            L.ptr(x), B, H, W, C, L.ptr(rois), R, PH, PW, ey, ex, L.ptr(valid), L.ptr(out), None, stream)
+        variants["max forward+argmax"] = lambda: lib.rpn_roi_max_pool(
+            L.ptr(x), B, H, W, C, L.ptr(rois), R, PH, PW, ey, ex, L.ptr(valid), L.ptr(out), L.ptr(argmax), stream)
+        variants["max backward"] = lambda: lib.rpn_roi_max_pool_backward(
+            L.ptr(dy), L.ptr(argmax), L.ptr(rois), L.ptr(valid), B, H, W, C, R, PH, PW, ey, ex, L.ptr(dx), stream)
+        variants["crop14 + max2x2"] = crop14_then_max
         results[label] = dict(time_variants(variants, args.rounds, args.iters), out_bytes=out.numel() * 4)
-        del x, out, dy, dx, fill, want
+        del x, out, dy, dx, fill, want, argmax, out14, nchw14
     from tf_rpn_amd.predictor import Proposer
     for backbone in ("vgg16", "mobilenet_v2"):
         prop = Proposer(backbone, precision="f16x3", max_batch=B)
@@ -134,6 +160,9 @@ def main():
             assert torch.equal(fe.roi_align(rois, (PH, PW), s, valid=valid), roi_utils.roi_align(tap, rois, (PH, PW), s, valid=valid))
             variants["align s=%d model" % s] = lambda s=s: lib.rpn_model_roi_align(
                 h, L.ptr(rois), B, R, PH, PW, s, float(H), float(W), L.ptr(valid), L.ptr(out), stream)
+        assert torch.equal(fe.roi_max_pool(rois, (PH, PW), valid=valid), roi_utils.roi_max_pooling(tap, rois, (PH, PW), valid=valid))
+        variants["max model"] = lambda: lib.rpn_model_roi_max_pool(
+            h, L.ptr(rois), B, R, PH, PW, float(H - 1), float(W - 1), L.ptr(valid), L.ptr(out), None, stream)
         results["%s f16x3 handle %dx%dx%d" % (backbone, H, W, C)] = dict(time_variants(variants, args.rounds, args.iters),
                                                                           out_bytes=out.numel() * 4)
         del prop, out, tap
@@ -141,7 +170,7 @@ def main():
     for label, row in results.items():
         for name, v in row.items():
             if name != "out_bytes":
-                writes_out = name in ("forward f32", "model pool", "zero_ fill", "torch gather") or name.endswith(("forward f32", "model"))
+                writes_out = name in ("forward f32", "model pool", "zero_ fill", "torch gather") or name.endswith(("forward f32", "model", "+argmax"))
                 rate = "%9.0f" % (row["out_bytes"] / v[0] / 1e3) if writes_out else ""
                 print("%-36s %-22s %10.1f %10.1f %s" % (label, name, v[0], v[1], rate))
     line = json.dumps({"B": B, "R": R, "pool": [PH, PW], "rounds": args.rounds, "iters": args.iters, "us_median_min": results})

@@ -134,6 +134,9 @@ _SIGNATURES = {
     "rpn_roi_align": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [vp, vp, vp]),
     "rpn_roi_align_backward": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 8 + [ctypes.c_float] * 2 + [vp, vp]),
     "rpn_model_roi_align": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_float] * 2 + [vp, vp, vp]),
+    "rpn_roi_max_pool": (ctypes.c_int, [vp] + [ctypes.c_int] * 4 + [vp] + [ctypes.c_int] * 3 + [ctypes.c_float] * 2 + [vp, vp, vp, vp]),
+    "rpn_roi_max_pool_backward": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 7 + [ctypes.c_float] * 2 + [vp, vp]),
+    "rpn_model_roi_max_pool": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 2 + [vp, vp, vp, vp]),
     "rpn_roi_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "rpn_roi_targets": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_float] * 3 + [c_float_p, vp, vp, vp, vp, vp,
                                                                                                        ctypes.c_size_t, vp]),

@@ -1545,6 +1545,21 @@ extern "C" int rpn_model_roi_align(rpn_model *m, const float *d_rois, int B, int
                              pw, sampling_ratio, extent_y, extent_x, d_valid, d_out, as_stream(stream));
 }
 
+// RoI max pooling of the feature tap, read from the arena the same way (roi_max_pool_kernel<SRC>): the failure rules of
+// rpn_model_roi_pool; d_argmax may be null
+extern "C" int rpn_model_roi_max_pool(rpn_model *m, const float *d_rois, int B, int R, int ph, int pw, float extent_y, float extent_x,
+                                      const int *d_valid, float *d_out, int32_t *d_argmax, void *stream)
+{
+    RPN_REQUIRE(m && d_rois && d_out, "rpn_model_roi_max_pool: null argument");
+    RPN_REQUIRE(B >= 1 && B <= m->max_batch, "rpn_model_roi_max_pool: batch %d outside [1, %d]", B, m->max_batch);
+    RPN_REQUIRE(R >= 1 && ph >= 1 && pw >= 1, "rpn_model_roi_max_pool: R and the pooling size must be >= 1 (got %d, %d x %d)", R, ph, pw);
+    RPN_REQUIRE(m->d_arena && m->feat_written, "rpn_model_roi_max_pool: no forward pass has run");
+    const Tensor &t = m->tensors[m->feat_tensor];
+    const int src = !t.split_fmt ? ROI_SRC_F32 : (m->f16 ? ROI_SRC_SPLIT_F16 : ROI_SRC_SPLIT_BF16);
+    return roi_max_pool_forward("rpn_model_roi_max_pool", m->d_arena + t.offset * (size_t)m->max_batch, src, B, t.H, t.W, t.C, d_rois, R,
+                                ph, pw, extent_y, extent_x, d_valid, d_out, d_argmax, as_stream(stream));
+}
+
 // ---- single-layer entry points (kernel-level parity tests, micro-benchmarks) -----------------
 extern "C" int rpn_conv2d(const float *d_x, int B, int H, int W, int Cin, const float *d_w, const float *d_bias,
                           int R, int S, int Cout, int stride, int pad_t, int pad_l, int OH, int OW, int act,

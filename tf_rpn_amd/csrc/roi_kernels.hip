@@ -24,6 +24,10 @@
 // output bin is the average of s x s bilinear samples spread over the bin, in pixel-centre coordinates (Detectron2's aligned=True
 // form; include/rpn_hip.h states the arithmetic operation by operation).  Same layout, same launch shape, same rules: float32,
 // every operation rounded on its own, the backward a gather in (r, i, j) order.
+//
+// RoI max pooling (roi_max_pool_kernel, roi_max_pool_backward_kernel) is the third: Fast R-CNN's RoIPool, every output bin the
+// maximum over a quantised block of feature pixels, with the pixel it came from kept as an argmax for the backward, which is
+// again a gather in (r, i, j) order.  include/rpn_hip.h states the quantisation operation by operation.
 #include <cmath>
 #include <cstdint>
 
@@ -393,6 +397,174 @@ roi_align_backward_kernel(const float *__restrict__ dy, const float *__restrict_
     if (active) *reinterpret_cast<float4 *>(dx + pix * C + c) = make_float4(acc.x / count, acc.y / count, acc.z / count, acc.w / count);
 }
 
+// ---- RoI max pooling ------------------------------------------------------------------------------------------------------------
+// one axis of a box in whole feature pixels: first pixel and bin size (include/rpn_hip.h states the arithmetic)
+struct RoiMaxAxis {
+    int p1;
+    float bin;
+};
+
+constexpr float kRoiMaxClamp = 1048576.0f;   // 2^20: the products are clamped here before they are rounded to int
+
+// false when a product is NaN (the RoI is dead)
+__device__ __forceinline__ bool roi_max_axis(float c1, float c2, float extent, int n, RoiMaxAxis *a)
+{
+    float s = c1 * extent, e = c2 * extent;
+    const bool ok = s == s && e == e;
+    s = fminf(fmaxf(s, -kRoiMaxClamp), kRoiMaxClamp);
+    e = fminf(fmaxf(e, -kRoiMaxClamp), kRoiMaxClamp);
+    const int p1 = ok ? (int)roundf(s) : 0, p2 = ok ? (int)roundf(e) : 0;
+    a->p1 = p1;
+    a->bin = (float)max(p2 - p1 + 1, 1) / (float)n;
+    return ok;
+}
+
+// pixels [*lo, *hi) of bin i along an axis of `size` pixels; empty when *hi <= *lo
+__device__ __forceinline__ void roi_max_bin(const RoiMaxAxis &a, int i, int size, int *lo, int *hi)
+{
+    *lo = min(max((int)floorf((float)i * a.bin) + a.p1, 0), size);
+    *hi = min(max((int)ceilf((float)(i + 1) * a.bin) + a.p1, 0), size);
+}
+
+__device__ __forceinline__ void roi_max_take(float v, int p, float *m, int *idx)
+{
+    if (v > *m || v != v) {
+        *m = v;
+        *idx = p;
+    }
+}
+
+// Forward.  The launch shape of roi_pool_kernel: workgroup (roi, tile of kRoiSampleTile bins), a wave owns kRoiSamplesPerWave
+// consecutive bins, the lanes run over the channels, 16 bytes each: one float4 store of the maximum per pass and, when `argmax`
+// is not null, one int4 store of the pixel y W + x it was taken from.  A bin's limits are wave-uniform and computed once per
+// bin; its pixels are scanned in (row, column) order, the first maximum wins and a NaN is taken (torch.max_pool2d's rule).
+// (he - hs)(we - ws) pixel loads per store: about 20 for a box that covers the 31 x 31 map at 7 x 7.
+template <int SRC>
+__global__ void __launch_bounds__(64 * kRoiWaves)
+roi_max_pool_kernel(const void *__restrict__ x, int H, int W, int C, const float *__restrict__ rois, int R, int ph, int pw,
+                    float extent_y, float extent_x, const int *__restrict__ valid, float *__restrict__ out, int *__restrict__ argmax)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const long long roi = blockIdx.x;
+    const int b = (int)(roi / R), r = (int)(roi - (long long)b * R);
+    const int nbins = ph * pw;
+    const float *box = rois + roi * 4;
+    RoiMaxAxis ay, ax;
+    const bool oky = roi_max_axis(box[0], box[2], extent_y, ph, &ay), okx = roi_max_axis(box[1], box[3], extent_x, pw, &ax);
+    const bool live = (valid == nullptr || r < valid[b]) && oky && okx;
+    const long long image = (long long)b * H * W;
+#pragma unroll
+    for (int k = 0; k < kRoiSamplesPerWave; ++k) {
+        const int q = (int)blockIdx.y * kRoiSampleTile + wave * kRoiSamplesPerWave + k;
+        if (q >= nbins) break;
+        const int i = q / pw, j = q - i * pw;
+        int hs, he, ws, we;
+        roi_max_bin(ay, i, H, &hs, &he);
+        roi_max_bin(ax, j, W, &ws, &we);
+        const bool ok = live && he > hs && we > ws;
+        const long long o = (roi * nbins + q) * C;
+        for (int c = lane * 4; c < C; c += kRoiChannelTile) {
+            float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            int4 idx = make_int4(-1, -1, -1, -1);
+            if (ok) {
+                const int first = hs * W + ws;
+                m = roi_load4<SRC>(x, image + first, C, c);
+                idx = make_int4(first, first, first, first);
+                for (int y = hs; y < he; ++y)
+                    for (int xx = y == hs ? ws + 1 : ws; xx < we; ++xx) {
+                        const int p = y * W + xx;
+                        const float4 v = roi_load4<SRC>(x, image + p, C, c);
+                        roi_max_take(v.x, p, &m.x, &idx.x);
+                        roi_max_take(v.y, p, &m.y, &idx.y);
+                        roi_max_take(v.z, p, &m.z, &idx.z);
+                        roi_max_take(v.w, p, &m.w, &idx.w);
+                    }
+            }
+            *reinterpret_cast<float4 *>(out + o + c) = m;
+            if (argmax) *reinterpret_cast<int4 *>(argmax + o + c) = idx;
+        }
+    }
+}
+
+// Backward, the gather of roi_pool_backward_kernel: one wave per (feature-map pixel, tile of kRoiChannelTile channels).  The wave
+// walks its image's RoIs in index order, 64 at a time: each lane tests ONE RoI (live, and the pixel inside the pixels its bins
+// cover, [hs(0), he(ph - 1)) x [ws(0), we(pw - 1))), the ballot lists the RoIs that pass; for each of those, in order, the lanes
+// test the ph bin rows (one per lane) and the pw bin columns for containing the pixel -- bins overlap, so up to two per axis do
+// when bin >= 1 and up to all of them otherwise -- and for each (i, j), in order, the lanes load argmax and dy of their four
+// channels and add dy where the argmax is this pixel.  What is added is decided per channel, the order is fixed.
+__global__ void __launch_bounds__(64)
+roi_max_pool_backward_kernel(const float *__restrict__ dy, const int *__restrict__ argmax, const float *__restrict__ rois,
+                             const int *__restrict__ valid, int H, int W, int C, int R, int ph, int pw, float extent_y, float extent_x,
+                             int ctiles, float *__restrict__ dx)
+{
+    const int lane = threadIdx.x;
+    const long long pix = blockIdx.x / (unsigned)ctiles;
+    const int ct = (int)(blockIdx.x - (unsigned)pix * (unsigned)ctiles);
+    const int px = (int)(pix % W), py = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
+    const int p = py * W + px;
+    const int c = ct * kRoiChannelTile + lane * 4;
+    const bool active = c < C;
+    int nr = R;
+    if (valid) nr = min(max(valid[b], 0), R);
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int r0 = 0; r0 < nr; r0 += 64) {
+        const int r = r0 + lane;
+        float4 box = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        bool hit = false;
+        if (r < nr) {
+            box = *reinterpret_cast<const float4 *>(rois + ((long long)b * R + r) * 4);
+            RoiMaxAxis ay, ax;
+            if (roi_max_axis(box.x, box.z, extent_y, ph, &ay) && roi_max_axis(box.y, box.w, extent_x, pw, &ax)) {
+                int lo, hi, unused;
+                roi_max_bin(ay, 0, H, &lo, &unused);
+                roi_max_bin(ay, ph - 1, H, &unused, &hi);
+                hit = py >= lo && py < hi;
+                roi_max_bin(ax, 0, W, &lo, &unused);
+                roi_max_bin(ax, pw - 1, W, &unused, &hi);
+                hit = hit && px >= lo && px < hi;
+            }
+        }
+        unsigned long long hits = __ballot(hit);
+        while (hits) {
+            const int k = __builtin_ctzll(hits);
+            hits &= hits - 1;
+            RoiMaxAxis ay, ax;
+            roi_max_axis(roi_lane_value(box.x, k), roi_lane_value(box.z, k), extent_y, ph, &ay);
+            roi_max_axis(roi_lane_value(box.y, k), roi_lane_value(box.w, k), extent_x, pw, &ax);
+            const long long roi = (long long)b * R + (r0 + k);
+            for (int i0 = 0; i0 < ph; i0 += 64) {
+                int lo = 0, hi = 0;
+                if (i0 + lane < ph) roi_max_bin(ay, i0 + lane, H, &lo, &hi);
+                unsigned long long rows = __ballot(py >= lo && py < hi);
+                while (rows) {
+                    const int li = __builtin_ctzll(rows);
+                    rows &= rows - 1;
+                    const long long row = (roi * ph + (i0 + li)) * pw;
+                    for (int j0 = 0; j0 < pw; j0 += 64) {
+                        lo = hi = 0;
+                        if (j0 + lane < pw) roi_max_bin(ax, j0 + lane, W, &lo, &hi);
+                        unsigned long long cols = __ballot(px >= lo && px < hi);
+                        while (cols) {
+                            const int lj = __builtin_ctzll(cols);
+                            cols &= cols - 1;
+                            if (active) {
+                                const long long at = (row + (j0 + lj)) * C + c;
+                                const int4 a = *reinterpret_cast<const int4 *>(argmax + at);
+                                const float4 g = *reinterpret_cast<const float4 *>(dy + at);
+                                if (a.x == p) acc.x += g.x;
+                                if (a.y == p) acc.y += g.y;
+                                if (a.z == p) acc.z += g.z;
+                                if (a.w == p) acc.w += g.w;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (active) *reinterpret_cast<float4 *>(dx + pix * C + c) = acc;
+}
+
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // the checks every entry shares; B R and B H W ctiles are grid dimensions, ph pw / kRoiSampleTile is one
@@ -462,6 +634,38 @@ int roi_align_forward(const char *who, const void *d_x, int src, int B, int H, i
     return RPN_OK;
 }
 
+static int roi_extent_check(const char *who, float extent_y, float extent_x)
+{
+    RPN_REQUIRE(std::isfinite(extent_y) && std::isfinite(extent_x) && extent_y > 0.0f && extent_x > 0.0f,
+                "%s: the extent must be finite and > 0 (got %g x %g)", who, (double)extent_y, (double)extent_x);
+    return RPN_OK;
+}
+
+int roi_max_pool_forward(const char *who, const void *d_x, int src, int B, int H, int W, int C, const float *d_rois, int R, int ph,
+                         int pw, float extent_y, float extent_x, const int *d_valid, float *d_out, int32_t *d_argmax, hipStream_t s)
+{
+    RPN_REQUIRE(d_x && d_rois && d_out, "%s: null pointer", who);
+    int st = roi_check(who, B, H, W, C, R, ph, pw);
+    if (st == RPN_OK) st = roi_extent_check(who, extent_y, extent_x);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(src == ROI_SRC_F32 || C % 8 == 0, "%s: a split-form feature map needs C %% 8 == 0 (got %d)", who, C);
+    RPN_REQUIRE(aligned16(d_x) && aligned16(d_out) && aligned16(d_argmax),
+                "%s: the feature map, the output and the argmax must be 16-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const dim3 grid((unsigned)((long long)B * R), (unsigned)((ph * pw + kRoiSampleTile - 1) / kRoiSampleTile)), block(64 * kRoiWaves);
+    if (src == ROI_SRC_F32)
+        hipLaunchKernelGGL(roi_max_pool_kernel<ROI_SRC_F32>, grid, block, 0, s, d_x, H, W, C, d_rois, R, ph, pw, extent_y, extent_x,
+                           d_valid, d_out, d_argmax);
+    else if (src == ROI_SRC_SPLIT_BF16)
+        hipLaunchKernelGGL(roi_max_pool_kernel<ROI_SRC_SPLIT_BF16>, grid, block, 0, s, d_x, H, W, C, d_rois, R, ph, pw, extent_y,
+                           extent_x, d_valid, d_out, d_argmax);
+    else
+        hipLaunchKernelGGL(roi_max_pool_kernel<ROI_SRC_SPLIT_F16>, grid, block, 0, s, d_x, H, W, C, d_rois, R, ph, pw, extent_y,
+                           extent_x, d_valid, d_out, d_argmax);
+    RPN_CHECK_LAUNCH();
+    return RPN_OK;
+}
+
 }  // namespace rpn
 
 using namespace rpn;
@@ -508,6 +712,32 @@ extern "C" int rpn_roi_align_backward(const float *d_dy, const float *d_rois, co
     const int ctiles = (C + kRoiChannelTile - 1) / kRoiChannelTile;
     hipLaunchKernelGGL(roi_align_backward_kernel, dim3((unsigned)((long long)B * H * W * ctiles)), dim3(64), 0, as_stream(stream), d_dy,
                        d_rois, d_valid, H, W, C, R, ph, pw, sampling_ratio, extent_y, extent_x, ctiles, d_dx);
+    RPN_CHECK_LAUNCH();
+    return RPN_OK;
+}
+
+extern "C" int rpn_roi_max_pool(const float *d_x, int B, int H, int W, int C, const float *d_rois, int R, int ph, int pw,
+                                float extent_y, float extent_x, const int *d_valid, float *d_out, int32_t *d_argmax, void *stream)
+{
+    return roi_max_pool_forward("rpn_roi_max_pool", d_x, ROI_SRC_F32, B, H, W, C, d_rois, R, ph, pw, extent_y, extent_x, d_valid, d_out,
+                                d_argmax, as_stream(stream));
+}
+
+extern "C" int rpn_roi_max_pool_backward(const float *d_dy, const int32_t *d_argmax, const float *d_rois, const int *d_valid, int B,
+                                         int H, int W, int C, int R, int ph, int pw, float extent_y, float extent_x, float *d_dx,
+                                         void *stream)
+{
+    const char *who = "rpn_roi_max_pool_backward";
+    RPN_REQUIRE(d_dy && d_argmax && d_rois && d_dx, "%s: null pointer", who);
+    int st = roi_check(who, B, H, W, C, R, ph, pw);
+    if (st == RPN_OK) st = roi_extent_check(who, extent_y, extent_x);
+    if (st != RPN_OK) return st;
+    RPN_REQUIRE(aligned16(d_dy) && aligned16(d_argmax) && aligned16(d_dx) && aligned16(d_rois),
+                "%s: dy, argmax, dx and rois must be 16-byte aligned", who);
+    RPN_REQUIRE_DEVICE();
+    const int ctiles = (C + kRoiChannelTile - 1) / kRoiChannelTile;
+    hipLaunchKernelGGL(roi_max_pool_backward_kernel, dim3((unsigned)((long long)B * H * W * ctiles)), dim3(64), 0, as_stream(stream),
+                       d_dy, d_argmax, d_rois, d_valid, H, W, C, R, ph, pw, extent_y, extent_x, ctiles, d_dx);
     RPN_CHECK_LAUNCH();
     return RPN_OK;
 }

@@ -52,6 +52,14 @@ class FeatureExtractor(object):
             raise ValueError("roi_align reads the model's feature tap %r, not %r" % (self._model.tap_layer, self.name))
         return self._model.roi_align(rois, pooling_size, sampling_ratio, extent, valid, out)
 
+    def roi_max_pool(self, rois, pooling_size=(7, 7), extent=None, valid=None, out=None):
+        """RoI max pooling of this layer's output as the model's last forward left it (``roi_utils.roi_max_pooling`` states the
+        operator): read straight from the arena like ``roi_pool``, bit-identical to
+        ``roi_utils.roi_max_pooling(self.output()[:B], ...)``.  No argmax is written (inference)."""
+        if self.name != self._model.tap_layer:
+            raise ValueError("roi_max_pool reads the model's feature tap %r, not %r" % (self._model.tap_layer, self.name))
+        return self._model.roi_max_pool(rois, pooling_size, extent, valid, out)
+
 
 # the layers a training step updates (models/rpn_vgg16.py:18-20, models/rpn_mobilenet_v2.py:18-20)
 HEAD_LAYERS = ("rpn_conv", "rpn_cls", "rpn_reg")
@@ -368,8 +376,18 @@ class RPNModel(O.OptimizerMixin):
                 "rpn_model_roi_align")
         return out
 
+    def roi_max_pool(self, rois, pooling_size=(7, 7), extent=None, valid=None, out=None):
+        """``FeatureExtractor.roi_max_pool``: rpn_model_roi_max_pool of the tap layer after a forward, without an argmax; ``extent``
+        defaults to the tap's (H - 1, W - 1).  ``out`` as in ``roi_pool``."""
+        from ..utils import roi_utils
+        sy, sx = roi_utils._max_extent(extent, *self.activation_shape(self.tap_layer)[1:3])
+        rois, valid, out, (B, R, ph, pw) = self._roi_args(rois, pooling_size, valid, out)
+        L.check(L.lib().rpn_model_roi_max_pool(self._h, L.ptr(rois), B, R, ph, pw, sy, sx, L.ptr(valid), L.ptr(out), None,
+                                               L.stream_ptr()), "rpn_model_roi_max_pool")
+        return out
+
     def _roi_args(self, rois, pooling_size, valid, out):
-        """the argument checks ``roi_pool`` and ``roi_align`` share -> (rois, valid, out (allocated when None), (B, R, ph, pw))"""
+        """the argument checks ``roi_pool``, ``roi_align`` and ``roi_max_pool`` share -> (rois, valid, out (allocated when None), (B, R, ph, pw))"""
         ph, pw = (int(v) for v in pooling_size)
         C = self.activation_shape(self.tap_layer)[3]
         for t, dtype, what in ((rois, torch.float32, "rois"), (valid, torch.int32, "valid")):

@@ -278,6 +278,34 @@ class DetectionHead(O.OptimizerMixin):
                 weights.setdefault(layer, {})[param] = data[key]
         return self.set_weights(weights, partial=bool(by_name))
 
+    def load_keras_weights(self, path, layers=("fc1", "fc2")):
+        """Start the hidden layers from a Keras VGG16 ``.h5`` (a weights file or a full model): reads the layer groups ``layers``
+        with ``h5_weights.read_keras_weights`` and sets them (``set_weights(..., partial=True)``: ``cls`` / ``reg`` and the layers
+        not named keep their values).  Returns the names set.  No transpose is needed: the head's flatten index
+        ``(i * pw + j) * channels + c`` is Keras' ``Flatten`` of an NHWC tensor, so at the default shape ``fc1`` / ``fc2`` are
+        exactly ``block5_pool -> flatten -> fc1 -> fc2`` -- layers trained on MAX-pooled ``block5_conv3`` features
+        (``roi_utils.roi_max_pooling``).  ``ValueError``: a layer that is not ``fc1`` / ``fc2``, that the file does not hold, or
+        whose kernel is not the head's ``(ph * pw * channels, H1)`` / ``(H1, H2)``."""
+        from ..utils import h5_weights
+        layers = tuple(layers)
+        for name in layers:
+            if name not in ("fc1", "fc2"):
+                raise ValueError("load_keras_weights: %r is not a hidden layer of the head (fc1, fc2)" % (name,))
+        weights, _info = h5_weights.read_keras_weights(path)
+        chosen = {}
+        for name in layers:
+            layer = weights.get(name)
+            if not layer or "kernel" not in layer or "bias" not in layer:
+                raise ValueError("load_keras_weights: the file holds no layer %r with a kernel and a bias (its layers: %s)"
+                                 % (name, ", ".join(weights)))
+            kernel, bias = np.asarray(layer["kernel"]), np.asarray(layer["bias"])
+            want = tuple(self.shapes[name])
+            if tuple(kernel.shape) != want or tuple(bias.shape) != (want[1],):
+                raise ValueError("load_keras_weights: layer %r has kernel %s / bias %s in the file, the head's is %s / (%d,)"
+                                 % (name, tuple(kernel.shape), tuple(bias.shape), want, want[1]))
+            chosen[name] = {"kernel": kernel, "bias": bias}
+        return self.set_weights(chosen, partial=True)
+
     # ---- forward / backward -------------------------------------------------------------
     def _forward(self, pooled, keep):
         B, R = int(pooled.shape[0]), int(pooled.shape[1])

@@ -202,9 +202,12 @@ class Proposer(object):
         not involved).  ``pooled`` is a buffer of this object, overwritten by the next call with the same pooling size.
 
         ``pooling="crop"`` (default) is ``crop_and_resize``, one sample per cell; ``pooling="align"`` is RoI Align
-        (``FeatureExtractor.roi_align`` with ``sampling_ratio`` and ``extent``, which "crop" ignores).  Both modes share the buffer."""
-        if pooling not in ("crop", "align"):
-            raise ValueError("pooling must be \"crop\" or \"align\", got %r" % (pooling,))
+        (``FeatureExtractor.roi_align`` with ``sampling_ratio`` and ``extent``, which "crop" ignores); ``pooling="max_pool"`` is
+        RoI max pooling, Fast R-CNN's RoIPool (``FeatureExtractor.roi_max_pool`` with ``extent``, whose default there is the tap's
+        (H - 1, W - 1); ``sampling_ratio`` is ignored; no argmax is written).  The modes share the buffer.  Any other name,
+        ``"max"`` among them, is refused."""
+        if pooling not in ("crop", "align", "max_pool"):
+            raise ValueError("pooling must be \"crop\", \"align\" or \"max_pool\", got %r" % (pooling,))
         B = self._check_imgs(imgs)
         ph, pw = (int(v) for v in pooling_size)
         deltas, scores = self.forward(imgs)
@@ -216,6 +219,8 @@ class Proposer(object):
             bufs[(ph, pw)] = torch.empty((self.max_batch, self.topn, ph, pw, C), dtype=torch.float32, device="cuda")
         if pooling == "align":
             pooled = self.feature_extractor.roi_align(ob, (ph, pw), sampling_ratio, extent, valid=ov, out=bufs[(ph, pw)][:B])
+        elif pooling == "max_pool":
+            pooled = self.feature_extractor.roi_max_pool(ob, (ph, pw), extent, valid=ov, out=bufs[(ph, pw)][:B])
         else:
             pooled = self.feature_extractor.roi_pool(ob, (ph, pw), valid=ov, out=bufs[(ph, pw)][:B])
         return ob, osc, ov, pooled

@@ -16,6 +16,12 @@ coordinates: every feature pixel under a box is read, whatever the size of the b
     roi_align(feature_map, rois, pooling_size=(7, 7), sampling_ratio=2, extent=None, valid=None)
                                                                       -> rpn_roi_align (+ rpn_roi_align_backward under autograd)
 
+and RoI max pooling, Fast R-CNN's RoIPool and the pooling of the VGG16 Faster R-CNN recipe (each bin the maximum over a quantised
+block of feature pixels; what ImageNet's ``fc1`` / ``fc2`` were trained behind):
+
+    roi_max_pooling(feature_map, rois, pooling_size=(7, 7), extent=None, valid=None, return_argmax=False)
+                                                                      -> rpn_roi_max_pool (+ rpn_roi_max_pool_backward under autograd)
+
 and, around them, what a second stage trains on and how its outputs become detections (the counterparts of the RPN's
 ``calculate_rpn_actual_outputs`` / ``reg_loss`` + ``cls_loss`` / ``decode_and_nms``; thresholds and sampling rule are this project's
 choice):
@@ -206,6 +212,109 @@ def roi_align(feature_map, rois, pooling_size=(7, 7), sampling_ratio=2, extent=N
     if needs_grad:
         return _RoIAlign.apply(x, r, v, ph, pw, s, sy, sx)
     return L.from_device(_align_forward(x.detach(), r, v, ph, pw, s, sy, sx), was_np)
+
+
+# ---- RoI max pooling ----------------------------------------------------------------------------------------------------------
+def _max_extent(extent, H, W):
+    """(Sy, Sx): the box scale in feature pixels; None -> (H - 1, W - 1), the box [0, 1] is exactly the pixels 0 .. H - 1 (an axis
+    of one pixel takes 1: the scale must be > 0, and every box that reaches the axis then pools that pixel)"""
+    return _extent((max(int(H) - 1, 1), max(int(W) - 1, 1)) if extent is None else extent, H, W)
+
+
+def _max_forward(x, rois, valid, ph, pw, sy, sx, want_argmax):
+    B, H, W, C = (int(v) for v in x.shape)
+    R = int(rois.shape[1])
+    out = torch.empty((B, R, ph, pw, C), dtype=torch.float32, device="cuda")
+    argmax = torch.empty((B, R, ph, pw, C), dtype=torch.int32, device="cuda") if want_argmax else None
+    st = L.lib().rpn_roi_max_pool(L.ptr(x), B, H, W, C, L.ptr(rois), R, ph, pw, sy, sx, L.ptr(valid), L.ptr(out), L.ptr(argmax),
+                                  L.stream_ptr())
+    L.check(st, "roi_max_pooling")
+    return out, argmax
+
+
+def roi_max_pooling_backward(grad_out, argmax, rois, feature_shape, extent=None, valid=None):
+    """Gradient of ``roi_max_pooling`` with respect to the feature map: ``grad_out`` (B, R, ph, pw, C) and the forward's ``argmax``
+    (same shape, int32) -> (B, H, W, C): every pixel gets the sum of the ``grad_out`` of the bins that chose it, added in float32
+    in (r, i, j) order (``rpn_roi_max_pool_backward``).  A gather without floating-point atomics: the same bits on every run, and
+    image b's gradient depends on image b alone.  ``rois``, ``extent`` and ``valid`` must be the forward's.  There is no gradient
+    with respect to the boxes."""
+    B, H, W, C = (int(v) for v in feature_shape)
+    sy, sx = _max_extent(extent, H, W)
+    gs, as_ = _shape(grad_out), _shape(argmax)
+    if len(gs) != 5 or gs[0] != B or gs[4] != C:
+        raise ValueError("grad_out must be (%d, R, ph, pw, %d), got %s" % (B, C, gs))
+    if str(getattr(argmax, "dtype", None)).split(".")[-1] != "int32":
+        raise ValueError("argmax must be int32, got %s" % (getattr(argmax, "dtype", type(argmax)),))
+    if as_ != gs:
+        raise ValueError("argmax must be %s int32 like grad_out, got %s" % (gs, as_))
+    if _shape(rois) != (B, gs[1], 4):
+        raise ValueError("rois must be (%d, %d, 4), got %s" % (B, gs[1], _shape(rois)))
+    if valid is not None and _shape(valid) != (B,):
+        raise ValueError("valid must be (%d,) int32, got %s" % (B, _shape(valid)))
+    if C < 4 or C % 4:
+        raise ValueError("the channel count must be a positive multiple of 4, got %d" % C)
+    g, was_np = L.to_device(grad_out)
+    a = L.to_device(argmax, dtype=torch.int32)[0]
+    r, _ = L.to_device(rois)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+    dx = torch.empty((B, H, W, C), dtype=torch.float32, device="cuda")
+    st = L.lib().rpn_roi_max_pool_backward(L.ptr(g), L.ptr(a), L.ptr(r), L.ptr(v), B, H, W, C, int(g.shape[1]), int(g.shape[2]),
+                                           int(g.shape[3]), sy, sx, L.ptr(dx), L.stream_ptr())
+    L.check(st, "roi_max_pooling_backward")
+    return L.from_device(dx, was_np)
+
+
+class _RoIMaxPooling(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rois, valid, ph, pw, sy, sx):
+        out, argmax = _max_forward(x, rois, valid, ph, pw, sy, sx, True)
+        ctx.save_for_backward(rois, valid if valid is not None else torch.empty(0), argmax)
+        ctx.has_valid = valid is not None
+        ctx.feature_shape = tuple(x.shape)
+        ctx.extent = (sy, sx)
+        ctx.mark_non_differentiable(argmax)
+        return out, argmax
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_argmax):
+        rois, valid, argmax = ctx.saved_tensors
+        dx = roi_max_pooling_backward(grad_out.contiguous(), argmax, rois, ctx.feature_shape, ctx.extent,
+                                      valid if ctx.has_valid else None)
+        return dx, None, None, None, None, None, None
+
+
+def roi_max_pooling(feature_map, rois, pooling_size=(7, 7), extent=None, valid=None, return_argmax=False):
+    """RoI max pooling (Fast R-CNN's RoIPool): feature_map (B, H, W, C) NHWC, rois (B, R, [y1, x1, y2, x2]) normalised ->
+    (B, R, ph, pw, C), every bin the maximum over a quantised block of feature pixels (``rpn_roi_max_pool``; Caffe's
+    ``ROIPooling`` arithmetic, stated in ``include/rpn_hip.h``).  The first maximum of a bin wins a tie, a NaN in a bin reaches the
+    output, an empty bin is 0.
+
+    ``extent`` (Sy, Sx): the box scale in feature pixels, default (H - 1, W - 1) -- the box [0, 0, 1, 1] is exactly the whole map,
+    as in ``roi_pooling``; the stride-exact value of a stride-16 backbone on 500 pixels is (500 / 16, 500 / 16).  ``valid`` (B,)
+    int32, optional: rows ``r >= valid[b]`` come back as zeros.  ``return_argmax``: also return the int32 tensor of the pixel
+    ``y * W + x`` every output was taken from (-1 for empty bins and dead rows), which ``roi_max_pooling_backward`` takes.
+
+    A CUDA ``feature_map`` that requires grad gets its gradient through ``rpn_roi_max_pool_backward`` (the forward then keeps the
+    argmax); otherwise no argmax is allocated unless asked for.  ``rois`` and ``valid`` get no gradient."""
+    ph, pw = _pool_size(pooling_size)
+    shape = tuple(int(v) for v in (feature_map.shape if hasattr(feature_map, "shape") else np.shape(feature_map)))
+    if len(shape) != 4:
+        raise ValueError("feature_map must be (B, H, W, C) NHWC, got %s" % (shape,))
+    if shape[3] < 4 or shape[3] % 4:
+        raise ValueError("the channel count must be a positive multiple of 4, got %d" % shape[3])
+    sy, sx = _max_extent(extent, shape[1], shape[2])
+    needs_grad = isinstance(feature_map, torch.Tensor) and feature_map.requires_grad and torch.is_grad_enabled()
+    x, was_np = L.to_device(feature_map)
+    r, _ = L.to_device(rois.detach() if isinstance(rois, torch.Tensor) else rois)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+    _check(x, r, v)
+    if needs_grad:
+        out, argmax = _RoIMaxPooling.apply(x, r, v, ph, pw, sy, sx)
+    else:
+        out, argmax = _max_forward(x.detach(), r, v, ph, pw, sy, sx, bool(return_argmax))
+        out = L.from_device(out, was_np)
+        argmax = L.from_device(argmax, was_np) if argmax is not None else None
+    return (out, argmax) if return_argmax else out
 
 
 # ---- second stage: targets, losses, detections ------------------------------------------------------------------------------
