@@ -704,6 +704,30 @@ int rpn_model_roi_max_pool(rpn_model *m, const float *d_rois, int B, int R, int 
  *   B, R, G >= 1, G <= 2048, 0 <= neg_lo <= neg_hi, pos_iou >= 0; d_workspace: rpn_roi_targets_workspace_bytes(B, R, G) bytes.
  *   One launch, one workgroup per image; the (B,R,G) IoU map is never written.
  *
+ * rpn_roi_sample_targets: the proposal-target layer: rpn_roi_targets' assignment over the proposals PLUS the gt boxes, and only the
+ * sampled RoIs handed on, as a dense (B,S) batch that the pools, the detection head and rpn_roi_losses take as it is.
+ *   d_rois, d_valid, d_gt_boxes, d_gt_labels, variances, the counts and the thresholds: as rpn_roi_targets takes them.  add_gt: 0 or
+ *   not 0.  N = add_gt ? R + G : R.  d_random_pos / d_random_neg (B,N) int32 >= 1.  S must equal total_pos + total_neg and be >= 1.
+ *   Candidates of image b: candidate i < R is RoI i, live iff i < clamp(valid[b], 0, R); candidate R + g is gt box g, live iff add_gt
+ *   and gt_labels[b,g] >= 1.  A candidate that is not live is never selected.
+ *   Per live candidate, in float32 with every operation rounded on its own (generate_iou_map):
+ *     best = 0, arg = none; for valid gt g in index order: iou = IoU(box, gt[g]); if (iou > best) { best = iou; arg = g; }
+ *   (strict: the first maximum wins, a NaN never wins).  A gt candidate meets itself at IoU exactly 1 unless it is degenerate: a
+ *   zero-area or NaN box has IoU 0 or NaN with everything, itself included.
+ *   Positive candidates: live, best > pos_iou; the total_pos of highest random_pos priority are kept, ties to the lower candidate
+ *   index.  Negative candidates: live, not kept as positives, neg_lo <= best < neg_hi; total_pos + total_neg - n_pos of them are kept
+ *   by random_neg the same way.  With add_gt == 0 the kept sets are rpn_roi_targets' for the same priorities.
+ *   Output rows of image b, in this order: the kept positives in ascending candidate index, the kept negatives in ascending
+ *   candidate index, then padding up to S.
+ *     d_out_rois (B,S,4): the candidate's box, a bit-exact copy; d_out_labels (B,S) int32: the matched gt's label, 0 for a negative;
+ *     d_out_deltas (B,S,4): encode(box, gt[arg]) / variances for a positive, exactly +0.0 for a negative;
+ *     d_out_index (B,S) int32: the candidate index (>= R: gt box index - R); d_out_counts (B,2) int32: [n_sampled, n_pos].
+ *     Padding rows s >= n_sampled: box and deltas +0.0, label -1, index -1.  Every element of all five is written on every call.
+ *   n_sampled is what rpn_roi_pool / rpn_roi_align / rpn_roi_max_pool / rpn_roi_decode_scores take as d_valid.
+ *   B, R >= 1, 1 <= G <= 2048, thresholds as above; d_workspace: rpn_roi_sample_targets_workspace_bytes(B, R, G, add_gt) bytes.
+ *   One launch, one workgroup per image; the row of a kept candidate comes from an ordered workgroup scan: no atomics on global
+ *   memory, no memset, the IoU map is never written.  d_out_rois and d_out_deltas 16-byte aligned.
+ *
  * rpn_roi_losses: the detection head's two losses and, optionally, their gradients.
  *   d_cls_logits (B,R,C) LOGITS (not probabilities); d_reg_pred (B,R,4C) class-specific boxes; d_roi_labels (B,R) int32;
  *   d_roi_deltas (B,R,4).  A row whose label is outside [0, C) is ignored by both losses and never indexes memory.
@@ -728,6 +752,12 @@ int rpn_roi_targets(const float *d_rois, const int32_t *d_valid, const float *d_
                     int G, int total_pos, int total_neg, float pos_iou, float neg_lo, float neg_hi, const float *variances,
                     const int32_t *d_random_pos, const int32_t *d_random_neg, float *d_roi_deltas, int32_t *d_roi_labels,
                     void *d_workspace, size_t workspace_bytes, void *stream);
+size_t rpn_roi_sample_targets_workspace_bytes(int B, int R, int G, int add_gt);
+int rpn_roi_sample_targets(const float *d_rois, const int32_t *d_valid, const float *d_gt_boxes, const int32_t *d_gt_labels, int B,
+                           int R, int G, int add_gt, int total_pos, int total_neg, float pos_iou, float neg_lo, float neg_hi,
+                           const float *variances, const int32_t *d_random_pos, const int32_t *d_random_neg, int S,
+                           float *d_out_rois, int32_t *d_out_labels, float *d_out_deltas, int32_t *d_out_index,
+                           int32_t *d_out_counts, void *d_workspace, size_t workspace_bytes, void *stream);
 size_t rpn_roi_losses_workspace_bytes(int B, int R, int C);
 int rpn_roi_losses(const float *d_cls_logits, const float *d_reg_pred, const int32_t *d_roi_labels, const float *d_roi_deltas, int B,
                    int R, int C, float *d_losses, float *d_grad_logits, float *d_grad_reg, void *d_workspace, size_t workspace_bytes,

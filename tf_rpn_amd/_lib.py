@@ -140,6 +140,9 @@ _SIGNATURES = {
     "rpn_roi_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "rpn_roi_targets": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_float] * 3 + [c_float_p, vp, vp, vp, vp, vp,
                                                                                                        ctypes.c_size_t, vp]),
+    "rpn_roi_sample_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "rpn_roi_sample_targets": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 6 + [ctypes.c_float] * 3 + [c_float_p, vp, vp, ctypes.c_int]
+                               + [vp] * 6 + [ctypes.c_size_t, vp]),
     "rpn_roi_losses_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "rpn_roi_losses": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "rpn_roi_decode_scores": (ctypes.c_int, [vp, vp, vp, vp, c_float_p] + [ctypes.c_int] * 3 + [vp, vp, vp]),

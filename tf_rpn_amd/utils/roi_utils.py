@@ -27,6 +27,8 @@ and, around them, what a second stage trains on and how its outputs become detec
 choice):
 
     calculate_roi_targets(rois, gt_boxes, gt_labels, hyper_params, ...)   -> rpn_roi_targets
+    sample_roi_targets(rois, gt_boxes, gt_labels, hyper_params, ...)      -> rpn_roi_sample_targets (the proposal-target layer:
+                                                                             the gt boxes are candidates, only the sampled RoIs go on)
     roi_losses(cls_logits, reg_pred, roi_labels, roi_deltas)              -> rpn_roi_losses (gradients under autograd)
     roi_detections(rois, reg_pred, cls_logits, variances, ...)            -> rpn_roi_decode_scores + rpn_combined_nms
 
@@ -383,6 +385,82 @@ def calculate_roi_targets(rois, gt_boxes, gt_labels, hyper_params, valid=None, t
                              vptr, L.ptr(rp), L.ptr(rn), L.ptr(deltas), L.ptr(labels), L.ptr(ws), ws_bytes, L.stream_ptr())
     L.check(st, "calculate_roi_targets")
     return L.from_device(deltas, was_np), L.from_device(labels, was_np)
+
+
+def sample_roi_targets(rois, gt_boxes, gt_labels, hyper_params, valid=None, add_gt=True, total_pos=None, total_neg=None, pos_iou=0.5,
+                       neg_iou=(0.1, 0.5), random_pos=None, random_neg=None, return_index=False):
+    """The proposal-target layer, one launch on the device (``rpn_roi_sample_targets``; contract in ``include/rpn_hip.h``): the
+    assignment of ``calculate_roi_targets`` over the proposals plus, with ``add_gt``, the gt boxes themselves, and only the sampled
+    RoIs handed on, as a dense batch of ``S = total_pos + total_neg`` rows per image.
+
+    Arguments as ``calculate_roi_targets``; the candidates of an image are its ``R`` RoIs followed by its ``G`` gt rows (``N = R + G``
+    with ``add_gt``, else ``R``), and ``random_pos`` / ``random_neg`` are (B,N) int32 >= 1.  A gt row is a candidate iff its label is
+    >= 1; it matches itself at IoU 1, so an image with a gt always has a positive.  Returns
+
+        rois_s (B,S,4) float32, roi_deltas (B,S,4) float32, roi_labels (B,S) int32, counts (B,2) int32 [n_sampled, n_pos]
+
+    and, with ``return_index=True``, the candidate index (B,S) int32 of every row (``>= R``: gt box ``index - R``).  Rows of an
+    image: the kept positives in ascending candidate index, then the kept negatives in ascending candidate index, then padding (box
+    and deltas +0.0, label -1, index -1).  ``counts[:, 0]`` is what the pools and ``roi_decode_scores`` take as ``valid``; the
+    labels are what ``roi_losses`` takes.  An image without a gt box has counts [0, 0] under the default thresholds: the pools write
+    zeros for it and it adds nothing to either loss.  No gradient flows to anything."""
+    rs, gs, ls = _shape(rois), _shape(gt_boxes), _shape(gt_labels)
+    if len(rs) != 3 or rs[2] != 4 or len(gs) != 3 or gs[2] != 4 or gs[0] != rs[0] or ls != gs[:2]:
+        raise ValueError("expected rois (B,R,4), gt_boxes (B,G,4), gt_labels (B,G); got %s %s %s" % (rs, gs, ls))
+    B, R, G = rs[0], rs[1], gs[1]
+    if B < 1 or R < 1 or G < 1:
+        raise ValueError("B, R and G must be >= 1 (gt_boxes needs at least one, possibly padded, row per image); got %d, %d, %d" % (B, R, G))
+    if valid is not None and _shape(valid) != (B,):
+        raise ValueError("valid must be (%d,) int32, got %s" % (B, _shape(valid)))
+    add_gt = bool(add_gt)
+    N = R + G if add_gt else R
+    for name, r in (("random_pos", random_pos), ("random_neg", random_neg)):
+        if r is not None and _shape(r) != (B, N):
+            raise ValueError("%s must be (%d, %d) int32, one priority per candidate (%d RoIs%s), got %s"
+                             % (name, B, N, R, " + %d gt rows" % G if add_gt else "", _shape(r)))
+    total_pos = int(hyper_params["total_pos_bboxes"] if total_pos is None else total_pos)
+    total_neg = int(hyper_params["total_neg_bboxes"] if total_neg is None else total_neg)
+    neg_lo, neg_hi = (float(v) for v in neg_iou)
+    if total_pos < 0 or total_neg < 0:
+        raise ValueError("total_pos and total_neg must be >= 0, got %d and %d" % (total_pos, total_neg))
+    S = total_pos + total_neg
+    if S < 1:
+        raise ValueError("total_pos + total_neg must be >= 1: the batch has that many rows per image")
+    if not (0.0 <= neg_lo <= neg_hi) or not float(pos_iou) >= 0.0:
+        raise ValueError("thresholds need 0 <= neg_iou[0] <= neg_iou[1] and pos_iou >= 0, got %r and %r" % (neg_iou, pos_iou))
+
+    def given(r, what):
+        if not isinstance(r, torch.Tensor):
+            r = torch.from_numpy(np.ascontiguousarray(np.asarray(r)))
+        if r.numel() and int(r.min()) < 1:          # key 0 marks a non-candidate: a priority <= 0 would silently drop the row
+            raise ValueError("%s: priorities must be >= 1" % what)
+        return r.to(device="cuda", dtype=torch.int32).contiguous()
+
+    r, was_np = L.to_device(rois.detach() if isinstance(rois, torch.Tensor) else rois)
+    g, _ = L.to_device(gt_boxes.detach() if isinstance(gt_boxes, torch.Tensor) else gt_boxes)
+    lab, _ = L.to_device(gt_labels, dtype=torch.int32)
+    v = L.to_device(valid, dtype=torch.int32)[0] if valid is not None else None
+
+    def draw():
+        return torch.randint(1, 2 ** 31 - 1, (B, N), dtype=torch.int32, device="cuda")
+
+    rp = given(random_pos, "random_pos") if random_pos is not None else draw()
+    rn = given(random_neg, "random_neg") if random_neg is not None else draw()
+    rois_s = torch.empty((B, S, 4), dtype=torch.float32, device="cuda")
+    deltas = torch.empty((B, S, 4), dtype=torch.float32, device="cuda")
+    labels = torch.empty((B, S), dtype=torch.int32, device="cuda")
+    index = torch.empty((B, S), dtype=torch.int32, device="cuda")
+    counts = torch.empty((B, 2), dtype=torch.int32, device="cuda")
+    lib = L.lib()
+    ws_bytes = int(lib.rpn_roi_sample_targets_workspace_bytes(B, R, G, int(add_gt)))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device="cuda")
+    _keep, vptr = L.host_floats(hyper_params["variances"])
+    st = lib.rpn_roi_sample_targets(L.ptr(r), L.ptr(v), L.ptr(g), L.ptr(lab), B, R, G, int(add_gt), total_pos, total_neg, float(pos_iou),
+                                    neg_lo, neg_hi, vptr, L.ptr(rp), L.ptr(rn), S, L.ptr(rois_s), L.ptr(labels), L.ptr(deltas),
+                                    L.ptr(index), L.ptr(counts), L.ptr(ws), ws_bytes, L.stream_ptr())
+    L.check(st, "sample_roi_targets")
+    out = (rois_s, deltas, labels, counts) + ((index,) if return_index else ())
+    return tuple(L.from_device(t, was_np) for t in out)
 
 
 def _check_losses(cs, ps, ls, ds):
