@@ -766,6 +766,44 @@ int rpn_roi_decode_scores(const float *d_rois, const int32_t *d_valid, const flo
                           const float *variances, int B, int R, int C, float *d_boxes, float *d_scores, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Soft-NMS (Bodla et al. 2017, "Improving Object Detection With One Line of Code"; TensorFlow's soft_nms_sigma) in place of
+ * rpn_combined_nms behind rpn_roi_decode_scores: overlapping boxes have their scores decayed instead of being deleted.  No
+ * reference counterpart.  d_boxes (B,N,q,4) with q in {1,C} and d_scores (B,N,C) as for rpn_combined_nms.
+ *
+ * Per image b and class c (class 0 is a class like any other here; rpn_roi_decode_scores gives it score 0), in float32:
+ *   thr = score_threshold >= 0 (a decay would RAISE a negative score).  A row n is a candidate iff scores[b,n,c] > thr (strict: a
+ *   NaN score never qualifies); cur[n] starts as that score.  While a candidate is live and fewer than max_per_class are selected:
+ *     m = the live candidate of highest cur, ties to the lower row index; emit (m, cur[m]); m is no longer live;
+ *     for every live n, with iou = the NMS-internal IoU of rpn_combined_nms (canonical corners, 0 when either area is <= 0,
+ *     inter / (area_m + area_n - inter), one rounding per operation) of box m and box n:
+ *       RPN_SOFT_NMS_LINEAR:    iou > iou_threshold:  cur[n] = fl(cur[n] * fl(1 - iou))
+ *       RPN_SOFT_NMS_GAUSSIAN:  iou > iou_threshold:  n is removed (TensorFlow's hard cut; a removal, not a product with 0)
+ *                               else iou > 0:         cur[n] = fl(cur[n] * expf(fl(fl(iou * iou) * k))),  k = (float)(-1.0 / (double)sigma)
+ *       every other case (a NaN iou, iou <= 0, a linear iou <= iou_threshold) leaves cur[n] unchanged;
+ *     n stays live iff cur[n] > thr.
+ *   iou_threshold = 1 with RPN_SOFT_NMS_GAUSSIAN is the paper's pure Gaussian; sigma = +inf (k = -0.0, every weight exactly 1) is
+ *   rpn_combined_nms at the same iou_threshold, bit for bit.  TensorFlow's soft_nms_sigma = s_tf is sigma = 2 s_tf here (TF
+ *   multiplies iou^2 by -0.5 / s_tf).
+ *   The emitted scores of a class are non-increasing.  The classes' lists of an image are merged by (emitted score descending,
+ *   class ascending, selection rank ascending), cut to max_total and padded with zeros.
+ * Outputs (M = max_total): d_out_boxes (B,M,4), clipped to [0,1] iff clip_boxes (the IoUs see the unclipped boxes);
+ *   d_out_scores (B,M) the DECAYED scores; d_out_classes (B,M) float32 or NULL; d_out_idx (B,M) int32 rows, -1 padded, or NULL;
+ *   d_out_valid (B) int32.
+ * Determinism: no floating-point atomics, fixed orders -- the same bits on every run, and image b's result depends on image b alone.
+ * Limits, refused with RPN_ERR_INVALID before any launch: N <= 4096 (the second stage has R <= 2000; the candidates of a pair
+ *   live in LDS, 96 + 28 N bytes); C * min(max_per_class, N) <= 16384 (the merge keeps every staged score in LDS); sigma > 0
+ *   (+inf allowed); iou_threshold >= 0; score_threshold >= 0; method one of the two below.
+ * d_workspace: rpn_soft_nms_workspace_bytes(...) bytes, REQUIRED (RPN_ERR_WORKSPACE otherwise): per (image, class) the selected
+ *   rows and their decayed scores.  Two launches: one workgroup per (image, class), then one per image.
+ * ---------------------------------------------------------------------------------- */
+typedef enum rpn_soft_nms_method { RPN_SOFT_NMS_LINEAR = 0, RPN_SOFT_NMS_GAUSSIAN = 1 } rpn_soft_nms_method;
+size_t rpn_soft_nms_workspace_bytes(int B, int N, int C, int max_per_class, int max_total);
+int rpn_soft_nms(const float *d_boxes, const float *d_scores, int B, int N, int q, int C, int max_per_class, int max_total,
+                 int method, float iou_threshold, float sigma, float score_threshold, int clip_boxes, float *d_out_boxes,
+                 float *d_out_scores, float *d_out_classes, int32_t *d_out_idx, int32_t *d_out_valid, void *d_workspace,
+                 size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Detection head: the fully-connected second stage on the RoI features (no reference counterpart: the reference stops at the
  * proposals; the architecture -- two ReLU layers and a class-specific box regressor, the Fast R-CNN head -- is this project's choice,
  * as the thresholds of rpn_roi_targets are).

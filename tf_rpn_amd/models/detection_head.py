@@ -395,7 +395,9 @@ class DetectionHead(O.OptimizerMixin):
 
     # ---- inference ----------------------------------------------------------------------
     def detect(self, rois, pooled, variances, valid=None, **nms_kwargs):
-        """``head(pooled)`` then ``roi_utils.roi_detections``: (boxes (B,M,4), scores (B,M), classes (B,M), valid_detections (B,))"""
+        """``head(pooled)`` then ``roi_utils.roi_detections``: (boxes (B,M,4), scores (B,M), classes (B,M), valid_detections (B,)).
+        ``nms_kwargs`` go to ``roi_detections`` unfiltered: the sizes and thresholds, and ``nms="linear"`` / ``"gaussian"`` with
+        ``sigma`` for Soft-NMS in place of the hard NMS."""
         with torch.no_grad():
             logits, deltas = self(pooled)
         return roi_utils.roi_detections(rois, deltas, logits, variances, valid=valid, **nms_kwargs)

@@ -230,7 +230,8 @@ class Proposer(object):
         ``max_total_size`` (300 unless given): ``propose_features`` at the head's pooling size, then ``head.detect`` (a
         ``models.DetectionHead``: its layers, ``roi_utils.roi_detections``) with this model's variances.  Everything on the current
         stream, no host synchronisation in between.  ``pooling``, ``sampling_ratio`` and ``extent`` go to ``propose_features``
-        (a head detects with the pooling it was trained on), ``nms_kwargs`` to ``roi_detections``."""
+        (a head detects with the pooling it was trained on), ``nms_kwargs`` to ``roi_detections`` (``nms="linear"`` /
+        ``"gaussian"`` and ``sigma`` select Soft-NMS there)."""
         rois, _scores, valid, pooled = self.propose_features(imgs, pooling_size=head.pooling_size, pooling=pooling,
                                                              sampling_ratio=sampling_ratio, extent=extent)
         return head.detect(rois, pooled, self.hyper_params["variances"], valid=valid, **nms_kwargs)

@@ -8,6 +8,10 @@
     normalize_bboxes / denormalize_bboxes(...)      -> rpn_scale_boxes        (bbox_utils.py:152-182)
     non_max_suppression(pred_bboxes, pred_labels, **kwargs) -> rpn_combined_nms (bbox_utils.py:48-70)
 
+and, without a counterpart in the reference, Soft-NMS (Bodla et al. 2017) with the same input and output shapes:
+
+    soft_non_max_suppression(pred_bboxes, pred_labels, max_output_size_per_class, max_total_size, ...) -> rpn_soft_nms
+
 Arguments may be torch tensors (any device; results come back as CUDA tensors) or numpy
 arrays (results come back as numpy).  Everything runs on the current torch HIP stream.
 There is no CPU path: without a GPU these functions raise ``RuntimeError``.
@@ -168,6 +172,71 @@ def non_max_suppression(pred_bboxes, pred_labels, **kwargs):
                                   int(clip_boxes), L.ptr(out_boxes), L.ptr(out_scores), L.ptr(out_classes),
                                   L.ptr(out_idx), L.ptr(out_valid), L.ptr(ws), ws_bytes, L.stream_ptr())
         L.check(st, "non_max_suppression")
+    res = (out_boxes, out_scores, out_classes, out_valid)
+    if return_indices:
+        res = res + (out_idx,)
+    return tuple(L.from_device(t, was_np) for t in res)
+
+
+SOFT_NMS_METHODS = {"linear": 0, "gaussian": 1}
+
+
+def soft_non_max_suppression(pred_bboxes, pred_labels, max_output_size_per_class, max_total_size, method="gaussian", sigma=0.5,
+                             iou_threshold=0.5, score_threshold=0.001, clip_boxes=True, return_indices=False):
+    """Per-image, per-class Soft-NMS (``rpn_soft_nms``; contract in ``include/rpn_hip.h``): the box of highest score is taken, the
+    scores of the boxes that overlap it are decayed, and so on until ``max_output_size_per_class`` boxes are taken or no score is
+    above ``score_threshold``.
+
+    ``method="linear"``: a score is multiplied by ``1 - iou`` when ``iou > iou_threshold``.  ``method="gaussian"``: a box with
+    ``iou > iou_threshold`` is removed (TensorFlow's hard cut; ``iou_threshold=1.0`` is the paper's pure Gaussian), any other
+    overlapping box has its score multiplied by ``exp(-iou^2 / sigma)``.  TensorFlow's ``soft_nms_sigma = s`` is ``sigma = 2 s``
+    here; ``sigma=float("inf")`` is hard NMS at ``iou_threshold``, bit for bit.
+
+    pred_bboxes (B, N, q, 4) with q == 1 or q == total_labels; pred_labels (B, N, total_labels); N <= 4096 and
+    ``total_labels * min(max_output_size_per_class, N) <= 16384``.  ``score_threshold`` must be >= 0.  Returns what
+    ``non_max_suppression`` returns -- (boxes (B,M,4), scores (B,M), classes (B,M), valid_detections (B,) int32), M =
+    ``max_total_size``, zero padded, + the selected rows (B,M) int32, -1 padded, with ``return_indices=True`` -- with the DECAYED
+    scores, ordered by them.  Runs on the current stream and does not synchronise."""
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (sorted(SOFT_NMS_METHODS), method))
+    max_per_class, M = int(max_output_size_per_class), int(max_total_size)
+    sigma, iou_thr, score_thr = float(sigma), float(iou_threshold), float(score_threshold)
+    if not sigma > 0.0:
+        raise ValueError("sigma must be > 0, got %r" % (sigma,))
+    if not iou_thr >= 0.0:
+        raise ValueError("iou_threshold must be >= 0, got %r" % (iou_thr,))
+    if not score_thr >= 0.0:
+        raise ValueError("score_threshold must be >= 0 (a decay would raise a negative score), got %r" % (score_thr,))
+    if max_per_class < 0 or M < 0:
+        raise ValueError("max_output_size_per_class and max_total_size must be >= 0")
+    bs = tuple(int(v) for v in (pred_bboxes.shape if hasattr(pred_bboxes, "shape") else np.shape(pred_bboxes)))
+    ss = tuple(int(v) for v in (pred_labels.shape if hasattr(pred_labels, "shape") else np.shape(pred_labels)))
+    if len(bs) != 4 or bs[-1] != 4 or len(ss) != 3:
+        raise ValueError("expected pred_bboxes (B,N,q,4) and pred_labels (B,N,C), got %s and %s" % (bs, ss))
+    B, N, q = bs[:3]
+    C = ss[2]
+    if ss[:2] != (B, N) or q not in (1, C) or C < 1:
+        raise ValueError("pred_bboxes %s and pred_labels %s are inconsistent" % (bs, ss))
+    lib = L.lib()
+    if B > 0 and M > 0:       # the library's limits, before anything is copied or launched
+        st = lib.rpn_soft_nms(None, None, 0, N, q, C, max_per_class, M, SOFT_NMS_METHODS[method], iou_thr, sigma, score_thr,
+                              int(bool(clip_boxes)), None, None, None, None, None, None, 0, None)
+        L.check(st, "soft_non_max_suppression")
+    boxes, was_np = L.to_device(pred_bboxes)
+    scores, _ = L.to_device(pred_labels)
+
+    out_boxes = torch.zeros((B, M, 4), dtype=torch.float32, device="cuda")
+    out_scores = torch.zeros((B, M), dtype=torch.float32, device="cuda")
+    out_classes = torch.zeros((B, M), dtype=torch.float32, device="cuda")
+    out_idx = torch.full((B, M), -1, dtype=torch.int32, device="cuda")
+    out_valid = torch.zeros((B,), dtype=torch.int32, device="cuda")
+    if B > 0 and M > 0:
+        ws_bytes = int(lib.rpn_soft_nms_workspace_bytes(B, N, C, max_per_class, M))
+        ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device="cuda")
+        st = lib.rpn_soft_nms(L.ptr(boxes), L.ptr(scores), B, N, q, C, max_per_class, M, SOFT_NMS_METHODS[method], iou_thr, sigma,
+                              score_thr, int(bool(clip_boxes)), L.ptr(out_boxes), L.ptr(out_scores), L.ptr(out_classes),
+                              L.ptr(out_idx), L.ptr(out_valid), L.ptr(ws), ws_bytes, L.stream_ptr())
+        L.check(st, "soft_non_max_suppression")
     res = (out_boxes, out_scores, out_classes, out_valid)
     if return_indices:
         res = res + (out_idx,)

@@ -316,7 +316,8 @@ def evaluate(proposer, head, feed, steps, evaluator, **nms_kwargs):
     """``steps`` batches of ``feed`` -- an iterator of (imgs, gt_boxes, gt_labels[, gt_difficult]) -- through ``proposer`` and
     ``head`` into ``evaluator`` (proposals and detections), then ``evaluator.result()``.  ``evaluator`` is a ``DetectionEvaluator``,
     a ``CocoEvaluator`` or a tuple / list of them: every batch goes to each (``update_proposals`` only to those that have it) and a
-    list of results comes back.  ``nms_kwargs`` go to ``head.detect``; ``max_total_size`` defaults to the (first) evaluator's
+    list of results comes back.  ``nms_kwargs`` go to ``head.detect`` and on to ``roi_utils.roi_detections`` (``nms="gaussian", sigma=0.5,
+    score_threshold=0.001`` scores Soft-NMS detections); ``max_total_size`` defaults to the (first) evaluator's
     ``max_detections``.  One synchronisation, at the end."""
     several = isinstance(evaluator, (tuple, list))
     evaluators = list(evaluator) if several else [evaluator]

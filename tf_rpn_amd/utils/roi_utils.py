@@ -30,7 +30,8 @@ choice):
     sample_roi_targets(rois, gt_boxes, gt_labels, hyper_params, ...)      -> rpn_roi_sample_targets (the proposal-target layer:
                                                                              the gt boxes are candidates, only the sampled RoIs go on)
     roi_losses(cls_logits, reg_pred, roi_labels, roi_deltas)              -> rpn_roi_losses (gradients under autograd)
-    roi_detections(rois, reg_pred, cls_logits, variances, ...)            -> rpn_roi_decode_scores + rpn_combined_nms
+    roi_detections(rois, reg_pred, cls_logits, variances, ...)            -> rpn_roi_decode_scores + rpn_combined_nms (nms="hard") or
+                                                                             rpn_soft_nms (nms="linear" / "gaussian")
 
 Arguments may be torch tensors (any device; results come back as CUDA tensors) or numpy arrays (results come back as numpy).
 Everything runs on the current torch HIP stream.  There is no CPU path: without a GPU ``roi_pooling`` raises ``RuntimeError``.
@@ -551,18 +552,31 @@ def roi_decode_scores(rois, reg_pred, cls_logits, variances, valid=None):
 
 
 def roi_detections(rois, reg_pred, cls_logits, variances, valid=None, max_output_size_per_class=100, max_total_size=300,
-                   iou_threshold=0.5, score_threshold=0.5, return_indices=False):
+                   iou_threshold=0.5, score_threshold=0.5, return_indices=False, nms="hard", sigma=0.5):
     """A trained head's outputs -> detections: ``roi_decode_scores`` then ``bbox_utils.non_max_suppression`` with class-specific
     boxes.  Returns (boxes (B,M,4) clipped to [0, 1], scores (B,M), classes (B,M), valid_detections (B,) int32), M =
     ``max_total_size`` (+ the selected RoI indices (B,M) int32 with ``return_indices=True``).  ``score_threshold`` must be above 0:
-    background and padding rows carry a score of exactly 0 and must never be selected."""
+    background and padding rows carry a score of exactly 0 and must never be selected.
+
+    ``nms``: ``"hard"`` (the default) deletes every box whose IoU with a selected one is above ``iou_threshold``; ``"linear"`` and
+    ``"gaussian"`` run ``bbox_utils.soft_non_max_suppression`` with that method, ``iou_threshold`` and ``sigma`` (> 0; used by
+    ``"gaussian"`` only) instead: overlapping boxes keep a decayed score, and the scores returned are the decayed ones."""
+    if nms not in ("hard",) + tuple(bbox_utils.SOFT_NMS_METHODS):
+        raise ValueError("nms must be 'hard', 'linear' or 'gaussian', got %r" % (nms,))
     if not float(score_threshold) > 0.0:
         raise ValueError("score_threshold must be > 0 (background and padding rows have score 0), got %r" % (score_threshold,))
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be > 0, got %r" % (sigma,))
     was_np = not isinstance(rois, torch.Tensor)
     if was_np:
         rois = torch.from_numpy(np.ascontiguousarray(np.asarray(rois, dtype=np.float32)))
     boxes, scores = roi_decode_scores(rois, reg_pred, cls_logits, variances, valid=valid)          # stay on the device
-    res = bbox_utils.non_max_suppression(boxes, scores, max_output_size_per_class=int(max_output_size_per_class),
-                                         max_total_size=int(max_total_size), iou_threshold=float(iou_threshold),
-                                         score_threshold=float(score_threshold), return_indices=bool(return_indices))
+    if nms == "hard":
+        res = bbox_utils.non_max_suppression(boxes, scores, max_output_size_per_class=int(max_output_size_per_class),
+                                             max_total_size=int(max_total_size), iou_threshold=float(iou_threshold),
+                                             score_threshold=float(score_threshold), return_indices=bool(return_indices))
+    else:
+        res = bbox_utils.soft_non_max_suppression(boxes, scores, int(max_output_size_per_class), int(max_total_size), method=nms,
+                                                  sigma=float(sigma), iou_threshold=float(iou_threshold),
+                                                  score_threshold=float(score_threshold), return_indices=bool(return_indices))
     return tuple(L.from_device(t, was_np) for t in res)
