@@ -155,6 +155,36 @@ int rpn_decode_nms(const float *d_anchors, const float *d_deltas, const float *v
                    void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The proposal layer's filters in front of the NMS (Faster R-CNN's proposal layer: decode and clip, drop boxes smaller than
+ * min_size, keep the pre_nms_topN best scored, NMS, keep post_nms_topN).  No reference counterpart.  rpn_decode_nms does the
+ * decode, the NMS and the last cut; this entry does the two filters between them, as a MASK over the scores:
+ *     rpn_proposal_filter(scores -> masked);  rpn_decode_nms(masked, the same score_threshold and clip_boxes)
+ * is the proposal layer.  float32 throughout; image b's outputs depend on image b alone.
+ *   d_scores (B,A) objectness; d_deltas (B,A,4) raw head output and d_anchors (A,4), read only with use_min_size (both may be
+ *   NULL otherwise: nothing is decoded); variances: HOST pointer to 4 floats, or NULL for no scaling.
+ * Anchor i of image b is a CANDIDATE iff
+ *   scores[b,i] > score_threshold   (strict; a NaN score is never a candidate: rpn_decode_nms's own rule), and
+ *   with use_min_size != 0: box = what rpn_decode returns for the anchor, bit for bit (get_bboxes_from_deltas on
+ *   deltas * variances), each coordinate clipped to [0, 1] (v < 0 ? 0 : v > 1 ? 1 : v) iff clip_boxes != 0;
+ *     (box.y2 - box.y1) >= min_h && (box.x2 - box.x1) >= min_w,   each difference one float32 subtraction.
+ *   A NaN side fails the test (a NaN or infinite delta, for instance).  A side exactly equal to the minimum passes.
+ * Candidates are ranked by score descending as floats compare (-0.0 ties with +0.0, +inf is first), ties to the lower index:
+ * the NMS's own order.  With pre_nms_topn > 0 the first pre_nms_topn candidates of that order are KEPT, exactly that many
+ * when there are more (a tie across the cut is split by index, never rounded up to a bin); with pre_nms_topn <= 0 every
+ * candidate is kept.
+ * Outputs: d_masked_scores (B,A) = scores[b,i], bit for bit, where kept and -inf elsewhere (-inf is never > score_threshold);
+ *   it must not overlap d_scores.  d_kept (B,) int32 = the number of kept anchors, or NULL.
+ * One launch of one workgroup per image on `stream`; no host synchronisation, no floating-point atomics: the same bits on every
+ * run.  d_workspace: rpn_proposal_filter_workspace_bytes(B, A) bytes (currently 0: the output row is the passes' staging buffer;
+ * may be NULL then).  RPN_ERR_INVALID before any device use for negative sizes, A > 2^30, a NULL pointer that is needed,
+ * overlapping score buffers, and with use_min_size a min_h or min_w that is negative or NaN.
+ * ---------------------------------------------------------------------------------- */
+size_t rpn_proposal_filter_workspace_bytes(int B, int A);
+int rpn_proposal_filter(const float *d_anchors, const float *d_deltas, const float *variances, const float *d_scores, int B, int A,
+                        int pre_nms_topn, int use_min_size, float min_h, float min_w, float score_threshold, int clip_boxes,
+                        float *d_masked_scores, int32_t *d_kept, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * calculate_rpn_actual_outputs(anchors, gt_boxes, gt_labels, hyper_params)   utils/train_utils.py:84-144
  *   (+ randomly_select_xyz_mask :50-65) -- the consumer of generate_iou_map; the (B,A,G) map is never written.
  *   d_gt_labels (B,G) int32, -1 = padding.  d_random_pos / d_random_neg (B,A) int32 >= 1 replace the two

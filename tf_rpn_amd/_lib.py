@@ -48,6 +48,9 @@ _SIGNATURES = {
     "rpn_decode_nms": (ctypes.c_int, [vp, vp, c_float_p, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, vp, vp, vp, vp, vp,
                                       ctypes.c_size_t, vp]),
+    "rpn_proposal_filter_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 2),
+    "rpn_proposal_filter": (ctypes.c_int, [vp, vp, c_float_p, vp] + [ctypes.c_int] * 4 + [ctypes.c_float] * 3 + [ctypes.c_int, vp, vp, vp,
+                                           ctypes.c_size_t, vp]),
     "rpn_soft_nms_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "rpn_soft_nms": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 7 + [ctypes.c_float] * 3 + [ctypes.c_int, vp, vp, vp, vp, vp, vp,
                                     ctypes.c_size_t, vp]),

@@ -71,7 +71,13 @@ class Proposer(object):
 
     def __init__(self, backbone="vgg16", hyper_params=None, weights="synthetic", precision="f32",
                  max_batch=8, iou_threshold=0.7, score_threshold=float("-inf"), seed=1, overlap_nms=False,
-                 check_range=True, avoid_streams=()):
+                 check_range=True, avoid_streams=(), pre_nms_topn=None, min_size=None):
+        # the proposal layer's filters in front of the NMS (bbox_utils.filter_proposals: ``min_size`` in the normalised units of the
+        # boxes); both None = no filter launch at all.  Checked before anything is built or launched.
+        self._filter = None
+        if pre_nms_topn is not None or min_size is not None:
+            self._filter = bbox_utils.check_proposal_filter(pre_nms_topn, min_size)
+        self.pre_nms_topn, self.min_size = pre_nms_topn, min_size
         if backbone == "mobilenet_v2":
             from .models.rpn_mobilenet_v2 import get_model
         else:
@@ -114,6 +120,14 @@ class Proposer(object):
         self._nms_ws_bytes = max(int(L.lib().rpn_nms_workspace_bytes(b, self.total_anchors, 1, M, M))
                                  for b in range(1, self.max_batch + 1))
         self._nms_ws = torch.empty((max(self._nms_ws_bytes, 16),), dtype=torch.uint8, device=dev)
+        if self._filter is not None:
+            # masked scores and the filter's scratch, like the NMS scratch: one buffer each, the launches are ordered on one stream.
+            # The library asks for no scratch today: nothing is allocated then and NULL is passed.
+            self._masked = torch.empty((max_batch, self.total_anchors), dtype=torch.float32, device=dev)
+            self._filter_ws_bytes = max(int(L.lib().rpn_proposal_filter_workspace_bytes(b, self.total_anchors))
+                                        for b in range(1, self.max_batch + 1))
+            self._filter_ws = (torch.empty((self._filter_ws_bytes,), dtype=torch.uint8, device=dev)
+                               if self._filter_ws_bytes else None)
         # optional 2-stage pipeline across batches: the NMS of batch k (one workgroup per image: 8 of 256 CUs)
         # runs on a side stream while the conv stack of batch k+1 runs on the main stream.  Head outputs and
         # proposal buffers are double buffered; ordering is by HIP events only (no host synchronisation).
@@ -162,7 +176,17 @@ class Proposer(object):
 
     def decode_nms(self, deltas, scores, B, ob, osc, oi, ov):
         """Fused ``deltas *= variances`` -> decode -> NMS(topn) of (B,A,4) / (B,A) head outputs on the current stream
-        (predictor.py:55-56 + utils/bbox_utils.py:48-70 -> rpn_decode_nms)."""
+        (predictor.py:55-56 + utils/bbox_utils.py:48-70 -> rpn_decode_nms).  With ``pre_nms_topn`` / ``min_size`` the proposal filter
+        (rpn_proposal_filter) masks the scores first, on the same stream."""
+        if self._filter is not None:
+            topn, use_min, min_h, min_w = self._filter
+            masked = self._masked[:B]
+            st = L.lib().rpn_proposal_filter(L.ptr(self.anchors) if use_min else None, L.ptr(deltas) if use_min else None,
+                                             self._vptr, L.ptr(scores), B, self.total_anchors, topn, use_min, min_h, min_w,
+                                             self.score_threshold, 1, L.ptr(masked), None, L.ptr(self._filter_ws),
+                                             self._filter_ws_bytes, L.stream_ptr())
+            L.check(st, "rpn_proposal_filter")
+            scores = masked
         st = L.lib().rpn_decode_nms(L.ptr(self.anchors), L.ptr(deltas), self._vptr, L.ptr(scores), B,
                                     self.total_anchors, self.topn, self.iou_threshold, self.score_threshold, 1,
                                     L.ptr(ob), L.ptr(osc), L.ptr(oi), L.ptr(ov), L.ptr(self._nms_ws), self._nms_ws_bytes,

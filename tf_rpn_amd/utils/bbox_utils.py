@@ -243,11 +243,86 @@ def soft_non_max_suppression(pred_bboxes, pred_labels, max_output_size_per_class
     return tuple(L.from_device(t, was_np) for t in res)
 
 
+def check_proposal_filter(pre_nms_topn, min_size):
+    """Validate the proposal layer's two filter arguments (no device involved) -> (topn int, 0 = no cut; use_min_size 0 / 1;
+    min_h; min_w).  ``pre_nms_topn``: None or a positive integer.  ``min_size``: None, a float or (min_h, min_w), >= 0, in the
+    normalised units of the boxes."""
+    topn = 0
+    if pre_nms_topn is not None:
+        if isinstance(pre_nms_topn, bool) or not isinstance(pre_nms_topn, (int, np.integer)) or int(pre_nms_topn) < 1:
+            raise ValueError("pre_nms_topn must be None or a positive integer, got %r" % (pre_nms_topn,))
+        topn = min(int(pre_nms_topn), 2 ** 31 - 1)
+    if min_size is None:
+        return topn, 0, 0.0, 0.0
+    try:
+        hw = [float(v) for v in min_size] if isinstance(min_size, (tuple, list, np.ndarray)) else [float(min_size)] * 2
+    except (TypeError, ValueError):
+        raise ValueError("min_size must be None, a number or (min_h, min_w), got %r" % (min_size,))
+    if len(hw) != 2 or not all(v >= 0.0 for v in hw):                  # (NaN >= 0 is False)
+        raise ValueError("min_size must be None, a number >= 0 or (min_h, min_w) >= 0, got %r" % (min_size,))
+    return topn, 1, hw[0], hw[1]
+
+
+def _shape_of(x):
+    return tuple(int(v) for v in (x.shape if hasattr(x, "shape") else np.shape(x)))
+
+
+def _check_proposal_shapes(anchors, deltas, scores):
+    a, d, s = _shape_of(anchors), _shape_of(deltas), _shape_of(scores)
+    if len(d) != 3 or d[-1] != 4 or a != (d[1], 4) or s != d[:2]:
+        raise ValueError("inconsistent shapes: anchors %s deltas %s scores %s" % (a, d, s))
+    return d[0], d[1]
+
+
+def _launch_proposal_filter(a, d, s, vptr, B, A, filt, score_threshold, clip_boxes, masked, kept):
+    topn, use_min, min_h, min_w = filt
+    ws_bytes = int(L.lib().rpn_proposal_filter_workspace_bytes(B, A))          # 0 today: NULL is passed and nothing is allocated
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device="cuda") if ws_bytes else None
+    st = L.lib().rpn_proposal_filter(L.ptr(a) if use_min else None, L.ptr(d) if use_min else None, vptr, L.ptr(s), B, A, topn,
+                                     use_min, min_h, min_w, float(score_threshold), int(bool(clip_boxes)), L.ptr(masked),
+                                     L.ptr(kept), L.ptr(ws), ws_bytes, L.stream_ptr())
+    L.check(st, "filter_proposals")
+
+
+def filter_proposals(anchors, deltas, scores, variances, pre_nms_topn=None, min_size=None, score_threshold=float("-inf"),
+                     clip_boxes=True):
+    """The proposal layer's filters in front of the NMS (``rpn_proposal_filter``; contract in ``include/rpn_hip.h``): raw head
+    deltas (B,A,4) and objectness (B,A) -> (masked_scores (B,A), kept (B,) int32).
+
+    An anchor is a candidate iff its score is > ``score_threshold`` and, with ``min_size``, its decoded box (clipped to [0, 1] iff
+    ``clip_boxes``) is at least ``min_h`` high and ``min_w`` wide.  ``min_size`` is a float or ``(min_h, min_w)`` in the NORMALISED
+    units of the boxes (16 px at 500 x 500 is ``16 / 500``); ``None`` switches the size test off.  With ``pre_nms_topn`` only that
+    many best-scored candidates are kept (ties to the lower index, exactly); ``None`` keeps them all.  ``masked_scores`` holds the
+    score where kept and -inf elsewhere, so ``decode_and_nms`` on it with the same threshold is the whole proposal layer
+    (``decode_and_nms(..., pre_nms_topn=, min_size=)`` does both).  Runs on the current stream and does not synchronise."""
+    filt = check_proposal_filter(pre_nms_topn, min_size)
+    B, A = _check_proposal_shapes(anchors, deltas, scores)
+    d, was_np = L.to_device(deltas)
+    s, _ = L.to_device(scores)
+    a, _ = L.to_device(anchors)
+    masked = torch.empty((B, A), dtype=torch.float32, device="cuda")
+    kept = torch.zeros((B,), dtype=torch.int32, device="cuda")
+    vptr = None
+    if variances is not None:
+        _keep, vptr = L.host_floats(variances)
+    if B > 0:
+        _launch_proposal_filter(a, d, s, vptr, B, A, filt, score_threshold, clip_boxes, masked, kept)
+    return L.from_device(masked, was_np), L.from_device(kept, was_np)
+
+
 def decode_and_nms(anchors, deltas, scores, variances, max_total_size, iou_threshold=0.5,
-                   score_threshold=float("-inf"), clip_boxes=True):
+                   score_threshold=float("-inf"), clip_boxes=True, pre_nms_topn=None, min_size=None):
     """predictor.py:52-56 followed by NMS, in one kernel: raw head deltas (B,A,4) and objectness
     (B,A) -> (boxes (B,M,4), scores (B,M), indices (B,M) int32, valid (B,) int32).  Decoded boxes
-    are never written to HBM (-> rpn_decode_nms)."""
+    are never written to HBM (-> rpn_decode_nms).
+
+    ``pre_nms_topn`` / ``min_size`` (see ``filter_proposals``; both ``None`` by default: the calls above and nothing else) put the
+    proposal layer's filters in front: ``rpn_proposal_filter`` masks the scores, then the same ``rpn_decode_nms`` runs on the masked
+    scores, both on the current stream without a synchronisation or a host copy."""
+    filt = None
+    if pre_nms_topn is not None or min_size is not None:
+        filt = check_proposal_filter(pre_nms_topn, min_size)
+        _check_proposal_shapes(anchors, deltas, scores)
     d, was_np = L.to_device(deltas)
     s, _ = L.to_device(scores)
     a, _ = L.to_device(anchors)
@@ -264,6 +339,10 @@ def decode_and_nms(anchors, deltas, scores, variances, max_total_size, iou_thres
     if variances is not None:
         _keep, vptr = L.host_floats(variances)
     if B > 0 and M > 0:
+        if filt is not None:
+            masked = torch.empty((B, A), dtype=torch.float32, device="cuda")
+            _launch_proposal_filter(a, d, s, vptr, B, A, filt, score_threshold, clip_boxes, masked, None)
+            s = masked
         ws_bytes = int(L.lib().rpn_nms_workspace_bytes(B, A, 1, M, M))
         ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device="cuda")
         st = L.lib().rpn_decode_nms(L.ptr(a), L.ptr(d), vptr, L.ptr(s), B, A, M, float(iou_threshold),
